@@ -2,19 +2,25 @@
 """Headline benchmark: training graphs/sec of the gnn-mlp detector hot path on MI355X.
 
     python bench.py --gpus 1 --steps 10 --warmup 3
+    python bench.py --gpus 1 --steps 10 --warmup 3 --full            # + every secondary measurement (below)
+    python bench.py --gpus 1 --steps 10 --warmup 3 --dump-outputs DIR  # + the last timed step's results as DIR/*.npy
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
     python bench.py --gpus N ...            # no launcher: re-runs itself under torch.distributed.run (self_launch)
     python bench.py --gpus 2 --dry-launch   # launcher self-test, CPU / gloo when no GPU is visible
 
 One "step" = forward + backward + gradient all-reduce (N > 1) + clip + Adam on one minibatch of
-synthetic PyPI-shaped code graphs that is already resident in HBM.  Workload at every N (weak
+synthetic PyPI-shaped code graphs that is already resident in HBM, every step from the same
+seeded parameters (so that its outputs are reproducible; see make_step).  Workload at every N (weak
 scaling): BASELINE.json configs[1] per GPU -- gnn-mlp, hidden 128, 8 MP layers, 16 edge types,
-64 graphs x (2000 nodes, 10000 messages), dropout 0.2, fp32.  Rank 0 prints ONE JSON line:
-the contract's fields + `roofline` (dominant kernel kind of a serial profiling pass, priced against the
-ceiling that binds), `box` (what this chip delivers: step clock / power, calibration kernels),
-`also` (configs[2] shard, the reference's 30 000-node regime, the other activation placement, the
-bf16x6 split, configs[4] seq-great), `cpu_baseline` (CPU oracle through ModelTrainer.train).
+64 graphs x (2000 nodes, 10000 messages), dropout 0.2, fp32.  Rank 0 prints ONE JSON line with
+the contract's fields (`value`, `ms_per_step` of the --steps timed steps, ...).  A plain run does
+only that: set up, warm up, time, dump (--dump-outputs), print.  --full adds, after the timed
+steps, `roofline` (dominant kernel kind of a serial profiling pass, priced against the ceiling
+that binds), `box` (what this chip delivers: step clock / power, calibration kernels),
+`predict_graphs_per_s` (forward only), `also` (configs[2] shard, the reference's 30 000-node
+regime, the other activation placement, the bf16x6 split, configs[4] seq-great) and
+`cpu_baseline` (CPU oracle through ModelTrainer.train); without it those fields are null.
 """
 import argparse
 import json
@@ -392,6 +398,41 @@ def dry_launch(expected_world: int) -> int:
     return 0 if ok else 1
 
 
+DUMP_BUDGET_BYTES = 60 << 20  # array data of one --dump-outputs directory (.npy headers on top stay far below 64 MB in all)
+
+
+def step_outputs(module, loss):
+    """What a caller of the timed step holds after it: the loss, the parameters the optimiser wrote and the gradients the
+    backward pass computed (name -> tensor)."""
+    out = {"loss": loss.detach()}
+    for name, p in module.named_parameters():
+        out[f"param.{name}"] = p.detach()
+        if p.grad is not None:
+            out[f"grad.{name}"] = p.grad.detach()
+    return out
+
+
+def dump_outputs(out_dir, arrays, budget_bytes=DUMP_BUDGET_BYTES, seed=0):
+    """Writes each tensor of `arrays` as out_dir/<name>.npy in float32, `budget_bytes` of data in all.  The smallest arrays
+    are written whole; one larger than its share of what is left becomes a fixed, seeded sample of its flattened elements
+    (the same positions on every run, in increasing order)."""
+    import numpy as np
+    import torch
+
+    os.makedirs(out_dir, exist_ok=True)
+    left = budget_bytes // 4
+    todo = sorted(arrays.items(), key=lambda kv: (kv[1].numel(), kv[0]))
+    for i, (name, t) in enumerate(todo):
+        share = left // (len(todo) - i)
+        t = t.float()
+        if t.numel() > share:
+            pick = torch.randperm(t.numel(), generator=torch.Generator().manual_seed(seed))[:share].sort().values
+            t = t.reshape(-1)[pick.to(t.device)]
+        a = t.cpu().numpy()
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+        left -= a.size
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -419,6 +460,12 @@ def main():
                          "terms with power-of-two tensor scales (default, csrc/bl_gemm_h3.hip) or three bf16 planes / six terms (rounds 2-5)")
     ap.add_argument("--serial", action="store_true", help="weight-gradient GEMMs on the main stream everywhere (no side-stream overlap): the run "
                     "whose rocprofv3 --kernel-trace --stats averages are the exclusive kernel times the roofline quotes")
+    ap.add_argument("--full", action="store_true", help="after the timed steps also measure the roofline (two profiling passes), the box "
+                    "calibration, the forward-only rate, the `also` configurations and the CPU baseline (each can be left out by its --no-* "
+                    "option); a plain run measures the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps write the last step's loss, updated "
+                    f"parameters and gradients as DIR/<name>.npy (float32; {DUMP_BUDGET_BYTES >> 20} MiB of data at most: larger arrays "
+                    "as a fixed, seeded sample)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-box", action="store_true", help="skip the box calibration (MFMA loop, HBM copy, clock / power sampling) after the timed region")
     ap.add_argument("--unfused-node-bwd", action="store_true", help="A/B: the node update's backward chain as three kernels "
@@ -433,6 +480,8 @@ def main():
     ap.add_argument("--dry-launch", action="store_true", help="launcher self-test: start the --gpus ranks, initialise the process group "
                     "(gloo on CPU when there is no GPU), all-reduce one number, print one JSON line and exit -- no kernels")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` without a launcher: become the launcher.  One process per GPU under
         # torch.distributed.run on this node, rendezvous on 127.0.0.1 (the container host name may not resolve).
@@ -500,8 +549,17 @@ def main():
         return module_, mb_, opt_
 
     def make_step(module_, mb_, opt_, graphs):
+        # Every step trains from the same parameters, so that a run's outputs are the same in every run up to the rounding of
+        # the kernels' unordered fp32 atomics.  Chained updates would carry that rounding into the next step's parameters,
+        # where the max aggregation turns last-bit differences into other winners: two runs of 25 chained steps differ by
+        # ~1 % in their gradients.  The restore is one device copy of the flat parameter buffer; Adam's moments, its step
+        # count and the dropout seeds advance as in training.
+        start_params = opt_.flat_param.clone()
+
         def step_():
-            opt_.zero_grad()
+            opt_.zero_grad()  # (joins the side stream: nothing reads the parameters any more)
+            opt_.flat_param.copy_(start_params)
+            hip_ops.invalidate_weight_packs()
             if world > 1:
                 opt_.begin_data_parallel_step(graphs)
             loss_ = module_(**mb_)
@@ -619,6 +677,8 @@ def main():
     elapsed = D.max_over_ranks(time.perf_counter() - t0, device)
     calls_per_step = (hip_ops.CALL_COUNT - calls0) / args.steps
     last_loss = float(loss.detach())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, step_outputs(module, loss))  # before any further step overwrites them
 
     # Per-kernel durations, measured live with HIP events on the stream each kernel is launched on (the C library
     # brackets every launch inside its per-layer entry points, hip_ops.KernelTimer the rest).  Two more passes over
@@ -627,17 +687,18 @@ def main():
     #       overlap and are flagged;
     #   (b) serial (side stream off): every span is exclusive kernel time.  The roofline entry is taken from (b):
     #       the kernel with the largest exclusive share of the step.
-    kern_overlap, _ = profile_pass(step, True)      # every rank steps (the optimiser all-reduces); rank 0 reports
-    kern, serial_step_s = profile_pass(step, False)
-    if world > 1:
-        dist.barrier()
+    if args.full:
+        kern_overlap, _ = profile_pass(step, True)      # every rank steps (the optimiser all-reduces); rank 0 reports
+        kern, serial_step_s = profile_pass(step, False)
+        if world > 1:
+            dist.barrier()
 
     # What this box delivers (outside the timed region, rank 0's device): boxes of the pool differ by several
     # per cent in the clock they hold at the package power limit.  (i) shader clock + package power sampled through librocm_smi64
     # while plain training steps run (no event records), (ii) two fixed kernels of the library: a dense bf16 MFMA loop from
     # registers and a 2 GiB HBM copy.  The roofline entry carries `frac_calibrated` = achieved / (this box's calibrated ceiling).
     box = None
-    if not args.no_box:
+    if args.full and not args.no_box:
         from buglab.models.hip_ops.calibration import SmiSampler, box_calibration
 
         torch.cuda.synchronize()
@@ -664,7 +725,7 @@ def main():
             module._compute_repair_logprobs(gout, mb["target_rewrites"], mb["rewrite_to_location_group"],
                                             mb["candidate_symbol_to_location_group"], mb["swapped_pair_to_call_location_group"],
                                             mb["repair_group_ptr"], mb["repair_group_items"])
-        if not args.no_predict:
+        if args.full and not args.no_predict:
             predict_pass()
             torch.cuda.synchronize()
             tp = time.perf_counter()
@@ -678,7 +739,7 @@ def main():
     # optimiser all-reduces): configs[2]'s per-GPU shard (hidden 256, 32 graphs per GPU -- 256 graphs over 8 GPUs) and, on
     # one GPU, configs[4] (seq-great).  Each on its own model / minibatch after the headline run has been measured.
     also = {}
-    if not args.no_also and not seq and args.hidden == 128 and args.degree == "uniform":
+    if args.full and not args.no_also and not seq and args.hidden == 128 and args.degree == "uniform":
         hip_ops.join_side_stream()
         torch.cuda.synchronize()
         del module, mb, opt, step
@@ -712,8 +773,10 @@ def main():
         total_graphs = args.graphs * world * args.steps
         fwd_flop, fwd_bytes = fwd_work(args)
         value = total_graphs / elapsed
-        roof = build_roofline(attach_message_gemm_bytes(kern, args, prof_steps), kern_overlap, prof_steps, serial_step_s, value / world,
-                              fwd_flop, fwd_bytes, dataflow=dataflow_of(args), graphs_per_step=args.graphs)
+        roof = None
+        if args.full:
+            roof = build_roofline(attach_message_gemm_bytes(kern, args, prof_steps), kern_overlap, prof_steps, serial_step_s, value / world,
+                                  fwd_flop, fwd_bytes, dataflow=dataflow_of(args), graphs_per_step=args.graphs)
         if box is not None:
             calibrate_rooflines(box, roof, also, value / world)
         line = {
@@ -752,7 +815,8 @@ def main():
             "roofline": roof,
             "box": box,
             "also": also or None,
-            "cpu_baseline": None if (args.no_cpu_baseline or world > 1) else (cpu_baseline_seq(args) if args.model == "seq-great" else None if seq else cpu_baseline(args)),
+            "full": args.full,
+            "cpu_baseline": None if (not args.full or args.no_cpu_baseline or world > 1) else (cpu_baseline_seq(args) if args.model == "seq-great" else None if seq else cpu_baseline(args)),
         }
         print(json.dumps(line), flush=True)
     if world > 1:

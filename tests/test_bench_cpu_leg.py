@@ -126,3 +126,27 @@ def test_dataflow_bytes_of_a_step_add_up():
     # the bf16x6 split packs 6 instead of 4 bytes per operand element: more bytes, same structure
     total6, _ = bench.dataflow_bytes_per_step(H, layers, N, E, T, 6.0)
     assert total < total6 < 1.1 * total
+
+
+def test_dump_outputs_keeps_small_arrays_whole_and_samples_large_ones_within_budget(tmp_path):
+    """bench.py --dump-outputs: every array lands as <name>.npy in float32, the data stay within the budget, arrays that fit their
+    share are written whole, a larger one becomes a sample of its flattened elements at the same positions on every run."""
+    import numpy as np
+
+    import bench
+
+    g = torch.Generator().manual_seed(3)
+    arrays = {"loss": torch.tensor(1.5), "param.small": torch.randn(7, 5, generator=g),
+              "param.big": torch.randn(300, 100, generator=g), "grad.big": torch.randn(50_000, generator=g, dtype=torch.float64)}
+    budget = 4 * 20_000
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), arrays, budget_bytes=budget)
+    got = {f[:-4]: np.load(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")}
+    assert set(got) == set(arrays) and all(a.dtype == np.float32 for a in got.values())
+    assert sum(a.nbytes for a in got.values()) <= budget
+    assert got["loss"] == np.float32(1.5) and np.array_equal(got["param.small"], arrays["param.small"].numpy())
+    for name in ("param.big", "grad.big"):
+        a, flat = got[name], arrays[name].reshape(-1).float().numpy()
+        assert 0 < a.size < flat.size
+        assert np.isin(a, flat).all()
+        assert np.array_equal(a, np.load(tmp_path / "b" / f"{name}.npy"))

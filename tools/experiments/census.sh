@@ -5,7 +5,7 @@ R=$(pwd); O=$R/gpurun_out; mkdir -p $O
 export TMPDIR=/tmp
 cd /tmp
 rm -rf /tmp/prof_census
-rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_census -o s -- python $R/bench.py --serial --steps 6 --warmup 2 --no-cpu-baseline --no-predict --no-also > $O/${TAG}_census_rocprof.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_census -o s -- python $R/bench.py --full --serial --steps 6 --warmup 2 --no-cpu-baseline --no-predict --no-also > $O/${TAG}_census_rocprof.log 2>&1
 f=$(find /tmp/prof_census -name '*kernel_stats.csv' | head -1)
 [ -n "$f" ] && cp $f $O/${TAG}_census_kernel_stats.csv
 cd $R

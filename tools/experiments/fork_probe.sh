@@ -24,7 +24,7 @@ for v in product forkafter_dgrad forkafter_sums product forkafter_dgrad forkafte
   if [ $v = product ]; then unset BL_HIP_LIB; else export BL_HIP_LIB=$B/libbuglab_hip_$v.so; fi
   echo "== $v"
   for cfg in "" "--hidden 256 --graphs 32" "--graphs 15"; do
-    python bench.py --no-cpu-baseline --no-also --no-box --no-predict $cfg 2>/dev/null | python -c "
+    python bench.py --full --no-cpu-baseline --no-also --no-box --no-predict $cfg 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('  $cfg', d['value'], d['unit'], d['ms_per_step'], 'ms')"
   done

@@ -23,7 +23,7 @@ rm -f $C/bl_gemm_h3r.hip $C/bl_gemm_h3w.hip $T/bl_gemm_h3r_switches.hip $T/bl_ge
 for rep in 1 2; do
   for v in base occ4rows occ4wgrad; do
     if [ $v = base ]; then unset BL_HIP_LIB; else export BL_HIP_LIB=$T/build/libbuglab_hip_$v.so; fi
-    python $R/bench.py --no-cpu-baseline --no-also --no-predict 2>/dev/null | python -c "
+    python $R/bench.py --full --no-cpu-baseline --no-also --no-predict 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1]); k = d['roofline']['kernels_serial']
 print('$v', d['value'], d['ms_per_step'], {n: k[n]['ms_per_step'] for n in ('msg_dgrad_h3', 'msg_gemm_h3', 'msg_wgrad_h3')})"

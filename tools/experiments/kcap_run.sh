@@ -4,7 +4,7 @@ O=gpurun_out; mkdir -p $O
 python tools/gemm_bench.py --which wgrad_x6,wgrad_x6_t128 --kcaps 1024,2048,3072,4096,8192 > $O/r04e_kcap_h128.log 2>&1
 python tools/gemm_bench.py --din 256 --dm 256 --which wgrad_x6,wgrad_x6_t128 --kcaps 1024,2048,4096,8192,16384 > $O/r04e_kcap_concat.log 2>&1
 for c in 1024 2816 4096; do
-  python bench.py --no-cpu-baseline --no-also --wgrad-kcap $c > $O/r04e_bench_kcap$c.json 2> $O/r04e_bench_kcap$c.err
+  python bench.py --full --no-cpu-baseline --no-also --wgrad-kcap $c > $O/r04e_bench_kcap$c.json 2> $O/r04e_bench_kcap$c.err
 done
 tail -n 20 $O/r04e_kcap_h128.log $O/r04e_kcap_concat.log
 python - <<'PY'

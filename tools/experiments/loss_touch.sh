@@ -15,7 +15,7 @@ for v in product lossold product lossold; do
   if [ $v = product ]; then unset BL_HIP_LIB; else export BL_HIP_LIB=$R/tools/experiments/build/libbuglab_hip_$v.so; fi
   for g in 64 15; do
     rm -rf /tmp/lt_prof
-    rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/lt_prof -o s -- python $R/bench.py --graphs $g --steps 10 --warmup 3 --no-cpu-baseline --no-also --no-box --no-predict > /tmp/lt_bench.json 2>/dev/null
+    rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/lt_prof -o s -- python $R/bench.py --full --graphs $g --steps 10 --warmup 3 --no-cpu-baseline --no-also --no-box --no-predict > /tmp/lt_bench.json 2>/dev/null
     f=$(find /tmp/lt_prof -name '*kernel_stats.csv' | head -1)
     python - "$v" "$g" "$f" <<'PY'
 import csv, json, sys

@@ -34,7 +34,7 @@ for v in product ntstore ntload ntboth; do
   echo "== $v"
   python tools/gemm_bench.py --which fwd_h3,nk_h3 2>/dev/null
   python tools/hbm_bench.py 2>/dev/null
-  python bench.py --no-cpu-baseline --no-also --no-box 2>/dev/null | python -c "
+  python bench.py --full --no-cpu-baseline --no-also --no-box 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); k=d['roofline']['kernels_serial']
 print('bench', d['value'], 'graphs/s', d['ms_per_step'], 'ms;', {n: k[n]['ms_per_step'] for n in ('msg_dgrad_h3','msg_gemm_h3','segment_max_ln','node_grad_sums')})"

@@ -73,13 +73,13 @@ for v in product $VARIANTS product; do
   if [ $v = product ]; then unset BL_HIP_LIB; else export BL_HIP_LIB=$B/libbuglab_hip_$v.so; fi
   echo "== $v"
   case $v in
-    x6nt) python bench.py --no-cpu-baseline --no-also --no-box 2>/dev/null | python -c "$show"
-          python bench.py --no-cpu-baseline --no-also --no-box --msg-gemm bf16x6 2>/dev/null | python -c "$show"
-          python bench.py --no-cpu-baseline --no-also --no-box --model seq-great 2>/dev/null | python -c "$show"
+    x6nt) python bench.py --full --no-cpu-baseline --no-also --no-box 2>/dev/null | python -c "$show"
+          python bench.py --full --no-cpu-baseline --no-also --no-box --msg-gemm bf16x6 2>/dev/null | python -c "$show"
+          python bench.py --full --no-cpu-baseline --no-also --no-box --model seq-great 2>/dev/null | python -c "$show"
           unset BL_HIP_LIB; echo "== product (bf16x6, seq-great)"
-          python bench.py --no-cpu-baseline --no-also --no-box --msg-gemm bf16x6 2>/dev/null | python -c "$show"
-          python bench.py --no-cpu-baseline --no-also --no-box --model seq-great 2>/dev/null | python -c "$show";;
+          python bench.py --full --no-cpu-baseline --no-also --no-box --msg-gemm bf16x6 2>/dev/null | python -c "$show"
+          python bench.py --full --no-cpu-baseline --no-also --no-box --model seq-great 2>/dev/null | python -c "$show";;
     *) python tools/gemm_bench.py --which fwd_h3,nk_h3 2>/dev/null
-       python bench.py --no-cpu-baseline --no-also --no-box 2>/dev/null | python -c "$show";;
+       python bench.py --full --no-cpu-baseline --no-also --no-box 2>/dev/null | python -c "$show";;
   esac
 done

@@ -40,5 +40,5 @@ for v in product $VARIANTS product; do
   if [ $v = product ]; then unset BL_HIP_LIB; else export BL_HIP_LIB=$B/libbuglab_hip_$v.so; fi
   echo "== $v"
   python tools/gemm_bench.py --which fwd_h3,nk_h3,wgrad_h3 2>/dev/null
-  python bench.py --no-cpu-baseline --no-also --no-box 2>/dev/null | python -c "$show"
+  python bench.py --full --no-cpu-baseline --no-also --no-box 2>/dev/null | python -c "$show"
 done

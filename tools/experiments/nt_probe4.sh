@@ -25,5 +25,5 @@ print("bench", d["value"], d["unit"], d["ms_per_step"], "ms;", {n: v["ms_per_ste
 for v in product seqnt product seqnt; do
   if [ $v = product ]; then unset BL_HIP_LIB; else export BL_HIP_LIB=$B/libbuglab_hip_$v.so; fi
   echo "== $v"
-  python bench.py --no-cpu-baseline --no-also --no-box --model seq-great 2>/dev/null | python -c "$show"
+  python bench.py --full --no-cpu-baseline --no-also --no-box --model seq-great 2>/dev/null | python -c "$show"
 done

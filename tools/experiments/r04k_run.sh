@@ -9,8 +9,8 @@ python tools/gemm_bench.py --din 256 --dm 256 --which fwd_x6,nk_x6 > $O/r04k_sta
 BL_HIP_LIB=$V python tools/gemm_bench.py --din 256 --dm 256 --which fwd_x6,nk_x6 > $O/r04k_direct_concat.log 2>&1
 grep -H "x6" $O/r04k_*.log
 timeout 900 python -m pytest tests -x -q -m gpu > $O/r04k_gputest.log 2>&1; tail -3 $O/r04k_gputest.log
-python bench.py --no-cpu-baseline --no-also > $O/r04k_bench.json 2> $O/r04k_bench.err
-BL_HIP_LIB=$V python bench.py --no-cpu-baseline --no-also > $O/r04k_bench_direct.json 2> $O/r04k_bench_direct.err
+python bench.py --full --no-cpu-baseline --no-also > $O/r04k_bench.json 2> $O/r04k_bench.err
+BL_HIP_LIB=$V python bench.py --full --no-cpu-baseline --no-also > $O/r04k_bench_direct.json 2> $O/r04k_bench_direct.err
 python - <<'PY'
 import json
 for n in ("r04k_bench", "r04k_bench_direct"):

@@ -1,8 +1,8 @@
 #!/bin/bash
 O=gpurun_out; mkdir -p $O
 timeout 600 python -m pytest tests/test_edge_features.py tests/test_seq_great_gpu.py -x -q -m gpu > $O/r04n_tests.log 2>&1; tail -4 $O/r04n_tests.log
-python bench.py > $O/r04n_bench.json 2> $O/r04n_bench.err
-python bench.py --model seq-great --no-cpu-baseline > $O/r04n_bench_seq.json 2> $O/r04n_bench_seq.err
+python bench.py --full > $O/r04n_bench.json 2> $O/r04n_bench.err
+python bench.py --full --model seq-great --no-cpu-baseline > $O/r04n_bench_seq.json 2> $O/r04n_bench_seq.err
 python - <<'PY'
 import json
 d = json.load(open("gpurun_out/r04n_bench.json"))

@@ -1,7 +1,7 @@
 #!/bin/bash
 O=gpurun_out; mkdir -p $O
 for p in 0 -1 0 -1; do
-  python bench.py --no-cpu-baseline --no-also --no-predict --main-stream-priority $p > $O/r04o_bench_m$p.json 2> $O/r04o_bench_m$p.err
+  python bench.py --full --no-cpu-baseline --no-also --no-predict --main-stream-priority $p > $O/r04o_bench_m$p.json 2> $O/r04o_bench_m$p.err
   python - <<PY
 import json
 try:

@@ -2,7 +2,7 @@
 O=gpurun_out; mkdir -p $O
 timeout 900 python -m pytest tests -x -q -m gpu > $O/r04p_gputest.log 2>&1; tail -3 $O/r04p_gputest.log
 for v in "" "--default-stream" "" "--default-stream"; do
-  python bench.py --no-cpu-baseline --no-also --no-predict $v > $O/r04p_bench.json 2> $O/r04p_bench.err
+  python bench.py --full --no-cpu-baseline --no-also --no-predict $v > $O/r04p_bench.json 2> $O/r04p_bench.err
   python - <<PY
 import json
 try:

@@ -2,7 +2,7 @@
 O=gpurun_out; mkdir -p $O
 timeout 900 python -m pytest tests -x -q -m gpu > $O/r04r_gputest.log 2>&1; tail -3 $O/r04r_gputest.log
 bash tools/experiments/trace_run.sh r04r > $O/r04r_trace.log 2>&1; tail -1 $O/r04r_trace.log
-python bench.py --no-cpu-baseline --no-also > $O/r04r_bench.json 2> $O/r04r_bench.err
+python bench.py --full --no-cpu-baseline --no-also > $O/r04r_bench.json 2> $O/r04r_bench.err
 python - <<'PY'
 import json
 d = json.load(open("gpurun_out/r04r_bench.json")); print(d["value"], d["ms_per_step"], d["predict_graphs_per_s"], d["roofline"]["serial_ms_per_step"])

@@ -2,7 +2,7 @@
 O=gpurun_out; mkdir -p $O
 timeout 900 python -m pytest tests -x -q -m gpu > $O/r04zz_gputest.log 2>&1; tail -2 $O/r04z_gputest.log
 python -c "import __graft_entry__ as g; g.smoke()" > $O/r04zz_smoke.log 2>&1; tail -1 $O/r04z_smoke.log
-python bench.py > $O/r04zz_bench.json 2> $O/r04z_bench.err
+python bench.py --full > $O/r04zz_bench.json 2> $O/r04z_bench.err
 python - <<'PY'
 import json
 d = json.load(open("gpurun_out/r04zz_bench.json"))

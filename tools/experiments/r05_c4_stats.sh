@@ -4,7 +4,7 @@ R=$(pwd); O=$R/gpurun_out; mkdir -p $O; export TMPDIR=/tmp; cd /tmp
 for cfg in c3 c4; do
   extra=""; [ $cfg = c4 ] && extra="--degree powerlaw"
   rm -rf /tmp/prof_$cfg
-  rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_$cfg -o s -- python $R/bench.py --hidden 256 --graphs 32 $extra --serial --steps 6 --warmup 2 --no-cpu-baseline --no-predict --no-also > /dev/null 2>&1
+  rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_$cfg -o s -- python $R/bench.py --full --hidden 256 --graphs 32 $extra --serial --steps 6 --warmup 2 --no-cpu-baseline --no-predict --no-also > /dev/null 2>&1
   f=$(find /tmp/prof_$cfg -name '*kernel_stats.csv' | head -1); cp $f $O/r05_${cfg}_serial_kernel_stats.csv
 done
 python - <<PY

@@ -2,7 +2,7 @@
 O=gpurun_out; mkdir -p $O
 timeout 900 python -m pytest tests/test_hip_kernels.py tests/test_hip_parity.py -x -q -m gpu -k "not 64" 2>&1 | tail -3
 for cfg in "--hidden 256 --graphs 32" "--hidden 256 --graphs 32 --degree powerlaw" ""; do
-  python bench.py $cfg --no-cpu-baseline --no-also --steps 20 --warmup 5 > /tmp/b.json 2>/dev/null
+  python bench.py --full $cfg --no-cpu-baseline --no-also --steps 20 --warmup 5 > /tmp/b.json 2>/dev/null
   python - "$cfg" <<PY
 import json, sys
 j=json.loads(open("/tmp/b.json").read().strip().splitlines()[-1]); k=j["roofline"]["kernels_serial"]

@@ -2,7 +2,7 @@
 TAG=${1:-r05j}
 O=gpurun_out; mkdir -p $O
 timeout 900 python -m pytest tests/test_seq_great_gpu.py tests/test_hip_kernels.py -x -q -m gpu > $O/${TAG}_gputest.log 2>&1; tail -3 $O/${TAG}_gputest.log
-python bench.py --model seq-great --no-cpu-baseline --no-also > $O/${TAG}_bench_seq.json 2>$O/${TAG}_bench_seq.err; python - <<PY
+python bench.py --full --model seq-great --no-cpu-baseline --no-also > $O/${TAG}_bench_seq.json 2>$O/${TAG}_bench_seq.err; python - <<PY
 import json
 f="$O/${TAG}_bench_seq.json"
 try:

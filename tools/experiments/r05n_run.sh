@@ -1,6 +1,6 @@
 #!/bin/bash
 O=gpurun_out; mkdir -p $O
-python -m cProfile -o /tmp/p.prof bench.py --no-cpu-baseline --no-predict --steps 6 --warmup 2 > $O/r05n_bench.json 2>$O/r05n_bench.err
+python -m cProfile -o /tmp/p.prof bench.py --full --no-cpu-baseline --no-predict --steps 6 --warmup 2 > $O/r05n_bench.json 2>$O/r05n_bench.err
 python - <<PY > $O/r05n_pstats.txt 2>&1
 import pstats
 p = pstats.Stats("/tmp/p.prof")

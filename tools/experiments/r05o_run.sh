@@ -3,7 +3,7 @@
 O=gpurun_out; mkdir -p $O
 for i in 1 2; do
 for v in "" 1; do
-  BL_AB_KEEP_NODE_ORDER=$v python bench.py --no-cpu-baseline --no-also --no-predict --steps 20 --warmup 5 > /tmp/b.json 2>/dev/null
+  BL_AB_KEEP_NODE_ORDER=$v python bench.py --full --no-cpu-baseline --no-also --no-predict --steps 20 --warmup 5 > /tmp/b.json 2>/dev/null
   python - <<PY
 import json
 j=json.loads(open("/tmp/b.json").read().strip().splitlines()[-1]); k=j["roofline"]["kernels_serial"]

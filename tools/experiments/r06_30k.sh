@@ -1,10 +1,10 @@
 set -u
 R=$(pwd); O=$R/gpurun_out; export TMPDIR=/tmp
-python bench.py --graphs 15 --no-box --no-also --no-cpu-baseline > $O/r06t1_bench_30k.json 2> $O/r06t1_bench_30k.err
-python bench.py --graphs 15 --no-box --no-also --no-cpu-baseline --steps 100 --warmup 20 > $O/r06t1_bench_30k_100.json 2>> $O/r06t1_bench_30k.err
+python bench.py --full --graphs 15 --no-box --no-also --no-cpu-baseline > $O/r06t1_bench_30k.json 2> $O/r06t1_bench_30k.err
+python bench.py --full --graphs 15 --no-box --no-also --no-cpu-baseline --steps 100 --warmup 20 > $O/r06t1_bench_30k_100.json 2>> $O/r06t1_bench_30k.err
 cd /tmp
 rm -rf /tmp/prof_30k
-rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_30k -o s -- python $R/bench.py --graphs 15 --steps 20 --warmup 5 --no-cpu-baseline --no-predict --no-also --no-box > $O/r06t1_30k_rocprof.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_30k -o s -- python $R/bench.py --full --graphs 15 --steps 20 --warmup 5 --no-cpu-baseline --no-predict --no-also --no-box > $O/r06t1_30k_rocprof.log 2>&1
 f=$(find /tmp/prof_30k -name '*kernel_stats.csv' | head -1)
 [ -n "$f" ] && cp $f $O/r06t1_bench_30k_kernel_stats.csv
 f=$(find /tmp/prof_30k -name '*kernel_trace.csv' | head -1)

@@ -32,5 +32,5 @@ print("bench", d["value"], d["unit"], d["ms_per_step"], "ms;", {n: k[n]["ms_per_
 for v in product sa_nobits sa_nofinish sa_noscan; do
   if [ $v = product ]; then unset BL_HIP_LIB; else export BL_HIP_LIB=$B/libbuglab_hip_$v.so; fi
   echo "== $v"
-  python bench.py --no-cpu-baseline --no-also --no-box --no-predict 2>/dev/null | python -c "$show"
+  python bench.py --full --no-cpu-baseline --no-also --no-box --no-predict 2>/dev/null | python -c "$show"
 done

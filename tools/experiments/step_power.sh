@@ -10,7 +10,7 @@ hw = []  # (the hwmon files of card0 are not the visible GPU's on these boxes: 4
 def read(path):
     try: return int(open(path).read().strip())
     except Exception: return None
-p = subprocess.Popen(f"python bench.py {cfg} --steps {steps} --warmup 20 --no-cpu-baseline --no-also --no-predict > /tmp/b.json 2>/dev/null", shell=True)
+p = subprocess.Popen(f"python bench.py --full {cfg} --steps {steps} --warmup 20 --no-cpu-baseline --no-also --no-predict > /tmp/b.json 2>/dev/null", shell=True)
 samples = []
 t0 = time.time()
 while p.poll() is None:

@@ -4,7 +4,7 @@ TAG=${1:-trace}
 R=$(pwd); O=$R/gpurun_out; mkdir -p $O
 export TMPDIR=/tmp
 cd /tmp; rm -rf /tmp/prof_trace
-rocprofv3 --kernel-trace --output-format csv -d /tmp/prof_trace -o t -- python $R/bench.py --steps 2 --warmup 2 --no-cpu-baseline --no-predict --no-also > $O/${TAG}_trace_rocprof.log 2>&1
+rocprofv3 --kernel-trace --output-format csv -d /tmp/prof_trace -o t -- python $R/bench.py --full --steps 2 --warmup 2 --no-cpu-baseline --no-predict --no-also > $O/${TAG}_trace_rocprof.log 2>&1
 f=$(find /tmp/prof_trace -name '*kernel_trace.csv' | head -1)
 cd $R
 python - <<PY

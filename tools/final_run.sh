@@ -7,12 +7,12 @@ mkdir -p $O
 # (the bench lines first: run right behind the test-suite, the launch-bound seq-great entry of `also` once measured 766 instead of
 # 3 200 sequences/s -- host contention from processes the tests leave winding down; r05m)
 bash tools/collect_profiles.sh $TAG > $O/${TAG}_collect.log 2>&1
-python bench.py --hidden 256 --graphs 32 --no-cpu-baseline --no-also > $O/${TAG}_bench_c3.json 2>/dev/null
-python bench.py --hidden 256 --graphs 32 --degree powerlaw --no-cpu-baseline --no-also > $O/${TAG}_bench_c4.json 2>/dev/null
-python bench.py --graphs 15 --no-cpu-baseline --no-also > $O/${TAG}_bench_30k.json 2>/dev/null
+python bench.py --full --hidden 256 --graphs 32 --no-cpu-baseline --no-also > $O/${TAG}_bench_c3.json 2>/dev/null
+python bench.py --full --hidden 256 --graphs 32 --degree powerlaw --no-cpu-baseline --no-also > $O/${TAG}_bench_c4.json 2>/dev/null
+python bench.py --full --graphs 15 --no-cpu-baseline --no-also > $O/${TAG}_bench_30k.json 2>/dev/null
 bash tools/seq_models_run.sh $TAG > $O/${TAG}_seq_models.log 2>&1
-python bench.py --msg-gemm f16x1 --no-cpu-baseline --no-also > $O/${TAG}_bench_amp.json 2>/dev/null
-python bench.py --aggregation sum --no-cpu-baseline --no-also > $O/${TAG}_bench_sum.json 2>/dev/null
+python bench.py --full --msg-gemm f16x1 --no-cpu-baseline --no-also > $O/${TAG}_bench_amp.json 2>/dev/null
+python bench.py --full --aggregation sum --no-cpu-baseline --no-also > $O/${TAG}_bench_sum.json 2>/dev/null
 python tools/gemm_bench.py --which fwd_x6,fwd_h3,nk_x6,nk_h3,wgrad_x6,wgrad_h3 --mixed 2 > $O/${TAG}_gemm_bench.log 2>&1
 python tools/gemm_bench.py --which fwd_x6w,fwd_h3,nk_x6w,nk_h3,wgrad_x6,wgrad_h3 --din 256 --dm 256 --mixed 2 >> $O/${TAG}_gemm_bench.log 2>&1
 python tools/hbm_bench.py > $O/${TAG}_hbm_bench.log 2>&1

@@ -17,7 +17,7 @@ for k in set(fetch) | set(write):
                   "launches": fetch.get(k, write.get(k))["launches"]}
 top = dict(sorted(kernels.items(), key=lambda kv: -(kv[1]["FETCH_SIZE_KB_per_launch"] + kv[1]["WRITE_SIZE_KB_per_launch"]) * kv[1]["launches"])[:16])
 json.dump({
-    "command": "rocprofv3 --pmc FETCH_SIZE (WRITE_SIZE in a separate pass) --kernel-trace -- python bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-predict",
+    "command": "rocprofv3 --pmc FETCH_SIZE (WRITE_SIZE in a separate pass) --kernel-trace -- python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-predict",
     "note": "averages per dispatch over the run (6 H=128 layers + 2 concat layers per step); KB as reported by rocprofv3; FETCH_SIZE counts a 16 B/lane "
             "streaming read at 1/2 of its bytes on gfx950 (MI355X_MICROARCH.md, HBM section) -> doubled in bench.py's `traffic`; Infinity-Cache hits are "
             "included in both counters",
@@ -28,7 +28,7 @@ for f in ("bench.json", "bench_seq.json", "bench_kernel_stats.csv", "bench_seria
 if os.path.exists(f"{G}/{tag}_sq_pmc.json"):  # SQ counter passes of the serial run (tools/pmc_passes.sh): keep the layer kernels
     sq = json.load(open(f"{G}/{tag}_sq_pmc.json"))["kernels"]
     keep = {k: v for k, v in sq.items() if any(s in k for s in ("x6", "h3", "segment_max", "routed_dgrad", "node_bwd", "mp_scatter", "pack_rows"))}
-    json.dump({"command": "rocprofv3 --pmc <one group per pass> --kernel-trace -- python bench.py --serial --steps 2 --warmup 1 --no-cpu-baseline --no-predict --no-also",
+    json.dump({"command": "rocprofv3 --pmc <one group per pass> --kernel-trace -- python bench.py --full --serial --steps 2 --warmup 1 --no-cpu-baseline --no-predict --no-also",
                "note": "per-dispatch averages; mfma_busy_frac = SQ_VALU_MFMA_BUSY_CYCLES / (GRBM_GUI_ACTIVE / 8 XCDs x 1024 SIMDs); l2_hit_rate = TCC_HIT_sum / (TCC_HIT_sum + TCC_MISS_sum)",
                "kernels": keep}, open(f"{P}/{tag}_pmc_sq.json", "w"), indent=1, sort_keys=True)
     for k, v in sorted(keep.items(), key=lambda kv: -kv[1].get("SQ_VALU_MFMA_BUSY_CYCLES", 0))[:8]:
