@@ -628,6 +628,39 @@ int bl_bug_loss_bwd(const bl_bug_loss_t* d, const float* loc_logprobs, const flo
                     float* scratch, float* g_loc_scores, float* g_repair_logits, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * GREAT var-misuse head (buglab/models/greatreimplementation.py): LayerNorm -> Linear(D, 2) -> masked logits (:202-214),
+ * localization cross-entropy, repair logsumexp over the targets of the candidate log-softmax, the loss loc + repair and the
+ * metric counters (:118-174, :103-116), in csrc/bl_varmisuse_head.hip.  Position i of sample b is unmasked iff
+ * i < lens_att[b]; the caller passes lens_att = min(length + 1, L) (the reference's mask is `arange(L) > length`, :198).
+ * A sample is buggy iff error_location != 0 (:209).  Every reduction runs in a fixed order: results are bit-identical
+ * from run to run. */
+#define BL_VARMISUSE_STATS 8
+typedef struct {
+  int32_t B, L, D;                             /* samples, padded length, width (multiple of 4, <= 1024) */
+  float ln_eps;
+  const float* x;                              /* [B * L, D] last layer's output */
+  const float *ln_g, *ln_b;                    /* [D] */
+  const float* W;                              /* [D, 2] (stored [in, out]) */
+  const float* bias;                           /* [2] */
+  const int32_t* lens_att;                     /* [B] unmasked positions per sample */
+  const int32_t* error_location;               /* [B] */
+  const uint8_t *candidate_mask, *target_mask; /* [B * L] */
+} bl_varmisuse_head_t;
+/* workspace bytes of both directions (-1 for an unsupported shape) */
+int64_t bl_varmisuse_head_workspace_bytes(int32_t B, int32_t L, int32_t D);
+/* greatreimplementation.py:118-214.  logits [B * L, 2] (-inf where masked; column 1 also at non-candidates), mean / rstd [B * L],
+ * lse [B, 3] (localization, candidates, candidates that are targets), loss [2] = (loss, number of buggy samples), both on the device.
+ * stats [BL_VARMISUSE_STATS] (double) is ADDED to: samples, localization hits, buggy localization hits, buggy samples, repair
+ * hits, localization loss sum, repair loss sum, steps (the counters of :93-101). */
+int bl_varmisuse_head_fwd(const bl_varmisuse_head_t* d, float* logits, float* mean, float* rstd, float* lse, void* workspace,
+                          float* loss, double* stats, void* stream);
+/* greatreimplementation.py:143, :161-174 differentiated.  g_loss: device scalar.  Writes every row of g_x [B * L, D] (zeros at
+ * masked rows) and g_W [D, 2], g_bias [2], g_ln_g [D], g_ln_b [D]. */
+int bl_varmisuse_head_bwd(const bl_varmisuse_head_t* d, const float* logits, const float* mean, const float* rstd, const float* lse,
+                          const float* loss, const float* g_loss, void* workspace, float* g_x, float* g_W, float* g_bias,
+                          float* g_ln_g, float* g_ln_b, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * `seq-great` / `seq-rat` relational-transformer block (reference buglab/models/layers/relational_transformer.py,
  * relational_multihead_attention.py, multihead_attention.py): the row-wise kernels around the MFMA GEMMs.
  * q (pre-scaled by dk^-0.5), k, v, the attention context and their gradients are [B, H, L, dk] (one [L, dk] matrix per

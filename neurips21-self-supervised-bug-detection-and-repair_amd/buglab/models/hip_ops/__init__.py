@@ -1488,6 +1488,87 @@ def bug_loss(loc_scores, logits, sizes, ix: BugLossIndex, w_buggy: float = 1.0, 
 
 
 # ------------------------------------------------------------------------------------------------
+# GREAT var-misuse head (csrc/bl_varmisuse_head.hip; include/buglab_hip.h::bl_varmisuse_head_t)
+def _byte_mask(t: torch.Tensor, name: str) -> torch.Tensor:
+    return _req(t.view(torch.uint8) if t.dtype == torch.bool else t, torch.uint8, name)
+
+
+def _varmisuse_desc(x, ln_g, ln_b, W, bias, lens_att, error_location, cand, tgt, eps: float) -> bl_varmisuse_head_t:
+    d = bl_varmisuse_head_t()
+    B = int(lens_att.shape[0])
+    n, D = x.shape
+    if B < 1 or n % B != 0:
+        raise ValueError(f"varmisuse_head: x has {n} rows, not a multiple of B = {B}")
+    if tuple(W.shape) != (D, 2) or tuple(bias.shape) != (2,) or tuple(ln_g.shape) != (D,) or tuple(ln_b.shape) != (D,):
+        raise ValueError(f"varmisuse_head: expected W [{D}, 2], bias [2], ln_g / ln_b [{D}]")
+    if cand.numel() != n or tgt.numel() != n or error_location.numel() != B:
+        raise ValueError("varmisuse_head: candidate / target masks must have B * L entries and error_location B")
+    d.B, d.L, d.D, d.ln_eps = B, n // B, int(D), float(eps)
+    d.x, d.ln_g, d.ln_b = _f32(x, "x").data_ptr(), _f32(ln_g, "ln_g").data_ptr(), _f32(ln_b, "ln_b").data_ptr()
+    d.W, d.bias = _f32(W, "W").data_ptr(), _f32(bias, "bias").data_ptr()
+    d.lens_att, d.error_location = _i32(lens_att, "lens_att").data_ptr(), _i32(error_location, "error_location").data_ptr()
+    d.candidate_mask = _byte_mask(cand, "candidate_mask").data_ptr()
+    d.target_mask = _byte_mask(tgt, "target_mask").data_ptr()
+    return d
+
+
+def _varmisuse_workspace(d: bl_varmisuse_head_t, dev) -> torch.Tensor:
+    nbytes = int(load_library().bl_varmisuse_head_workspace_bytes(d.B, d.L, d.D))
+    if nbytes < 0:
+        raise ValueError(f"varmisuse_head: unsupported shape B={d.B} L={d.L} D={d.D} (D: a multiple of 4, at most 1024)")
+    return torch.empty(((nbytes + 15) // 16 * 4,), dtype=torch.float32, device=dev)
+
+
+class _VarMisuseHead(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, ln_g, ln_b, W, bias, lens_att, error_location, cand, tgt, stats, eps):
+        d = _varmisuse_desc(x, ln_g, ln_b, W, bias, lens_att, error_location, cand, tgt, eps)
+        dev = x.device
+        n = x.shape[0]
+        logits = torch.empty((n, 2), dtype=torch.float32, device=dev)
+        mean = torch.empty((n,), dtype=torch.float32, device=dev)
+        rstd = torch.empty((n,), dtype=torch.float32, device=dev)
+        lse = torch.empty((d.B, 3), dtype=torch.float32, device=dev)
+        out = torch.empty((2,), dtype=torch.float32, device=dev)  # [loss | number of buggy samples]
+        ws = _varmisuse_workspace(d, dev)
+        _req(stats, torch.float64, "stats")
+        if stats.numel() != VARMISUSE_STATS:
+            raise ValueError(f"varmisuse_head: stats must have {VARMISUSE_STATS} entries")
+        _check(load_library().bl_varmisuse_head_fwd(ctypes.byref(d), logits.data_ptr(), mean.data_ptr(), rstd.data_ptr(), lse.data_ptr(),
+                                                    ws.data_ptr(), out.data_ptr(), stats.data_ptr(), _stream()), "bl_varmisuse_head_fwd")
+        ctx.saved = (x, ln_g, ln_b, W, bias, lens_att, error_location, cand, tgt, eps, logits, mean, rstd, lse, out)
+        loss, num_buggy = out[0], out[1]
+        ctx.mark_non_differentiable(logits, num_buggy)
+        return loss, logits, num_buggy
+
+    @staticmethod
+    def backward(ctx, g_loss, _g_logits, _g_num_buggy):
+        x, ln_g, ln_b, W, bias, lens_att, error_location, cand, tgt, eps, logits, mean, rstd, lse, out = _take_saved(ctx)
+        d = _varmisuse_desc(x, ln_g, ln_b, W, bias, lens_att, error_location, cand, tgt, eps)
+        dev = x.device
+        ws = _varmisuse_workspace(d, dev)
+        g_x = torch.empty_like(x)
+        g_W, g_bias = torch.empty_like(W), torch.empty_like(bias)
+        g_ln_g, g_ln_b = torch.empty_like(ln_g), torch.empty_like(ln_b)
+        g = _f32(g_loss.contiguous().reshape(1), "g_loss")
+        _check(load_library().bl_varmisuse_head_bwd(ctypes.byref(d), logits.data_ptr(), mean.data_ptr(), rstd.data_ptr(), lse.data_ptr(),
+                                                    out.data_ptr(), g.data_ptr(), ws.data_ptr(), g_x.data_ptr(), g_W.data_ptr(),
+                                                    g_bias.data_ptr(), g_ln_g.data_ptr(), g_ln_b.data_ptr(), _stream()),
+               "bl_varmisuse_head_bwd")
+        return g_x, g_ln_g, g_ln_b, g_W, g_bias, None, None, None, None, None, None
+
+
+def varmisuse_head(x, ln_g, ln_b, W, bias, lens_att, error_location, candidate_mask, target_mask, stats, eps: float = 1e-5):
+    """GREAT's output head (reference greatreimplementation.py:143-174, :202-214) on x [B * L, D]: LayerNorm(ln_g, ln_b), Linear
+    (W [D, 2], bias [2]), the masked localization / pointer logits and loss = localization cross-entropy + mean repair loss over
+    the buggy samples.  lens_att int32 [B]: unmasked positions per sample; error_location int32 [B]; masks bool / uint8 [B * L].
+    `stats` (float64 [VARMISUSE_STATS], on the device) is added to (see include/buglab_hip.h).
+    -> (loss scalar, logits [B * L, 2], number of buggy samples as a device scalar); nothing is read back to the host."""
+    return _VarMisuseHead.apply(x.contiguous(), ln_g, ln_b, W.contiguous(), bias, lens_att.contiguous(), error_location.contiguous(),
+                                candidate_mask.reshape(-1).contiguous(), target_mask.reshape(-1).contiguous(), stats, float(eps))
+
+
+# ------------------------------------------------------------------------------------------------
 # `seq-great` relational transformer block (csrc/bl_seq_ops.hip + the MFMA GEMMs)
 class _AddLayerNorm(torch.autograd.Function):
     """y = LayerNorm(x + r) (r optional); backward hands the same gradient to x and r."""

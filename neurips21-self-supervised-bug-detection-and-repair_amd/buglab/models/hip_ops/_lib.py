@@ -94,6 +94,15 @@ class bl_bug_loss_t(Structure):
                 ("target", c_void_p * 3), ("ntarget", c_int32 * 3), ("w_buggy", c_float), ("abstain_weight", c_float)]
 
 
+class bl_varmisuse_head_t(Structure):
+    _fields_ = [("B", c_int32), ("L", c_int32), ("D", c_int32), ("ln_eps", c_float), ("x", c_void_p), ("ln_g", c_void_p), ("ln_b", c_void_p),
+                ("W", c_void_p), ("bias", c_void_p), ("lens_att", c_void_p), ("error_location", c_void_p), ("candidate_mask", c_void_p),
+                ("target_mask", c_void_p)]
+
+
+VARMISUSE_STATS = 8  # BL_VARMISUSE_STATS
+
+
 _SIGNATURES = {
     "bl_version": ([], ctypes.c_int),
     "bl_set_deterministic": ([c_int32], None),
@@ -158,6 +167,11 @@ _SIGNATURES = {
                                     c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p], ctypes.c_int),
     "bl_bug_loss_fwd": ([POINTER(bl_bug_loss_t), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p], ctypes.c_int),
     "bl_bug_loss_bwd": ([POINTER(bl_bug_loss_t), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p], ctypes.c_int),
+    "bl_varmisuse_head_workspace_bytes": ([c_int32, c_int32, c_int32], c_int64),
+    "bl_varmisuse_head_fwd": ([POINTER(bl_varmisuse_head_t), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
+                              ctypes.c_int),
+    "bl_varmisuse_head_bwd": ([POINTER(bl_varmisuse_head_t), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                              c_void_p, c_void_p, c_void_p, c_void_p, c_void_p], ctypes.c_int),
     "bl_add_layernorm_fwd": ([c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p], ctypes.c_int),
     "bl_add_layernorm_fwd_packed": ([c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                      c_void_p], ctypes.c_int),
