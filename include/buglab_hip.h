@@ -661,6 +661,29 @@ int bl_varmisuse_head_bwd(const bl_varmisuse_head_t* d, const float* logits, con
                           float* g_ln_g, float* g_ln_b, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Ensemble combine (buglab/models/ensemble/wrapper.py:33-89: `EnsembleWrapper.predict`'s avg / consensus and
+ * `_avg_ensembling`), in csrc/bl_ensemble.hip.  src: the M members' flat fp32 outputs [loc | text | var | swap], concatenated
+ * (n_src floats).  loc_idx [M, total_loc] / rw_idx [M, total_rw]: per member, the index into src of every entry of the canonical
+ * layout -- sample b owns entries loc_off[b] .. loc_off[b + 1] (np.unique(reference_nodes) ascending, then NO_BUG) and
+ * rw_off[b] .. rw_off[b + 1] (by original candidate-rewrite index); -1 on all of a sample's entries = the member has no
+ * prediction for it.  Per sample, with the M' present members in member order:
+ *   BL_ENSEMBLE_AVG        r = a_0 + w, r = logaddexp(r, a_m + w), w = -log(M') (numpy's logaddexp);
+ *   BL_ENSEMBLE_CONSENSUS  the avg result if every present member's first-maximum location (canonical order; Python's max
+ *                          semantics for NaN) is the same entry, else every location -inf, NO_BUG 0 and the first present
+ *                          member's rewrite values unchanged.
+ * A sample no member predicts gets NaN.  out_loc [total_loc] and out_rw [total_rw] are DOUBLE: an explicit exception to the
+ * float32 convention above, because the reference combines Python floats (doubles) made from the members' fp32 outputs, and an
+ * ensemble of one member must then equal that member's own prediction bit for bit (v + -log(1) = v).  One launch, one
+ * workgroup per sample, no atomics: bit-identical from run to run.  BL_ERANGE: M > BL_ENSEMBLE_MAX_MEMBERS, or n_src,
+ * M * total_loc or M * total_rw beyond int32. */
+#define BL_ENSEMBLE_AVG 0
+#define BL_ENSEMBLE_CONSENSUS 1
+#define BL_ENSEMBLE_MAX_MEMBERS 16
+int bl_ensemble_combine(const float* src, int64_t n_src, const int32_t* loc_idx, const int32_t* loc_off, int64_t total_loc,
+                        const int32_t* rw_idx, const int32_t* rw_off, int64_t total_rw, int32_t M, int32_t B, int32_t kind,
+                        double* out_loc, double* out_rw, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * `seq-great` / `seq-rat` relational-transformer block (reference buglab/models/layers/relational_transformer.py,
  * relational_multihead_attention.py, multihead_attention.py): the row-wise kernels around the MFMA GEMMs.
  * q (pre-scaled by dk^-0.5), k, v, the attention context and their gradients are [B, H, L, dk] (one [L, dk] matrix per

@@ -7,7 +7,7 @@ from __future__ import annotations
 
 from collections import defaultdict
 from contextlib import contextmanager
-from typing import Dict, List, Optional, Sequence, Tuple
+from typing import Dict, List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -117,63 +117,138 @@ class AbstractBugLabModel:
         )
 
     # -------------------------------------------------------------------------------------------
+    def _finalize_prediction_minibatch(self, accumulated_minibatch_data, device):
+        """`finalize_minibatch` for predict: collate, compute the un-batching gather indices on the host (in the collate worker
+        of `minibatch_iterator`, off the device's critical path), then the one host->device copy."""
+        from buglab.data.collate import to_device
+
+        mb = self.collate_minibatch(accumulated_minibatch_data)
+        layout = prediction_layout(mb)
+        out = to_device(mb, device)
+        out["prediction_layout"] = layout
+        return out
+
     def _iter_per_sample_results(self, mb_data, candidate_location_sample_idx, candidate_location_log_probs,
                                  arg_swap_logprobs, num_samples, original_datapoints, text_repair_logprobs,
                                  varmisuse_logprobs, node_mappings: List[Dict[int, int]] = None):
         """Un-batch a predicted minibatch into (datapoint, {node_idx: logprob, -1: NO_BUG}, [rewrite logprob])
-        triples -- reference basemodel.py:240-346.  All array work is NumPy; one D2H per tensor."""
+        triples -- reference basemodel.py:240-346.  The four outputs are concatenated and copied to the host once, then
+        gathered through `prediction_layout` (precomputed by `_finalize_prediction_minibatch` when present)."""
         to_np = lambda t: t.detach().cpu().numpy() if hasattr(t, "detach") else np.asarray(t)
-        loc_sample = to_np(candidate_location_sample_idx)
-        loc_lp = to_np(candidate_location_log_probs)
-        per_sample_loc = [loc_lp[loc_sample == b] for b in range(num_samples)]  # candidates in order, NO_BUG last
+        layout = mb_data.get("prediction_layout")
+        if layout is None:
+            keys = None
+            if node_mappings is not None:
+                keys = [[node_mappings[b][k] for k in np.unique(original_datapoints[b]["graph"]["reference_nodes"])]
+                        for b in range(num_samples)]
+            layout = prediction_layout(mb_data, to_np(candidate_location_sample_idx), keys)
+        parts = (candidate_location_log_probs, text_repair_logprobs, varmisuse_logprobs, arg_swap_logprobs)
+        if all(hasattr(t, "detach") for t in parts):
+            import torch
 
-        def by_group(logprobs, groups):
-            d = defaultdict(list)
-            for g, lp in zip(to_np(groups).tolist(), to_np(logprobs).tolist()):
-                d[g].append(lp)
-            return d
-
-        swap_g = by_group(arg_swap_logprobs, mb_data["swapped_pair_to_call_location_group"])
-        text_g = by_group(text_repair_logprobs, mb_data["rewrite_to_location_group"])
-        var_g = by_group(varmisuse_logprobs, mb_data["candidate_symbol_to_location_group"])
-
-        next_group = 0
+            flat = torch.cat([t.detach().reshape(-1).float() for t in parts]).cpu().numpy()
+        else:
+            flat = np.concatenate([to_np(t).reshape(-1).astype(np.float32) for t in parts])
+        assert flat.shape[0] == layout.flat_size
+        loc_all, rw_all = flat[layout.loc_idx].tolist(), flat[layout.rw_idx].tolist()
+        assert layout.num_samples == num_samples
         for b in range(num_samples):
             point = original_datapoints[b]
             ref_nodes = point["graph"]["reference_nodes"]
-            cand_nodes = np.unique(ref_nodes)
-            if node_mappings is not None:
-                cand_nodes = np.array([node_mappings[b][k] for k in cand_nodes])
-            dist = per_sample_loc[b]
+            cand_nodes = np.unique(ref_nodes).tolist()
+            lo, hi = int(layout.loc_off[b]), int(layout.loc_off[b + 1])
+            dist = loc_all[lo:hi]
             assert len(dist) == len(cand_nodes) + 1
-            location_logprobs = {int(n): float(lp) for n, lp in zip(cand_nodes, dist)}
-            location_logprobs[-1] = float(dist[-1])
-
-            flat_swap, flat_text, flat_var = [], [], []
-            for _ in range(len(np.unique(ref_nodes))):
-                flat_swap.extend(swap_g[next_group])
-                flat_text.extend(text_g[next_group])
-                flat_var.extend(var_g[next_group])
-                next_group += 1
-            text_idx = mb_data["text_rewrite_original_idxs"][b]
-            var_idx = mb_data["candidate_rewrite_original_idxs"][b]
-            swap_idx = mb_data["pair_rewrite_original_idx"][b]
-            assert len(text_idx) == len(flat_text) and len(var_idx) == len(flat_var) and len(swap_idx) == len(flat_swap)
-            rewrite_probs: List[Optional[float]] = [None] * len(point["candidate_rewrites"])
-            for idxs, lps in ((text_idx, flat_text), (var_idx, flat_var), (swap_idx, flat_swap)):
-                for i, lp in zip(idxs, lps):
-                    assert rewrite_probs[i] is None
-                    rewrite_probs[i] = lp
-            assert None not in rewrite_probs
-
-            if node_mappings is not None:  # :320-335 (sequence models map graph nodes to tokens)
+            rewrite_probs = rw_all[int(layout.rw_off[b]):int(layout.rw_off[b + 1])]
+            assert len(rewrite_probs) == len(point["candidate_rewrites"])
+            if node_mappings is None:
+                location_logprobs = dict(zip(cand_nodes, dist))
+            else:  # :320-335 (sequence models map graph nodes to tokens): the reference's key order, token by token
+                value = dict(zip(cand_nodes, dist))
+                in_refs = set(cand_nodes)
                 reverse = defaultdict(list)
                 for old, new in node_mappings[b].items():
-                    if old in ref_nodes:
+                    if old in in_refs:
                         reverse[new].append(old)
-                remapped = {}
-                for n, p in location_logprobs.items():
-                    for node in (reverse[n] if n >= 0 else [n]):
-                        remapped[node] = p
-                location_logprobs = remapped
+                location_logprobs = {}
+                for n in dict.fromkeys(node_mappings[b][k] for k in cand_nodes):
+                    for node in reverse[n]:
+                        location_logprobs[node] = value[node]
+            location_logprobs[-1] = dist[-1]
             yield point, location_logprobs, rewrite_probs
+
+
+class PredictionLayout(NamedTuple):
+    """Where each per-sample prediction value sits in a model's flat output `[loc | text | var | swap]` (the concatenation of
+    `compute_localization_logprobs`'s log-probabilities and `_compute_repair_logprobs`' text / var-misuse / arg-swap
+    log-probabilities).  Canonical order per sample b:
+      locations  loc_idx[loc_off[b] : loc_off[b + 1]]  -- np.unique(reference_nodes) ascending, then NO_BUG;
+      rewrites   rw_idx[rw_off[b] : rw_off[b + 1]]     -- by original candidate-rewrite index.
+    All int32; every index < flat_size."""
+
+    loc_idx: np.ndarray
+    loc_off: np.ndarray
+    rw_idx: np.ndarray
+    rw_off: np.ndarray
+    flat_size: int
+    num_samples: int
+
+
+def prediction_layout(mb, candidate_location_sample_idx=None, location_keys: Optional[Sequence[Sequence]] = None
+                      ) -> PredictionLayout:
+    """Gather indices of `_iter_per_sample_results` (reference basemodel.py:240-346) from a collated minibatch (NumPy, or
+    tensors on the CPU), so that un-batching is one gather.  Rules reproduced exactly:
+      * the location entries of sample b are those with sample id b, in flat order: the candidates, NO_BUG last;
+      * a family's logprobs of sample b are its entries ordered by location group (stable), and the k-th of them belongs to
+        the k-th original rewrite index of that family (text, then var-misuse, then arg-swap);
+      * location keys (sequence models: the token a candidate node maps to; `node_mappings` branch, :320-335): candidates that
+        share a key all take the value of the LAST flat entry with that key (the reference builds {token: logprob} first).
+    `candidate_location_sample_idx`: default cat(candidate -> sample ids, arange(B)), what the localization head returns.
+    `location_keys`: per sample, one key per unique reference node; default: none for graph minibatches, the candidates' token
+    positions for sequence minibatches (`collate_sequences`, which carry `node_mappings`)."""
+    as_np = lambda a: a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a)
+    gd = mb["graph_data"]
+    B = int(gd["num_graphs"])
+    cand = as_np(gd["reference_node_ids"]["candidate_nodes"]).astype(np.int64)
+    if candidate_location_sample_idx is None:
+        candidate_location_sample_idx = np.concatenate(
+            [as_np(gd["reference_node_graph_idx"]["candidate_nodes"]).astype(np.int64), np.arange(B, dtype=np.int64)])
+    ids = np.asarray(candidate_location_sample_idx, dtype=np.int64).reshape(-1)
+    n_loc = np.bincount(ids, minlength=B)[:B]
+    loc_off = np.zeros(B + 1, dtype=np.int64)
+    np.cumsum(n_loc, out=loc_off[1:])
+    loc_order = np.argsort(ids, kind="stable")  # sample b's entries, in flat order: loc_order[loc_off[b]:loc_off[b + 1]]
+    if location_keys is None and mb.get("node_mappings") is not None:
+        cand_ptr = as_np(gd["candidate_ptr"]).astype(np.int64)
+        location_keys = [cand[cand_ptr[b]:cand_ptr[b + 1]] for b in range(B)]
+    loc_idx = loc_order.copy()
+    if location_keys is not None:
+        for b in range(B):
+            keys = [int(k) for k in location_keys[b]]
+            assert len(keys) + 1 == n_loc[b]
+            last = {k: j for j, k in enumerate(keys)}
+            loc_idx[loc_off[b]:loc_off[b] + len(keys)] = loc_order[loc_off[b] + np.asarray([last[k] for k in keys], dtype=np.int64)]
+
+    fams = (("rewrite_to_location_group", "text_rewrite_original_idxs"),
+            ("candidate_symbol_to_location_group", "candidate_rewrite_original_idxs"),
+            ("swapped_pair_to_call_location_group", "pair_rewrite_original_idx"))
+    sizes = [int(as_np(mb[g]).shape[0]) for g, _ in fams]
+    n_rw = np.array([sum(len(mb[o][b]) for _, o in fams) for b in range(B)], dtype=np.int64)
+    rw_off = np.zeros(B + 1, dtype=np.int64)
+    np.cumsum(n_rw, out=rw_off[1:])
+    rw_idx = np.full(int(rw_off[-1]), -1, dtype=np.int64)
+    base = ids.shape[0]
+    for (g, o), size in zip(fams, sizes):
+        order = np.argsort(as_np(mb[g]).astype(np.int64), kind="stable") + base
+        pos = 0
+        for b in range(B):
+            orig = np.asarray(mb[o][b], dtype=np.int64)
+            if orig.size:
+                assert orig.min() >= 0 and orig.max() < n_rw[b] and (rw_idx[rw_off[b] + orig] == -1).all()
+                rw_idx[rw_off[b] + orig] = order[pos:pos + orig.size]
+            pos += orig.size
+        assert pos == size
+        base += size
+    assert (rw_idx >= 0).all()
+    i32 = lambda a: np.ascontiguousarray(a, dtype=np.int32)
+    return PredictionLayout(i32(loc_idx), i32(loc_off), i32(rw_idx), i32(rw_off), int(base), B)

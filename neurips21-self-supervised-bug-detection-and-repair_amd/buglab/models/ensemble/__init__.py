@@ -1,0 +1,2 @@
+"""Model ensembles (reference buglab/models/ensemble/): `wrapper.EnsembleWrapper` / `wrapper.EnsembleModuleWrapper`, and
+`python -m buglab.models.ensemble OUT KIND MODEL...` to build an ensemble file that evaluate.py loads like any checkpoint."""

@@ -1488,6 +1488,31 @@ def bug_loss(loc_scores, logits, sizes, ix: BugLossIndex, w_buggy: float = 1.0, 
 
 
 # ------------------------------------------------------------------------------------------------
+# ensemble combine (csrc/bl_ensemble.hip; include/buglab_hip.h::bl_ensemble_combine)
+ENSEMBLE_KINDS = {"avg": 0, "consensus": 1}  # BL_ENSEMBLE_AVG, BL_ENSEMBLE_CONSENSUS
+ENSEMBLE_MAX_MEMBERS = 16  # BL_ENSEMBLE_MAX_MEMBERS
+
+
+def ensemble_combine(src, loc_idx, loc_off, rw_idx, rw_off, kind: str) -> torch.Tensor:
+    """M members' concatenated flat fp32 outputs `src` -> the ensemble's values in the canonical layout, float64
+    [total_loc + total_rw] (locations first): ONE buffer, so the caller needs one device->host copy.  loc_idx [M, total_loc] /
+    rw_idx [M, total_rw] int32 (-1: member absent from that sample), loc_off / rw_off int32 [B + 1].  No sync."""
+    if kind not in ENSEMBLE_KINDS:
+        raise ValueError(f"ensemble_combine: kind must be one of {sorted(ENSEMBLE_KINDS)} (got {kind!r})")
+    _f32(src, "src")
+    _i32(loc_idx, "loc_idx"), _i32(rw_idx, "rw_idx"), _i32(loc_off, "loc_off"), _i32(rw_off, "rw_off")
+    M, total_loc = loc_idx.shape
+    total_rw = rw_idx.shape[1]
+    assert rw_idx.shape[0] == M and loc_off.shape == rw_off.shape
+    out = torch.empty(total_loc + total_rw, dtype=torch.float64, device=src.device)
+    _check(load_library().bl_ensemble_combine(src.data_ptr(), src.numel(), loc_idx.data_ptr(), loc_off.data_ptr(), total_loc,
+                                              rw_idx.data_ptr(), rw_off.data_ptr(), total_rw, M, loc_off.shape[0] - 1,
+                                              ENSEMBLE_KINDS[kind], out.data_ptr(), out.data_ptr() + 8 * total_loc, _stream()),
+           "bl_ensemble_combine")
+    return out
+
+
+# ------------------------------------------------------------------------------------------------
 # GREAT var-misuse head (csrc/bl_varmisuse_head.hip; include/buglab_hip.h::bl_varmisuse_head_t)
 def _byte_mask(t: torch.Tensor, name: str) -> torch.Tensor:
     return _req(t.view(torch.uint8) if t.dtype == torch.bool else t, torch.uint8, name)

@@ -257,7 +257,8 @@ class SeqBugLabModel(AbstractNeuralModel, AbstractBugLabModel):
         with torch.no_grad(), self._tensorize_all_location_rewrites():
             for mb_data, original_datapoints in self.minibatch_iterator(
                     self.tensorize_dataset(data, return_input_data=True, parallelize=parallelize), device,
-                    max_minibatch_size=50, parallelize=parallelize):
+                    max_minibatch_size=50, parallelize=parallelize,
+                    finalize=self._finalize_prediction_minibatch):
                 ids, loc_lp, enc_out, _ = trained_nn.compute_localization_logprobs(mb_data["graph_data"])
                 swap_lp, text_lp, var_lp, _ = trained_nn._compute_repair_logprobs(
                     enc_out, mb_data["target_rewrites"], mb_data["rewrite_to_location_group"],

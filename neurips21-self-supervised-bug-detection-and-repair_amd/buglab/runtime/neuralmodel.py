@@ -24,6 +24,34 @@ TNeuralModule = TypeVar("TNeuralModule")
 COLLATE_WORKERS = 3  # minibatches collated concurrently by minibatch_iterator(parallelize=True)
 
 
+def ordered_map(fn, iterable: Iterable, parallelize: bool = False, num_workers: int = 8) -> Iterator:
+    """fn(x) for every x, in order; with `parallelize` in worker threads, at most 4 * num_workers results ahead."""
+    if not parallelize:
+        for x in iterable:
+            yield fn(x)
+        return
+    with ThreadPoolExecutor(max_workers=num_workers) as pool:
+        window: "deque" = deque()
+        for x in iterable:
+            window.append(pool.submit(fn, x))
+            if len(window) >= 4 * num_workers:
+                yield window.popleft().result()
+        while window:
+            yield window.popleft().result()
+
+
+def write_checkpoint(path: Path, model, neural_module) -> None:
+    """The checkpoint format: gzip-pickled `(model, neural_module)`.  Written to a temporary file and moved into place: a crash
+    mid-write cannot corrupt the previous best checkpoint."""
+    import os
+
+    path = Path(path)
+    tmp = path.with_name(path.name + ".tmp")
+    with gzip.open(tmp, "wb") as f:
+        torch.save((model, neural_module), f)
+    os.replace(tmp, path)
+
+
 class AbstractNeuralModel(ABC, Generic[TRawDatapoint, TTensorizedDatapoint, TNeuralModule]):
     def __init__(self):
         self.__metadata_initialized = False
@@ -64,33 +92,18 @@ class AbstractNeuralModel(ABC, Generic[TRawDatapoint, TTensorizedDatapoint, TNeu
                           num_workers: int = 8) -> Iterator:
         """Tensorise lazily; samples for which `tensorize` returns None are dropped (reference
         gnn.py:404-405).  `parallelize` tensorises in worker threads, preserving order."""
-        def one(d):
-            return self.tensorize(d), d
-
-        if parallelize:
-            with ThreadPoolExecutor(max_workers=num_workers) as pool:
-                window: List = []
-                for d in dataset_iterator:
-                    window.append(pool.submit(one, d))
-                    if len(window) >= 4 * num_workers:
-                        t, orig = window.pop(0).result()
-                        if t is not None:
-                            yield (t, orig) if return_input_data else t
-                for f in window:
-                    t, orig = f.result()
-                    if t is not None:
-                        yield (t, orig) if return_input_data else t
-        else:
-            for d in dataset_iterator:
-                t = self.tensorize(d)
-                if t is not None:
-                    yield (t, d) if return_input_data else t
+        for t, orig in ordered_map(lambda d: (self.tensorize(d), d), dataset_iterator, parallelize, num_workers):
+            if t is not None:
+                yield (t, orig) if return_input_data else t
 
     def minibatch_iterator(self, tensorized_data: Iterable, device: Union[str, torch.device], max_minibatch_size: int,
-                           yield_partial_minibatches: bool = True, parallelize: bool = False) -> Iterator:
+                           yield_partial_minibatches: bool = True, parallelize: bool = False, finalize=None) -> Iterator:
         """Yields `(minibatch dict, [original datapoints])`.  With `parallelize` the next minibatch
         is collated and copied (pinned, non-blocking) in a background thread while the device
-        works on the current one."""
+        works on the current one.  `finalize(accumulated, device)`: replaces `finalize_minibatch` (predict adds its
+        un-batching indices there, so they are built in the collate workers too)."""
+        finalize = finalize or self.finalize_minibatch
+
         def gather():
             """Groups tensorised samples into un-collated minibatches (cheap: list appends)."""
             mb = self.initialize_minibatch()
@@ -109,7 +122,7 @@ class AbstractNeuralModel(ABC, Generic[TRawDatapoint, TTensorizedDatapoint, TNeu
 
         if not parallelize:
             for mb, originals in gather():
-                yield self.finalize_minibatch(mb, device), originals
+                yield finalize(mb, device), originals
             return
         # Collation (NumPy + the native counting sorts release the GIL) and the pinned host->device copy of the next
         # minibatches run in a few worker threads while the device works on the current one; order is preserved.
@@ -122,7 +135,7 @@ class AbstractNeuralModel(ABC, Generic[TRawDatapoint, TTensorizedDatapoint, TNeu
                 with ThreadPoolExecutor(max_workers=COLLATE_WORKERS) as pool:
                     pending: "deque" = deque()
                     for mb, originals in gather():
-                        pending.append((pool.submit(self.finalize_minibatch, mb, device), originals))
+                        pending.append((pool.submit(finalize, mb, device), originals))
                         while len(pending) > COLLATE_WORKERS:
                             fut, orig = pending.popleft()
                             q.put((fut.result(), orig))
@@ -144,14 +157,7 @@ class AbstractNeuralModel(ABC, Generic[TRawDatapoint, TTensorizedDatapoint, TNeu
 
     # ---- persistence --------------------------------------------------------------------------
     def save(self, path: Path, neural_module) -> None:
-        """Written to a temporary file and moved into place: a crash mid-write cannot corrupt the previous best checkpoint."""
-        import os
-
-        path = Path(path)
-        tmp = path.with_name(path.name + ".tmp")
-        with gzip.open(tmp, "wb") as f:
-            torch.save((self, neural_module), f)
-        os.replace(tmp, path)
+        write_checkpoint(path, self, neural_module)
 
     @classmethod
     def restore_model(cls, path: Path, device=None) -> Tuple["AbstractNeuralModel", Any]:
