@@ -683,6 +683,36 @@ int bl_ensemble_combine(const float* src, int64_t n_src, const int32_t* loc_idx,
                         const int32_t* rw_idx, const int32_t* rw_off, int64_t total_rw, int32_t M, int32_t B, int32_t kind,
                         double* out_loc, double* out_rw, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Self-supervision services (buglab/controllers/bugselectorserver.py:22-28, 120-150 and
+ * buglab/controllers/detectordatascoringworker.py:118-130), in csrc/bl_selfsup.hip.  Both read a model's flat fp32 output
+ * src = [loc | text | var | swap] (n_src floats) through int32 indices derived from `prediction_layout`, and work in DOUBLE
+ * from the fp32 inputs -- the same exception to the fp32 convention as bl_ensemble_combine, for the same reason: the
+ * reference does this arithmetic on Python floats made from fp32 values.  One launch each per minibatch, no atomics,
+ * bit-identical from run to run.  An index outside [0, n_src) reads as NaN.
+ *
+ * bl_score_targets: out[b] = src[tgt_loc[b]] + (tgt_rw[b] >= 0 ? src[tgt_rw[b]] : 0), b < B.  tgt_loc: the location entry of
+ * the ground node (or NO_BUG's for a sample without a bug); tgt_rw: the target rewrite's entry, -1 for a sample without a bug.
+ *
+ * bl_selector_sample: sample b has n_b = rw_off[b + 1] - rw_off[b] candidate rewrites (by original rewrite index; total_rw in
+ * all) and n_b + 1 ENTRIES, NO_BUG last, at e_b = rw_off[b] + b .. e_b + n_b of u, out_logprob and out_p (total_rw + B each).
+ *   out_logprob  g_i = src[rw_idx[i]] + src[rw_loc_idx[i]] (rw_loc_idx: the location entry of the rewrite's reference node);
+ *                g_{n_b} = src[nobug_idx[b]];
+ *   out_p        1 / (n_b + 1) if u_eps[b] < epsilon, else exp(g_i / T) / sum_j exp(g_j / T) computed literally (no max
+ *                subtraction: where the reference overflows to inf / nan, so does this);
+ *   out_entropy  [B] -sum_i p_i log p_i (0 * log 0 = nan, as NumPy);
+ *   out_selected [B, K] int32: k_b = min(K, #{i : p_i > 0}) entries drawn without replacement by Gumbel top-k,
+ *                key_i = log p_i - log(-log u_i), u in (0, 1) from the caller; the k_b largest keys in descending order, ties to
+ *                the lower index; -1 padded.  Entry index n_b means NO_BUG.
+ * BL_EINVAL: K < 1, temperature 0 or NaN, null pointers, negative sizes.  BL_ERANGE: K > BL_SELECTOR_MAX_K, or n_src or
+ * total_rw + B beyond int32. */
+#define BL_SELECTOR_MAX_K 32
+int bl_score_targets(const float* src, int64_t n_src, const int32_t* tgt_loc, const int32_t* tgt_rw, int32_t B, double* out, void* stream);
+int bl_selector_sample(const float* src, int64_t n_src, const int32_t* rw_idx, const int32_t* rw_loc_idx, const int32_t* rw_off,
+                       int64_t total_rw, const int32_t* nobug_idx, int32_t B, const double* u_eps, const double* u, double temperature,
+                       double epsilon, int32_t K, double* out_logprob, double* out_p, double* out_entropy, int32_t* out_selected,
+                       void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * `seq-great` / `seq-rat` relational-transformer block (reference buglab/models/layers/relational_transformer.py,
  * relational_multihead_attention.py, multihead_attention.py): the row-wise kernels around the MFMA GEMMs.

@@ -1,0 +1,149 @@
+"""What the two services share: the minibatches of a model's own `predict` with the services' gather indices added in the
+collate worker, the model's flat output, and input-order bookkeeping."""
+from __future__ import annotations
+
+import threading
+from collections import deque
+from typing import Any, Callable, Dict, Iterable, Iterator, List, NamedTuple, Sequence, Tuple
+
+import numpy as np
+import torch
+
+from buglab.models.basemodel import PredictionLayout
+from buglab.runtime.neuralmodel import ordered_map
+
+MAX_MINIBATCH_SIZE = 50  # samples per minibatch, as the models' own predict
+
+
+class SelfSupIndices(NamedTuple):
+    """Indices into a model's flat output [loc | text | var | swap], int32, from `prediction_layout` and the datapoints:
+      rw_loc_idx [total_rw]  per rewrite (layout order: sample by sample, by original rewrite index), the location entry of its
+                             reference node -- what `location_logprobs[reference_nodes[i]]` reads;
+      nobug_idx  [B]         the sample's NO_BUG location entry (`location_logprobs[-1]`);
+      tgt_loc    [B]         the ground node's location entry, NO_BUG's when `target_fix_action_idx` is None;
+      tgt_rw     [B]         the target rewrite's entry, -1 when `target_fix_action_idx` is None.
+    Sequence models need nothing extra: `prediction_layout` has already resolved their location keys."""
+
+    rw_loc_idx: np.ndarray
+    nobug_idx: np.ndarray
+    tgt_loc: np.ndarray
+    tgt_rw: np.ndarray
+
+
+def selfsup_indices(layout: PredictionLayout, datapoints: Sequence[Any]) -> SelfSupIndices:
+    B = layout.num_samples
+    assert len(datapoints) == B
+    rw_loc = np.empty(int(layout.rw_off[-1]), np.int32)
+    nobug, tgt_loc, tgt_rw = np.empty(B, np.int32), np.empty(B, np.int32), np.full(B, -1, np.int32)
+    for b, point in enumerate(datapoints):
+        loc = layout.loc_idx[layout.loc_off[b]:layout.loc_off[b + 1]]
+        r0, r1 = int(layout.rw_off[b]), int(layout.rw_off[b + 1])
+        # a reference node's place in np.unique(reference_nodes): the canonical order of the location entries
+        nodes, place = np.unique(np.asarray(point["graph"]["reference_nodes"], dtype=np.int64), return_inverse=True)
+        assert loc.shape[0] == nodes.shape[0] + 1 and place.shape[0] == r1 - r0
+        rw_loc[r0:r1] = loc[place]
+        nobug[b] = loc[-1]
+        target = point["target_fix_action_idx"]
+        if target is None:
+            tgt_loc[b] = loc[-1]
+        else:
+            tgt_loc[b] = loc[place[target]]
+            tgt_rw[b] = layout.rw_idx[r0 + int(target)]
+    return SelfSupIndices(rw_loc, nobug, tgt_loc, tgt_rw)
+
+
+def to_device_i32(arrays: Sequence[np.ndarray], device) -> List[torch.Tensor]:
+    """Several int32 arrays -> device tensors through ONE pinned staging buffer and one (non-blocking) copy."""
+    sizes = [int(a.shape[0]) for a in arrays]
+    dev = torch.device(device)
+    staging = torch.empty(sum(sizes), dtype=torch.int32, pin_memory=dev.type == "cuda")
+    if sum(sizes):
+        np.concatenate([np.asarray(a, np.int32) for a in arrays], out=staging.numpy())
+    blob = staging.to(dev, non_blocking=True)
+    out, pos = [], 0
+    for n in sizes:
+        out.append(blob[pos:pos + n])
+        pos += n
+    return out
+
+
+def require_single_model(model, what: str) -> None:
+    from buglab.models.ensemble.wrapper import EnsembleWrapper
+
+    if isinstance(model, EnsembleWrapper):
+        raise TypeError(f"{what} runs on a single detector / selector model; ensembles (EnsembleWrapper) are not supported here.")
+    for attr in ("tensorize", "minibatch_iterator", "_finalize_prediction_minibatch", "_tensorize_all_location_rewrites"):
+        if not hasattr(model, attr):
+            raise TypeError(f"{what}: {type(model).__name__} has no `{attr}`; expected one of the registry's BugLab models.")
+
+
+def prediction_minibatches(model, tagged: Iterable[Tuple[Any, Any]], device, parallelize: bool,
+                           extend: Callable[[PredictionLayout, List[Any], Any], Dict[str, Any]],
+                           rejected: Callable[[Any], None]) -> Iterator[Tuple[Dict[str, Any], List[Any]]]:
+    """The minibatches `model.predict` would form from the datapoints of `tagged` = (datapoint, tag) pairs (same
+    `minibatch_iterator`, same `_finalize_prediction_minibatch`, 50 samples at most), as (minibatch on the device, [tag]).
+    `extend(layout, datapoints, device)` runs in the collate worker, after the layout; its result is the minibatch's
+    "selfsup" entry.  `rejected(tag)` is called (from the tensorising side, in input order) for a datapoint `tensorize`
+    rejects.  Call under `torch.no_grad()` and `model._tensorize_all_location_rewrites()`."""
+    side: Dict[int, Any] = {}  # id(tensorised sample) -> (the sample: keeps the id unique, its datapoint)
+
+    def tensorized():
+        for t, (point, tag) in ordered_map(lambda x: (model.tensorize(x[0]), x), tagged, parallelize):
+            if t is None:
+                rejected(tag)
+                continue
+            side[id(t)] = (t, point)
+            yield t, tag
+
+    def finalize(accumulated, dev):
+        points = [side.pop(id(s))[1] for s in accumulated["samples"]]
+        out = model._finalize_prediction_minibatch(accumulated, dev)
+        out["selfsup"] = extend(out["prediction_layout"], points, dev)
+        return out
+
+    yield from model.minibatch_iterator(tensorized(), device, max_minibatch_size=MAX_MINIBATCH_SIZE, parallelize=parallelize,
+                                        finalize=finalize)
+
+
+def flat_prediction_output(trained_nn, mb_data) -> torch.Tensor:
+    """The forward of the model's own `predict` (gnn.py / seqmodel.py) -> its flat fp32 output [loc | text | var | swap],
+    left on the device."""
+    _, loc_lp, enc_out, _ = trained_nn.compute_localization_logprobs(mb_data["graph_data"])
+    swap_lp, text_lp, var_lp, _ = trained_nn._compute_repair_logprobs(
+        enc_out, mb_data["target_rewrites"], mb_data["rewrite_to_location_group"], mb_data["candidate_symbol_to_location_group"],
+        mb_data["swapped_pair_to_call_location_group"], mb_data["repair_group_ptr"], mb_data["repair_group_items"])
+    flat = torch.cat([t.detach().reshape(-1).float() for t in (loc_lp, text_lp, var_lp, swap_lp)])
+    assert flat.shape[0] == mb_data["prediction_layout"].flat_size
+    return flat
+
+
+class InOrder:
+    """Results leave in the order their slots were opened, whatever order they are completed in.  Slots are opened by the
+    tensorising side (a worker thread when parallelised) and completed / drained by the consumer."""
+
+    def __init__(self):
+        self._slots: "deque" = deque()
+        self.lock = threading.Lock()
+
+    def open(self, slot) -> None:  # slot: any object with a boolean `done`
+        self._slots.append(slot)
+
+    def drain(self) -> Iterator[Any]:
+        while self._slots and self._slots[0].done:
+            yield self._slots.popleft()
+
+    def __len__(self) -> int:
+        return len(self._slots)
+
+
+def save_msgpack_l_gz_reproducibly(data: Iterable[Any], filename) -> None:
+    """`utils.msgpackutils.save_msgpack_l_gz` without the time stamp and file name in the gzip header: the same data gives the
+    same bytes."""
+    import gzip
+
+    import msgpack
+
+    with open(filename, "wb") as raw, gzip.GzipFile(filename="", mode="wb", fileobj=raw, mtime=0) as out_file:
+        packer = msgpack.Packer(use_bin_type=True)
+        for element in data:
+            out_file.write(packer.pack(element))

@@ -365,3 +365,36 @@ def make_buglab_seq_dataset(n: int, seed: int = 0, min_statements: int = 4, max_
         if d["candidate_rewrites"]:
             out.append(d)
     return out
+
+
+# ------------------------------------------------------------------------------------------------
+# Records for detector scoring (buglab.controllers.detectorscoring; reference detectordatascoringworker.py:99-111): an original
+# datapoint and what it "became" under a few of its candidate rewrites.  Real rewriting is libcst work and out of scope: a
+# rewritten datapoint here is a copy of the original with its own `target_fix_action_idx` (the rewrite that would undo it),
+# which is what the scoring looks at.
+def make_scoring_records(datapoints, seed: int = 0, num_rewrites: int = 4, selections=None):
+    """-> [{"original": datapoint, "rewrites": {str(idx) | "NO_BUG": (datapoint, prob)}}], one per datapoint (deep copies; the
+    originals get `target_fix_action_idx` None, as un-bugged code has).  `selections`: per datapoint the bug selector's reply
+    `{"NO_BUG" | str(idx): value}` to build the rewrites of; default: NO_BUG and up to `num_rewrites` random rewrites."""
+    import copy
+
+    rng = np.random.default_rng(seed)
+    records = []
+    for k, point in enumerate(datapoints):
+        original = copy.deepcopy(point)
+        original["target_fix_action_idx"] = None
+        original.pop("candidate_rewrite_logprobs", None)
+        n = len(original["candidate_rewrites"])
+        if selections is not None:
+            chosen = dict(selections[k])
+        else:
+            picks = rng.choice(n, size=min(num_rewrites, n), replace=False).tolist() if n else []
+            chosen = {"NO_BUG": 1.0 / (n + 1), **{str(int(i)): 1.0 / (n + 1) for i in picks}}
+        rewrites = {}
+        for key, prob in chosen.items():
+            rewritten = copy.deepcopy(original)
+            if key != "NO_BUG":
+                rewritten["target_fix_action_idx"] = int(rng.integers(0, n))
+            rewrites[key] = (rewritten, float(prob))
+        records.append({"original": original, "rewrites": rewrites})
+    return records

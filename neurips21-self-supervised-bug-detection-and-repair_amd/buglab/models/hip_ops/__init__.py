@@ -1513,6 +1513,51 @@ def ensemble_combine(src, loc_idx, loc_off, rw_idx, rw_off, kind: str) -> torch.
 
 
 # ------------------------------------------------------------------------------------------------
+# self-supervision services (csrc/bl_selfsup.hip; include/buglab_hip.h::bl_score_targets, bl_selector_sample)
+SELECTOR_MAX_K = 32  # BL_SELECTOR_MAX_K
+
+
+def _f64(t, name="tensor"):
+    return _req(t, torch.float64, name)
+
+
+def score_targets(src, tgt_loc, tgt_rw) -> torch.Tensor:
+    """The log-probability a model's flat fp32 output `src` gives to each sample's true fix, float64 [B]:
+    src[tgt_loc[b]] + (src[tgt_rw[b]] if tgt_rw[b] >= 0).  tgt_loc / tgt_rw int32 [B].  No sync."""
+    _f32(src, "src"), _i32(tgt_loc, "tgt_loc"), _i32(tgt_rw, "tgt_rw")
+    if tgt_loc.dim() != 1 or tgt_loc.shape != tgt_rw.shape:
+        raise ValueError(f"score_targets: tgt_loc {tuple(tgt_loc.shape)} and tgt_rw {tuple(tgt_rw.shape)} must both be [B]")
+    out = torch.empty(tgt_loc.shape[0], dtype=torch.float64, device=src.device)
+    _check(load_library().bl_score_targets(src.data_ptr(), src.numel(), tgt_loc.data_ptr(), tgt_rw.data_ptr(), tgt_loc.shape[0],
+                                           out.data_ptr(), _stream()), "bl_score_targets")
+    return out
+
+
+def selector_sample(src, rw_idx, rw_loc_idx, rw_off, nobug_idx, u_eps, u, *, temperature: float, epsilon: float, k: int
+                    ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Bug selection on a model's flat fp32 output `src` -> (logprob, p, entropy, selected).  Sample b owns the entries
+    rw_off[b] + b .. rw_off[b + 1] + b (its rewrites by original index, then NO_BUG) of logprob / p / u (float64
+    [total_rw + B]); entropy float64 [B]; selected int32 [B, k]: entry indices within the sample (n_b = NO_BUG) in descending
+    Gumbel-key order, -1 padded.  rw_idx / rw_loc_idx int32 [total_rw], rw_off int32 [B + 1], nobug_idx int32 [B], u_eps
+    float64 [B], u float64 [total_rw + B] in (0, 1).  No sync."""
+    _f32(src, "src")
+    _i32(rw_idx, "rw_idx"), _i32(rw_loc_idx, "rw_loc_idx"), _i32(rw_off, "rw_off"), _i32(nobug_idx, "nobug_idx")
+    _f64(u_eps, "u_eps"), _f64(u, "u")
+    B, total_rw = nobug_idx.shape[0], rw_idx.shape[0]
+    if rw_loc_idx.shape != rw_idx.shape or rw_off.shape[0] != B + 1 or u_eps.shape[0] != B or u.shape[0] != total_rw + B:
+        raise ValueError(f"selector_sample: inconsistent shapes (B {B}, total_rw {total_rw}, rw_loc_idx {tuple(rw_loc_idx.shape)}, "
+                         f"rw_off {tuple(rw_off.shape)}, u_eps {tuple(u_eps.shape)}, u {tuple(u.shape)})")
+    values = torch.empty(2 * (total_rw + B) + B, dtype=torch.float64, device=src.device)  # one buffer: [logprob | p | entropy]
+    selected = torch.empty((B, int(k)), dtype=torch.int32, device=src.device)
+    n = total_rw + B
+    _check(load_library().bl_selector_sample(src.data_ptr(), src.numel(), rw_idx.data_ptr(), rw_loc_idx.data_ptr(), rw_off.data_ptr(),
+                                             total_rw, nobug_idx.data_ptr(), B, u_eps.data_ptr(), u.data_ptr(), float(temperature),
+                                             float(epsilon), int(k), values.data_ptr(), values.data_ptr() + 8 * n,
+                                             values.data_ptr() + 16 * n, selected.data_ptr(), _stream()), "bl_selector_sample")
+    return values[:n], values[n:2 * n], values[2 * n:], selected
+
+
+# ------------------------------------------------------------------------------------------------
 # GREAT var-misuse head (csrc/bl_varmisuse_head.hip; include/buglab_hip.h::bl_varmisuse_head_t)
 def _byte_mask(t: torch.Tensor, name: str) -> torch.Tensor:
     return _req(t.view(torch.uint8) if t.dtype == torch.bool else t, torch.uint8, name)

@@ -13,6 +13,8 @@ Options:
     --sequential                  Do not parallelize data loading. Makes debugging easier.
     --quiet                       Do not show progress bar.
     --model-spec=<json>           Extra model kwargs as JSON (e.g. '{"hidden_state_size": 256}').
+    --selector                    Train a bug selector on scored data (`candidate_rewrite_logprobs`, written by
+                                  buglab.controllers.detectorscoring): rewrites at every location are tensorised.
     -h --help                     Show this screen.
     --debug                       Enable debug routines. [default: False]
 
@@ -96,8 +98,13 @@ def run(arguments):
             dist.broadcast_object_list(box, src=0)
             if dist.get_rank() != 0:
                 trainer.model, trainer.neural_module = box[0]
-    trainer.train(training_data, validation_data, show_progress_bar=not arguments["--quiet"], initialize_metadata=False,
-                  parallelize=not arguments["--sequential"], use_multiprocessing=not arguments["--sequential"], patience=10)
+    from contextlib import nullcontext
+
+    # selector data carries a score for rewrites at EVERY location (reference controllers/trainbugselector.py:143)
+    all_locations = trainer.model._tensorize_all_location_rewrites() if arguments.get("--selector") else nullcontext()
+    with all_locations:
+        trainer.train(training_data, validation_data, show_progress_bar=not arguments["--quiet"], initialize_metadata=False,
+                      parallelize=not arguments["--sequential"], use_multiprocessing=not arguments["--sequential"], patience=10)
 
 
 def parse_args(argv=None):
@@ -115,6 +122,7 @@ def parse_args(argv=None):
     p.add_argument("--sequential", action="store_true")
     p.add_argument("--quiet", action="store_true")
     p.add_argument("--model-spec", default=None)
+    p.add_argument("--selector", action="store_true")
     p.add_argument("--debug", action="store_true")
     ns = p.parse_args(argv)
     d = {"MODEL_NAME": ns.MODEL_NAME, "TRAIN_DATA_PATH": ns.TRAIN_DATA_PATH, "VALID_DATA_PATH": ns.VALID_DATA_PATH,
