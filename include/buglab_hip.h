@@ -713,6 +713,44 @@ int bl_selector_sample(const float* src, int64_t n_src, const int32_t* rw_idx, c
                        double epsilon, int32_t K, double* out_logprob, double* out_p, double* out_entropy, int32_t* out_selected,
                        void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Bug reports (buglab/models/visualize.py:75-170: what decides whether and where a sample appears), in csrc/bl_report.hip.
+ * Same conventions as the self-supervision services: src = a model's flat fp32 output (n_src floats), int32 indices, DOUBLE
+ * results, no atomics, bit-identical from run to run, an index outside [0, n_src) reads as NaN.  "First maximum" is Python's
+ * max(): the first value stays unless a later one is greater (a NaN in front wins, a NaN elsewhere never does).
+ *
+ * bl_report_summarize, one launch per predict minibatch of B samples.  Sample b owns
+ *   loc_idx[loc_off[b] : loc_off[b + 1]]   its location entries in the key order of the dict `predict` yields, NO_BUG last;
+ *   rw_idx [rw_off[b]  : rw_off[b + 1]]    its rewrites by original index (as PredictionLayout), rw_eq_target alongside: 1 where
+ *                                          the rewrite's value equals the target rewrite's value;
+ *   groups grp_off[b] : grp_off[b + 1]     its range groups (rewrites with equal candidate_rewrite_ranges), by first occurrence.
+ * Group g owns grp_rw[grp_rw_off[g] : grp_rw_off[g + 1]]: its rewrites as positions in rw_idx, ascending (grp_rw_off has
+ * total_grp + 1 entries and covers [0, total_rw]); grp_loc[g]: the POSITION among the sample's location entries of the node the
+ * group's last rewrite refers to; grp_shown[g]: 1 if the range survives text_to_range_segments.  tgt_grp[b]: the target
+ * rewrite's group within the sample (-1: NO_BUG); ground_loc[b]: the position of the ground node's location entry (NO_BUG's
+ * without a target); nobug_idx[b]: NO_BUG's entry in src.
+ *   out_best_rw    [total_grp] the group's first-maximum rewrite, as an index within the sample's rewrites;
+ *   out_best_range [total_grp] src[location of grp_loc[g]] + that rewrite's log-probability (one fp64 addition);
+ *   out_sample_i   [3, B]      pred_loc (position of the first-maximum location entry) | pred_is_nobug | is_wrong: ground_loc !=
+ *                              pred_loc, replaced, when the target's group is shown, by (grp_loc != pred_loc, or
+ *                              rw_eq_target[best rewrite of the group] == 0);
+ *   out_sample_d   [2, B]      prediction_logprob = the greatest non-NaN out_best_range over the shown groups, -inf if none |
+ *                              no_bug_logprob = src[nobug_idx[b]].
+ *
+ * bl_report_order, once per report: out[0 : *out_count] = the indices i < n with keep[i] != 0, ordered as Python's stable
+ * sorted(key=-keys[i]) orders them when by_confidence != 0 (greater key first, input order on ties, -inf last, NaN after that)
+ * and in input order otherwise; cut to the first k when k > 0.  out has room for n entries; those beyond *out_count are not
+ * written.  BL_ERANGE: n > BL_REPORT_MAX_SAMPLES (the ranks are counted pair by pair). */
+#define BL_REPORT_MAX_SAMPLES (1 << 20)
+int bl_report_summarize(const float* src, int64_t n_src, const int32_t* loc_idx, const int32_t* loc_off, int64_t total_loc,
+                        const int32_t* rw_idx, const int32_t* rw_off, int64_t total_rw, const int32_t* rw_eq_target,
+                        const int32_t* grp_rw, const int32_t* grp_rw_off, const int32_t* grp_loc, const int32_t* grp_shown,
+                        const int32_t* grp_off, int64_t total_grp, const int32_t* tgt_grp, const int32_t* ground_loc,
+                        const int32_t* nobug_idx, int32_t B, int32_t* out_best_rw, double* out_best_range, int32_t* out_sample_i,
+                        double* out_sample_d, void* stream);
+int bl_report_order(const double* keys, const int32_t* keep, int64_t n, int64_t k, int32_t by_confidence, int32_t* out,
+                    int32_t* out_count, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * `seq-great` / `seq-rat` relational-transformer block (reference buglab/models/layers/relational_transformer.py,
  * relational_multihead_attention.py, multihead_attention.py): the row-wise kernels around the MFMA GEMMs.

@@ -79,11 +79,13 @@ def require_single_model(model, what: str) -> None:
 
 def prediction_minibatches(model, tagged: Iterable[Tuple[Any, Any]], device, parallelize: bool,
                            extend: Callable[[PredictionLayout, List[Any], Any], Dict[str, Any]],
-                           rejected: Callable[[Any], None]) -> Iterator[Tuple[Dict[str, Any], List[Any]]]:
+                           rejected: Callable[[Any], None], extend_sees_minibatch: bool = False
+                           ) -> Iterator[Tuple[Dict[str, Any], List[Any]]]:
     """The minibatches `model.predict` would form from the datapoints of `tagged` = (datapoint, tag) pairs (same
     `minibatch_iterator`, same `_finalize_prediction_minibatch`, 50 samples at most), as (minibatch on the device, [tag]).
     `extend(layout, datapoints, device)` runs in the collate worker, after the layout; its result is the minibatch's
-    "selfsup" entry.  `rejected(tag)` is called (from the tensorising side, in input order) for a datapoint `tensorize`
+    "selfsup" entry (with `extend_sees_minibatch` it is called as `extend(layout, datapoints, device, minibatch)`: the
+    sequence models' minibatch carries their node -> token maps).  `rejected(tag)` is called (from the tensorising side, in input order) for a datapoint `tensorize`
     rejects.  Call under `torch.no_grad()` and `model._tensorize_all_location_rewrites()`."""
     side: Dict[int, Any] = {}  # id(tensorised sample) -> (the sample: keeps the id unique, its datapoint)
 
@@ -98,7 +100,8 @@ def prediction_minibatches(model, tagged: Iterable[Tuple[Any, Any]], device, par
     def finalize(accumulated, dev):
         points = [side.pop(id(s))[1] for s in accumulated["samples"]]
         out = model._finalize_prediction_minibatch(accumulated, dev)
-        out["selfsup"] = extend(out["prediction_layout"], points, dev)
+        out["selfsup"] = (extend(out["prediction_layout"], points, dev, out) if extend_sees_minibatch
+                          else extend(out["prediction_layout"], points, dev))
         return out
 
     yield from model.minibatch_iterator(tensorized(), device, max_minibatch_size=MAX_MINIBATCH_SIZE, parallelize=parallelize,

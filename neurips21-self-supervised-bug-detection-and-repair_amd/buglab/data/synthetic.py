@@ -398,3 +398,81 @@ def make_scoring_records(datapoints, seed: int = 0, num_rewrites: int = 4, selec
             rewrites[key] = (rewritten, float(prob))
         records.append({"original": original, "rewrites": rewrites})
     return records
+
+
+# ------------------------------------------------------------------------------------------------
+# Synthetic raw datapoints WITH SOURCE: what a bug report (buglab/models/visualize.py) cuts and annotates.  The graphs and
+# rewrites are those of the generators above; on top of them a multi-line `text`, a `code_range` that starts neither at
+# line 1 nor at column 0, and `candidate_rewrite_ranges` inside it that nest, overlap, repeat (two reference nodes with one
+# range), are empty (start == end), collide once widened (an empty range at (l, c) and the range (l, c)-(l, c + 1)), and span
+# lines.  The text holds characters that HTML must escape.
+_SOURCE_TOKENS = ["if", "x", "<", "y", "&", "z", ":", "return", "'a'", '"b"', "(", ")", "+=", "1", "value", "<=", "not", ">"]
+
+
+def add_report_source(rng: np.random.Generator, point: dict, package: str = "synthetic") -> dict:
+    num_lines = int(rng.integers(3, 8))
+    lines = []
+    for _ in range(num_lines):
+        line = "    " * int(rng.integers(0, 3)) + " ".join(_SOURCE_TOKENS[int(rng.integers(0, len(_SOURCE_TOKENS)))] for _ in range(int(rng.integers(8, 14))))
+        lines.append(line)
+    line0, col0 = int(rng.integers(2, 40)), int(rng.integers(1, 12))
+    absolute = lambda i, c: (line0 + i, c + col0 if i == 0 else c)
+    code_range = ((line0, col0), absolute(num_lines - 1, len(lines[-1])))
+
+    def fresh():
+        i = int(rng.integers(0, num_lines))
+        a = int(rng.integers(0, len(lines[i]) - 6))
+        return i, a, a + int(rng.integers(2, 6))
+
+    node_range, prev = {}, None
+    shift = int(rng.integers(0, 7))  # a sample with few reference nodes still meets every shape across a data set
+    for node in dict.fromkeys(point["graph"]["reference_nodes"]):
+        kind = (len(node_range) + shift) % 7
+        if prev is None or kind == 0:
+            i, a, b = fresh()
+            rng_abs = (absolute(i, a), absolute(i, b))
+        elif kind == 1:  # nested in the previous one
+            i, a, b = prev
+            a, b = a + 1, max(a + 1, b - 1)
+            rng_abs = (absolute(i, a), absolute(i, b))
+        elif kind == 2:  # overlaps the previous one
+            i, a, b = prev
+            a, b = a + 1, min(len(lines[i]), b + 2)
+            rng_abs = (absolute(i, a), absolute(i, b))
+        elif kind == 3:  # the previous node's range again
+            i, a, b = prev
+            rng_abs = (absolute(i, a), absolute(i, b))
+        elif kind == 4:  # empty
+            i, a, _ = fresh()
+            b = a
+            rng_abs = (absolute(i, a), absolute(i, a))
+        elif kind == 5:  # what the empty one is widened to
+            i, a, _ = prev
+            b = a + 1
+            rng_abs = (absolute(i, a), absolute(i, b))
+        else:  # spans lines
+            i = int(rng.integers(0, num_lines - 1))
+            a, b = int(rng.integers(0, len(lines[i]))), int(rng.integers(1, len(lines[i + 1])))
+            rng_abs = (absolute(i, a), absolute(i + 1, b))
+            node_range[node] = rng_abs
+            prev = None
+            continue
+        node_range[node] = rng_abs
+        prev = (i, a, b)
+    out = dict(point)
+    out["graph"] = dict(point["graph"])
+    out["graph"]["text"] = "\n".join(lines)
+    out["graph"]["code_range"] = code_range
+    out["graph"]["path"] = f"/usr/lib/python3/site-packages/{package}/module_{int(rng.integers(0, 100))}.py" if rng.integers(0, 2) else f"{package}/f.py"
+    out["candidate_rewrite_ranges"] = [node_range[n] for n in point["graph"]["reference_nodes"]]
+    out["package_name"] = package
+    return out
+
+
+def make_report_dataset(n: int, seed: int = 0, kind: str = "graph"):
+    """`kind`: "graph" (make_buglab_datapoint) or "seq" (make_buglab_seq_datapoint) underneath."""
+    if kind not in ("graph", "seq"):
+        raise ValueError(f"make_report_dataset: kind must be 'graph' or 'seq' (got {kind!r})")
+    rng = np.random.default_rng(seed)
+    base = make_buglab_dataset(n, seed) if kind == "graph" else make_buglab_seq_dataset(n, seed)
+    return [add_report_source(rng, p, package=f"package{i % 5}") for i, p in enumerate(base)]

@@ -1558,6 +1558,54 @@ def selector_sample(src, rw_idx, rw_loc_idx, rw_off, nobug_idx, u_eps, u, *, tem
 
 
 # ------------------------------------------------------------------------------------------------
+# bug reports (csrc/bl_report.hip; include/buglab_hip.h::bl_report_summarize, bl_report_order)
+REPORT_MAX_SAMPLES = 1 << 20  # BL_REPORT_MAX_SAMPLES
+REPORT_INDEX_FIELDS = ("loc_idx", "loc_off", "rw_idx", "rw_off", "rw_eq_target", "grp_rw", "grp_rw_off", "grp_loc", "grp_shown",
+                       "grp_off", "tgt_grp", "ground_loc", "nobug_idx")
+
+
+def report_summarize(src, ix) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """The verdicts of one predict minibatch from a model's flat fp32 output `src` -> (best_rw int32 [total_grp],
+    best_range_logprob float64 [total_grp], sample_i int32 [3, B] = pred_loc | pred_is_nobug | is_wrong, sample_d float64
+    [2, B] = prediction_logprob | no_bug_logprob).  `ix`: a mapping with the int32 tensors of REPORT_INDEX_FIELDS
+    (buglab/models/_report.py::report_indices).  No sync."""
+    _f32(src, "src")
+    t = {name: _i32(ix[name], name) for name in REPORT_INDEX_FIELDS}
+    B, total_loc, total_rw, total_grp = t["nobug_idx"].shape[0], t["loc_idx"].shape[0], t["rw_idx"].shape[0], t["grp_loc"].shape[0]
+    sizes = {"loc_off": B + 1, "rw_off": B + 1, "grp_off": B + 1, "tgt_grp": B, "ground_loc": B, "rw_eq_target": total_rw,
+             "grp_rw": total_rw, "grp_rw_off": total_grp + 1, "grp_shown": total_grp}
+    bad = {name: tuple(t[name].shape) for name, n in sizes.items() if t[name].dim() != 1 or t[name].shape[0] != n}
+    if bad:
+        raise ValueError(f"report_summarize: inconsistent shapes (B {B}, total_loc {total_loc}, total_rw {total_rw}, "
+                         f"total_grp {total_grp}): {bad}")
+    best_rw = torch.empty(total_grp, dtype=torch.int32, device=src.device)
+    best_range = torch.empty(total_grp, dtype=torch.float64, device=src.device)
+    sample_i = torch.empty((3, B), dtype=torch.int32, device=src.device)
+    sample_d = torch.empty((2, B), dtype=torch.float64, device=src.device)
+    p = lambda name: t[name].data_ptr()
+    _check(load_library().bl_report_summarize(
+        src.data_ptr(), src.numel(), p("loc_idx"), p("loc_off"), total_loc, p("rw_idx"), p("rw_off"), total_rw, p("rw_eq_target"),
+        p("grp_rw"), p("grp_rw_off"), p("grp_loc"), p("grp_shown"), p("grp_off"), total_grp, p("tgt_grp"), p("ground_loc"),
+        p("nobug_idx"), B, best_rw.data_ptr(), best_range.data_ptr(), sample_i.data_ptr(), sample_d.data_ptr(), _stream()),
+        "bl_report_summarize")
+    return best_rw, best_range, sample_i, sample_d
+
+
+def report_order(keys, keep, *, by_confidence: bool, k: int = 0) -> torch.Tensor:
+    """The indices of the samples with keep != 0, int32, in report order: as Python's stable sorted(key=-keys[i]) when
+    `by_confidence`, else input order; the first k when k > 0.  keys float64 [n], keep int32 [n].  Syncs (reads the count)."""
+    _f64(keys, "keys"), _i32(keep, "keep")
+    if keys.dim() != 1 or keys.shape != keep.shape:
+        raise ValueError(f"report_order: keys {tuple(keys.shape)} and keep {tuple(keep.shape)} must both be [n]")
+    n = keys.shape[0]
+    out = torch.full((n,), -1, dtype=torch.int32, device=keys.device)
+    count = torch.zeros(1, dtype=torch.int32, device=keys.device)
+    _check(load_library().bl_report_order(keys.data_ptr(), keep.data_ptr(), n, int(k), int(bool(by_confidence)), out.data_ptr(),
+                                          count.data_ptr(), _stream()), "bl_report_order")
+    return out[:int(count.item())]
+
+
+# ------------------------------------------------------------------------------------------------
 # GREAT var-misuse head (csrc/bl_varmisuse_head.hip; include/buglab_hip.h::bl_varmisuse_head_t)
 def _byte_mask(t: torch.Tensor, name: str) -> torch.Tensor:
     return _req(t.view(torch.uint8) if t.dtype == torch.bool else t, torch.uint8, name)

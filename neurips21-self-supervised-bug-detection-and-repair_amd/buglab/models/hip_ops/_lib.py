@@ -177,6 +177,10 @@ _SIGNATURES = {
     "bl_score_targets": ([c_void_p, c_int64, c_void_p, c_void_p, c_int32, c_void_p, c_void_p], ctypes.c_int),
     "bl_selector_sample": ([c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int32, c_void_p, c_void_p, c_double,
                             c_double, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p], ctypes.c_int),
+    "bl_report_summarize": ([c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
+                             c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p,
+                             c_void_p], ctypes.c_int),
+    "bl_report_order": ([c_void_p, c_void_p, c_int64, c_int64, c_int32, c_void_p, c_void_p, c_void_p], ctypes.c_int),
     "bl_add_layernorm_fwd": ([c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p], ctypes.c_int),
     "bl_add_layernorm_fwd_packed": ([c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                      c_void_p], ctypes.c_int),
