@@ -12,13 +12,13 @@ from oracle import great_oracle as G
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 
-@pytest.mark.parametrize("name", ["great", "rat", "scalar", "great32"])
+@pytest.mark.parametrize("name", ["great", "rat", "scalar", "great32", "rezero_scalar", "rezero_vector", "normoff"])
 def test_encoder_stack_matches_reference(name):
     z = np.load(os.path.join(GOLD, f"great_{name}.npz"))
     D, H, layers, FF, T, value_bias, scalar = (int(v) for v in z["cfg"])
     cfg = G.GreatConfig(d_model=D, num_heads=H, num_layers=layers, dim_feedforward=FF, num_edge_types=T,
                         use_edge_value_biases=bool(value_bias), edge_attention_bias_is_scalar=bool(scalar),
-                        normalisation_mode=str(z["norm"]))
+                        normalisation_mode=str(z["norm"]), rezero_mode=str(z["rezero"]) if "rezero" in z.files else "off")
     p = {k[2:]: torch.from_numpy(z[k]).clone().requires_grad_(True) for k in z.files if k.startswith("p.")}
     x = torch.from_numpy(z["x"]).clone().requires_grad_(True)
     masked = torch.from_numpy(z["masked"])
