@@ -751,6 +751,40 @@ int bl_report_summarize(const float* src, int64_t n_src, const int32_t* loc_idx,
 int bl_report_order(const double* keys, const int32_t* keep, int64_t n, int64_t k, int32_t by_confidence, int32_t* out,
                     int32_t* out_count, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Near-duplicate detection (buglab/data/deduplication/index.py:15-70: `DuplicationIndex.check_if_duplicate_and_add`, which
+ * updates a 256-permutation MinHash one token at a time and keeps one Python dict per LSH band), in csrc/bl_dedup.hip.  The
+ * arithmetic is the written specification of DESIGN.md "Near-duplicate detection"; all of it is integer work and every result is
+ * exact.  Buffers are the caller's, on the device; nothing is read back.
+ *
+ * bl_dedup_sha1_u32 (index.py:36-37, `min_hash.update(token.encode())`: the token's hash value): token t is
+ *   bytes[tok_off[t] : tok_off[t + 1]] (tok_off has ntokens + 1 entries, clamped to [0, nbytes]; any length, the empty token
+ *   included); out[t] = the first four bytes of its SHA-1 digest read as a little-endian uint32.  One thread per token.
+ *
+ * bl_dedup_minhash (index.py:35-37): document d owns hashes[doc_off[d] : doc_off[d + 1]] (ndocs + 1 offsets, clamped to
+ *   [0, nhashes]); sigs[d, k] = min(2^32 - 1, min over its hashes hv of (((perm_a[k] * hv + perm_b[k]) mod 2^64) mod (2^61 - 1))
+ *   & 0xFFFFFFFF), k < num_perm; sigs is [ndocs, num_perm].  One workgroup per document, one permutation per lane:
+ *   BL_EINVAL unless 1 <= num_perm <= BL_DEDUP_MAX_PERM.  A repeated hash changes nothing (a minimum).
+ *
+ * bl_dedup_lsh_insert_query (index.py:39-46, the query and the insert): sigs [total, num_perm] holds the signatures of the
+ *   documents numbered 0 .. total - 1 in insertion order; band j of a document is its values [j rows, (j + 1) rows).  table
+ *   [bands, slots] uint32, 0xFFFFFFFF = empty, slots a power of two: per band an open-addressing table in which each band key
+ *   owns one slot holding the smallest document number inserted with that key; keys are told apart by comparing all `rows`
+ *   values with the stored signature.  The call files documents insert_from .. total - 1, and then (a second launch) writes
+ *   flags[i - query_from] = 1 if some document numbered below i shares a whole band with i, else 0, for i = query_from ..
+ *   total - 1.  The answers do not depend on the order in which the device runs the threads, nor on how the documents were
+ *   split into calls.  insert_from = 0 on an empty table rebuilds the index (growth, or a loaded checkpoint); query_from =
+ *   total asks nothing (flags may be NULL).  BL_EINVAL: bands * rows > num_perm, slots not a power of two, 2 * total > slots
+ *   (the load bound: rebuild at a larger capacity first), ranges out of order, null pointers.  *status (device, zeroed by the
+ *   caller once) has bit 0 / bit 1 set if an insert found no slot / a queried document was not in the table: both mean the
+ *   caller broke the contract, and the flags of that call are then not to be trusted. */
+#define BL_DEDUP_MAX_PERM 256
+int bl_dedup_sha1_u32(const uint8_t* bytes, int64_t nbytes, const int64_t* tok_off, int64_t ntokens, uint32_t* out, void* stream);
+int bl_dedup_minhash(const uint32_t* hashes, int64_t nhashes, const int64_t* doc_off, int64_t ndocs, const uint64_t* perm_a,
+                     const uint64_t* perm_b, int32_t num_perm, uint32_t* sigs, void* stream);
+int bl_dedup_lsh_insert_query(const uint32_t* sigs, int32_t num_perm, int32_t bands, int32_t rows, uint32_t* table, int64_t slots,
+                              int64_t insert_from, int64_t query_from, int64_t total, int32_t* flags, int32_t* status, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * `seq-great` / `seq-rat` relational-transformer block (reference buglab/models/layers/relational_transformer.py,
  * relational_multihead_attention.py, multihead_attention.py): the row-wise kernels around the MFMA GEMMs.

@@ -476,3 +476,89 @@ def make_report_dataset(n: int, seed: int = 0, kind: str = "graph"):
     rng = np.random.default_rng(seed)
     base = make_buglab_dataset(n, seed) if kind == "graph" else make_buglab_seq_dataset(n, seed)
     return [add_report_source(rng, p, package=f"package{i % 5}") for i, p in enumerate(base)]
+
+
+# ------------------------------------------------------------------------------------------------
+# A corpus for near-duplicate detection (buglab/data/deduplication): datapoints of make_report_dataset whose `text` is a real
+# Python function, in families --
+#   "base"       an unrelated function with its own identifiers;
+#   "copy"       the text of an earlier base function under another path;
+#   "rename"     the text of an earlier base function with k of its identifiers replaced by fresh ones, for each k of `rename_ks`;
+#   "short"      fewer distinct tokens than any sensible min_num_tokens;
+# each function present as `rewrites_per_function` datapoints that share its key (package_name, path, start of code_range) and
+# differ in one token, as the rewrites of one function do; with `scatter_keys` some functions' datapoints are not adjacent.
+def _dedup_function_text(name: str, identifiers: List[str], strings: List[str]) -> str:
+    ids = list(identifiers)
+    lines = [f"def {name}({', '.join(ids[:4])}):", f'    """{strings[0]}"""']
+    i = 4
+    while i + 3 <= len(ids):
+        a, b, c = ids[i:i + 3]
+        form = (i // 3) % 4
+        if form == 0:
+            lines.append(f"    {a} = {b} + {c} * 2")
+        elif form == 1:
+            lines += [f"    if {a} < {b}:", f"        {c} = {a}.get({strings[(i // 3) % len(strings)]!r}, None)"]
+        elif form == 2:
+            lines += [f"    for {a} in range({b}):", f"        {c}.append({a})"]
+        else:
+            lines.append(f"    {a}[{b}] = not {c}")
+        i += 3
+    lines.append(f"    return {', '.join(ids[i:] or ids[:1])}")
+    return "\n".join(lines) + "\n"
+
+
+def make_dedup_corpus(n: int, seed: int = 0, *, num_identifiers: int = 150, rename_ks=(2, 75), rewrites_per_function: int = 3,
+                      scatter_keys: bool = True):
+    """-> (datapoints, functions): `n` functions as n * rewrites_per_function BugLabData dicts, and per function a dict with its
+    `key` fields (package_name, path, start), `family`, `k` (identifiers renamed) and `base` (index of the function it derives
+    from, or None) in order of first appearance."""
+    rng = np.random.default_rng(seed)
+    points = make_report_dataset(n * rewrites_per_function, seed)
+    fresh = [0]
+
+    def identifier() -> str:
+        fresh[0] += 1
+        return f"{_identifier(rng)}_{fresh[0]}"
+
+    families = [("base", 0), ("base", 0), ("copy", 0)] + [("rename", int(k)) for k in rename_ks] + [("base", 0), ("short", 0)]
+    functions, texts, bases = [], [], []  # bases: (function index, identifiers, strings, name)
+    for f in range(n):
+        family, k = families[f % len(families)]
+        base = None
+        if family == "base":
+            ids = [identifier() for _ in range(num_identifiers)]
+            strings = [f"{_identifier(rng)} {fresh[0]} {j}" for j in range(4)]
+            name = identifier()
+            bases.append((f, ids, strings, name))
+            text = _dedup_function_text(name, ids, strings)
+        elif family == "short":
+            text = f"def {identifier()}(x):\n    return x\n"
+        else:
+            base, ids, strings, name = bases[int(rng.integers(0, len(bases)))]
+            ids = list(ids)
+            if family == "rename":
+                for j in rng.choice(len(ids), size=min(k, len(ids)), replace=False):
+                    ids[int(j)] = identifier()
+            text = _dedup_function_text(name, ids, strings)
+        line0, col0 = int(rng.integers(1, 500)), 4 * int(rng.integers(0, 3))
+        functions.append({"package_name": f"package{f % 7}", "path": f"package{f % 7}/module_{f}.py", "start": (line0, col0),
+                          "family": family, "k": k, "base": base})
+        texts.append(text)
+
+    datapoints = []
+    for f, (fn, text) in enumerate(zip(functions, texts)):
+        num_lines = text.count("\n")
+        for j in range(rewrites_per_function):
+            point = dict(points[f * rewrites_per_function + j])
+            point["graph"] = dict(point["graph"])
+            # the first datapoint carries the function as written; the others one rewritten token each
+            point["graph"]["text"] = text if j == 0 else text.replace(" + ", (" - ", " * ", " / ")[j % 3], 1).replace(" < ", " <= ", j % 2)
+            point["graph"]["path"] = fn["path"]
+            point["graph"]["code_range"] = (fn["start"], (fn["start"][0] + num_lines, 0))
+            point["package_name"] = fn["package_name"]
+            datapoints.append(point)
+    if scatter_keys and n >= 4:  # the last datapoint of every fourth function moves to the end: keys that are not adjacent
+        moved = [f * rewrites_per_function + rewrites_per_function - 1 for f in range(0, n, 4)] if rewrites_per_function > 1 else []
+        taken = set(moved)
+        datapoints = [p for i, p in enumerate(datapoints) if i not in taken] + [datapoints[i] for i in moved]
+    return datapoints, functions

@@ -1606,6 +1606,65 @@ def report_order(keys, keep, *, by_confidence: bool, k: int = 0) -> torch.Tensor
 
 
 # ------------------------------------------------------------------------------------------------
+# near-duplicate detection (csrc/bl_dedup.hip; include/buglab_hip.h::bl_dedup_sha1_u32, bl_dedup_minhash,
+# bl_dedup_lsh_insert_query).  torch has no arithmetic on unsigned 32 / 64-bit tensors, so the unsigned buffers travel as
+# int32 / int64 tensors holding the same bits.
+DEDUP_MAX_PERM = 256  # BL_DEDUP_MAX_PERM
+DEDUP_EMPTY_SLOT = -1  # 0xFFFFFFFF
+
+
+def _i64(t, name="offsets"):
+    return _req(t, torch.int64, name)
+
+
+def dedup_sha1_u32(token_bytes, tok_off) -> torch.Tensor:
+    """One hash value per token: the first four bytes of SHA-1(token) as a little-endian uint32 (returned as the int32 with the
+    same bits).  token_bytes uint8 [nbytes]: the tokens' UTF-8 bytes back to back; tok_off int64 [ntokens + 1].  No sync."""
+    _req(token_bytes, torch.uint8, "token_bytes"), _i64(tok_off, "tok_off")
+    if token_bytes.dim() != 1 or tok_off.dim() != 1 or tok_off.shape[0] < 1:
+        raise ValueError(f"dedup_sha1_u32: token_bytes {tuple(token_bytes.shape)} must be [nbytes] and tok_off {tuple(tok_off.shape)} [ntokens + 1]")
+    n = tok_off.shape[0] - 1
+    out = torch.empty(n, dtype=torch.int32, device=token_bytes.device)
+    _check(load_library().bl_dedup_sha1_u32(token_bytes.data_ptr(), token_bytes.numel(), tok_off.data_ptr(), n, out.data_ptr(), _stream()),
+           "bl_dedup_sha1_u32")
+    return out
+
+
+def dedup_minhash(hashes, doc_off, perm_a, perm_b, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """MinHash signatures int32 [ndocs, num_perm] (uint32 bits) of documents given as token hashes int32 [nhashes] with doc_off
+    int64 [ndocs + 1]; perm_a / perm_b int64 [num_perm] (uint64 bits).  `out`: rows of a larger signature matrix to fill.  No sync."""
+    _i32(hashes, "hashes"), _i64(doc_off, "doc_off"), _i64(perm_a, "perm_a"), _i64(perm_b, "perm_b")
+    if hashes.dim() != 1 or doc_off.dim() != 1 or doc_off.shape[0] < 1 or perm_a.dim() != 1 or perm_a.shape != perm_b.shape:
+        raise ValueError(f"dedup_minhash: inconsistent shapes (hashes {tuple(hashes.shape)}, doc_off {tuple(doc_off.shape)}, "
+                         f"perm_a {tuple(perm_a.shape)}, perm_b {tuple(perm_b.shape)})")
+    ndocs, num_perm = doc_off.shape[0] - 1, perm_a.shape[0]
+    if out is None:
+        out = torch.empty((ndocs, num_perm), dtype=torch.int32, device=hashes.device)
+    elif tuple(_i32(out, "out").shape) != (ndocs, num_perm):
+        raise ValueError(f"dedup_minhash: out {tuple(out.shape)} must be [{ndocs}, {num_perm}]")
+    _check(load_library().bl_dedup_minhash(hashes.data_ptr(), hashes.numel(), doc_off.data_ptr(), ndocs, perm_a.data_ptr(),
+                                           perm_b.data_ptr(), num_perm, out.data_ptr(), _stream()), "bl_dedup_minhash")
+    return out
+
+
+def dedup_lsh_insert_query(sigs, bands: int, rows: int, table, status, *, insert_from: int, query_from: int, total: int
+                           ) -> Optional[torch.Tensor]:
+    """Files documents insert_from .. total - 1 of sigs (int32 [>= total, num_perm]) in the band index `table` (int32
+    [bands, slots], DEDUP_EMPTY_SLOT where empty) and answers for documents query_from .. total - 1: int32 [total - query_from],
+    1 = an earlier document shares a whole band (None when query_from == total).  `status` int32 [1], zeroed once by the
+    caller: non-zero after a call that broke the load bound (see include/buglab_hip.h).  No sync."""
+    _i32(sigs, "sigs"), _i32(table, "table"), _i32(status, "status")
+    if sigs.dim() != 2 or table.dim() != 2 or table.shape[0] != bands or sigs.shape[0] < total:
+        raise ValueError(f"dedup_lsh_insert_query: sigs {tuple(sigs.shape)} must hold {total} rows and table {tuple(table.shape)} "
+                         f"{bands} bands")
+    flags = torch.empty(total - query_from, dtype=torch.int32, device=sigs.device) if 0 <= query_from < total else None
+    _check(load_library().bl_dedup_lsh_insert_query(sigs.data_ptr(), sigs.shape[1], int(bands), int(rows), table.data_ptr(),
+                                                    table.shape[1], int(insert_from), int(query_from), int(total), _p(flags),
+                                                    status.data_ptr(), _stream()), "bl_dedup_lsh_insert_query")
+    return flags
+
+
+# ------------------------------------------------------------------------------------------------
 # GREAT var-misuse head (csrc/bl_varmisuse_head.hip; include/buglab_hip.h::bl_varmisuse_head_t)
 def _byte_mask(t: torch.Tensor, name: str) -> torch.Tensor:
     return _req(t.view(torch.uint8) if t.dtype == torch.bool else t, torch.uint8, name)

@@ -181,6 +181,10 @@ _SIGNATURES = {
                              c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p,
                              c_void_p], ctypes.c_int),
     "bl_report_order": ([c_void_p, c_void_p, c_int64, c_int64, c_int32, c_void_p, c_void_p, c_void_p], ctypes.c_int),
+    "bl_dedup_sha1_u32": ([c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p], ctypes.c_int),
+    "bl_dedup_minhash": ([c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int32, c_void_p, c_void_p], ctypes.c_int),
+    "bl_dedup_lsh_insert_query": ([c_void_p, c_int32, c_int32, c_int32, c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p,
+                                   c_void_p], ctypes.c_int),
     "bl_add_layernorm_fwd": ([c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p], ctypes.c_int),
     "bl_add_layernorm_fwd_packed": ([c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                      c_void_p], ctypes.c_int),
