@@ -1,6 +1,10 @@
 """ctypes table of libbuglab_hip.so (include/buglab_hip.h): structures, prototypes, loader, argument helpers.
-Part of buglab.models.hip_ops (split in round 6: this file = the C ABI as Python sees it; _streams.py = stream policy and
-live timing; __init__.py = the operators and their autograd Functions).  No CPU fallback: HipOpsUnavailable."""
+Part of buglab.models.hip_ops: this file = the C ABI as Python sees it; _switches.py = the A/B switches; _streams.py = stream
+policy and live timing; the operators and their autograd Functions are in the domain modules (gemm, weights, graph, linear,
+heads, seq, services, optim, runtime) that the package re-exports.  No CPU fallback: HipOpsUnavailable.
+
+The library handle `_lib`, `LIB_PATH` and `CALL_COUNT` have their one copy HERE: the package forwards reads and assignments of
+these three names to this module (FORWARDED_BY_PACKAGE), every other module calls `load_library()` / `_check()`."""
 from __future__ import annotations
 
 import ctypes
@@ -9,6 +13,14 @@ from ctypes import POINTER, Structure, c_double, c_float, c_int8, c_int32, c_int
 from typing import List, NamedTuple, Optional, Sequence, Tuple
 
 import torch
+
+__all__ = [
+    "ACT_NONE", "ACT_RELU", "ACT_SIGMOID", "ACT_TANH", "ACT_GELU", "ACT_GELU_AGG", "_ACTS", "message_activation_code", "LIB_NAME",
+    "HipOpsUnavailable", "bl_rows_t", "bl_rows_packed_t", "bl_dropout_t", "bl_mp_layer_t", "bl_x6_epi_t", "bl_head_view_t",
+    "bl_packed_head_view_t", "bl_great_layer_t", "bl_great_layer_grads_t", "bl_pack_job_t", "bl_bug_loss_t", "bl_varmisuse_head_t",
+    "VARMISUSE_STATS", "_SIGNATURES", "EXPORTED_SYMBOLS", "load_library", "_check", "_stream", "_p", "_req", "_f32", "_i32", "Dropout",
+    "NO_DROPOUT", "RowSource", "_rows", "_rows_packed"]
+FORWARDED_BY_PACKAGE = ("CALL_COUNT", "_lib", "LIB_PATH")  # never star-imported: a copy would go stale
 
 ACT_NONE, ACT_RELU, ACT_SIGMOID, ACT_TANH, ACT_GELU, ACT_GELU_AGG = 0, 1, 2, 3, 4, 5
 # "gelu_aggregated": GELU on the aggregate of a segmented max (gelu(max x)) instead of on every item (max gelu(x)) -- only
@@ -358,3 +370,14 @@ def _rows(sources: Sequence[RowSource]) -> Tuple[bl_rows_t, int]:
     return r, K
 
 
+def _rows_packed(sources):
+    r = bl_rows_packed_t()
+    K = 0
+    for j, (xp, idx, width) in enumerate(sources):
+        _req(xp, torch.int16, f"packed source {j}")
+        r.xp[j] = xp.data_ptr()
+        r.idx[j] = _i32(idx).data_ptr() if idx is not None else None
+        r.width[j] = width
+        K += width
+    r.nsrc = len(sources)
+    return r, K

@@ -4,8 +4,8 @@
   opted in to direct gradient accumulation, keep running behind the main chain until `join_side_stream()`;
 * step stream: the training step's dependent chain on a high-priority stream (`use_step_stream`);
 * `KernelTimer` / `_timed`: HIP events around every launch for bench.py's roofline tables.
-All mutable state of the three lives HERE (one module, one copy); `hip_ops.USE_SIDE_STREAM = ...` on the package is forwarded
-to this module (hip_ops/__init__.py::_HipOpsModule)."""
+All mutable state of the three lives HERE (one module, one copy).  Their switches (USE_SIDE_STREAM, DIRECT_PARAM_GRAD,
+SIDE_STREAM_PRIORITY) are owned by _switches.py like every other switch and read from there at call time."""
 from __future__ import annotations
 
 import ctypes
@@ -15,7 +15,11 @@ from typing import Optional
 
 import torch
 
-from ._lib import _check, load_library
+from . import _switches
+from ._cabi import _check, load_library
+
+__all__ = ["KernelTimer", "_timed", "use_step_stream", "join_side_stream", "_opted_in_for_direct_grad", "_direct_small", "_direct_grad_target",
+           "_on_side_stream", "side_stream_if_any"]  # (what the package re-exports; the rest is reached as _streams.NAME)
 
 # ------------------------------------------------------------------------------------------------
 # optional live kernel timing (bench.py): HIP events recorded on the launch stream around each GEMM
@@ -92,31 +96,13 @@ class _timed:
 
 
 # ------------------------------------------------------------------------------------------------
-# side stream: weight-gradient GEMMs run next to the input-gradient chain of the same layer (both
-# only read the node gradient), so one kernel's prologue / epilogue / last-round tail is filled by
-# the other kernel's workgroups.  BL_SIDE_STREAM=0 disables.
+# side stream of the weight-gradient GEMMs (_switches.USE_SIDE_STREAM / DIRECT_PARAM_GRAD / SIDE_STREAM_PRIORITY)
 _side_streams = {}
-USE_SIDE_STREAM = os.environ.get("BL_SIDE_STREAM", "1") != "0"
-# Weight gradients of the message-passing layers are accumulated (fp32 atomics in the kernel)
-# straight into `param.grad` for parameters whose owner OPTED IN (`param._bl_direct_grad = True`, set by
-# FlatAdam, which pre-binds every .grad to a view of its flat gradient buffer), on the side stream, WITHOUT
-# joining at the end of the layer's backward: the side stream runs one weight-gradient GEMM after the other
-# behind the main chain and is joined once, by `join_side_stream()`, before the gradients are consumed
-# (FlatAdam.zero_grad / .step).  Parameters of any other optimiser get ordinary autograd gradients, complete
-# when backward() returns (the side stream is joined inside the layer's backward).
-DIRECT_PARAM_GRAD = os.environ.get("BL_DIRECT_GRAD", "1") != "0"
-
-
 _held_for_side_stream: list = []  # tensors the free-running side-stream GEMMs read: kept alive until the join
 
 
-# Priority of the side stream that carries the weight-gradient GEMMs (lower number = higher priority; out-of-range values are
-# mapped to the nearest valid one).  BL_SIDE_STREAM_PRIORITY: A/B knob.
-SIDE_STREAM_PRIORITY = int(os.environ.get("BL_SIDE_STREAM_PRIORITY", "0"))
-
-
 def _new_side_stream():
-    return torch.cuda.Stream(priority=SIDE_STREAM_PRIORITY) if SIDE_STREAM_PRIORITY != 0 else torch.cuda.Stream()
+    return torch.cuda.Stream(priority=_switches.SIDE_STREAM_PRIORITY) if _switches.SIDE_STREAM_PRIORITY != 0 else torch.cuda.Stream()
 
 
 # The training step's dependent chain (forward, the backward's input-gradient chain, clip + Adam) runs on a HIGH-priority stream,
@@ -168,7 +154,7 @@ def _opted_in_for_direct_grad(param) -> bool:
     tensor hooks registered on it would never fire -- so a parameter that has hooks (or post-accumulate-grad hooks) is treated
     as not opted in and receives its gradient through autograd as usual.  Parameters without the flag always take that
     path."""
-    if not (DIRECT_PARAM_GRAD and getattr(param, "_bl_direct_grad", False)):
+    if not (_switches.DIRECT_PARAM_GRAD and getattr(param, "_bl_direct_grad", False)):
         return False
     if getattr(param, "_backward_hooks", None) or getattr(param, "_post_accumulate_grad_hooks", None):
         return False
@@ -186,7 +172,7 @@ def _direct_small(param):
 
 def _direct_grad_target(param):
     g = getattr(param, "grad", None)
-    if (USE_SIDE_STREAM and _opted_in_for_direct_grad(param) and g is not None and g.is_cuda
+    if (_switches.USE_SIDE_STREAM and _opted_in_for_direct_grad(param) and g is not None and g.is_cuda
             and g.dtype == torch.float32 and g.is_contiguous()):
         return g
     return None
@@ -194,7 +180,7 @@ def _direct_grad_target(param):
 
 class _on_side_stream:
     def __init__(self, device):
-        self.enabled = USE_SIDE_STREAM
+        self.enabled = _switches.USE_SIDE_STREAM
         if self.enabled:
             key = torch.cuda.current_device()
             if key not in _side_streams:
@@ -239,7 +225,7 @@ def mark_free_running(*held) -> None:
 
 def side_stream_for_current_device():
     """The side stream of the current device (created on first use), or None when the side stream is switched off."""
-    if not USE_SIDE_STREAM:
+    if not _switches.USE_SIDE_STREAM:
         return None
     key = torch.cuda.current_device()
     if key not in _side_streams:

@@ -1,0 +1,189 @@
+"""Forward-only device services: ensemble combine, self-supervision scoring / sampling, bug reports, near-duplicate detection."""
+from __future__ import annotations
+
+from typing import Optional, Tuple
+
+import torch
+
+from ._cabi import _check, _f32, _i32, load_library, _p, _req, _stream
+
+__all__ = ["ENSEMBLE_KINDS", "ENSEMBLE_MAX_MEMBERS", "ensemble_combine", "SELECTOR_MAX_K", "_f64", "score_targets",
+           "selector_sample", "REPORT_MAX_SAMPLES", "REPORT_INDEX_FIELDS", "report_summarize", "report_order", "DEDUP_MAX_PERM",
+           "DEDUP_EMPTY_SLOT", "_i64", "dedup_sha1_u32", "dedup_minhash", "dedup_lsh_insert_query"]
+
+
+# ------------------------------------------------------------------------------------------------
+# ensemble combine (csrc/bl_ensemble.hip; include/buglab_hip.h::bl_ensemble_combine)
+ENSEMBLE_KINDS = {"avg": 0, "consensus": 1}  # BL_ENSEMBLE_AVG, BL_ENSEMBLE_CONSENSUS
+ENSEMBLE_MAX_MEMBERS = 16  # BL_ENSEMBLE_MAX_MEMBERS
+
+
+def ensemble_combine(src, loc_idx, loc_off, rw_idx, rw_off, kind: str) -> torch.Tensor:
+    """M members' concatenated flat fp32 outputs `src` -> the ensemble's values in the canonical layout, float64
+    [total_loc + total_rw] (locations first): ONE buffer, so the caller needs one device->host copy.  loc_idx [M, total_loc] /
+    rw_idx [M, total_rw] int32 (-1: member absent from that sample), loc_off / rw_off int32 [B + 1].  No sync."""
+    if kind not in ENSEMBLE_KINDS:
+        raise ValueError(f"ensemble_combine: kind must be one of {sorted(ENSEMBLE_KINDS)} (got {kind!r})")
+    _f32(src, "src")
+    _i32(loc_idx, "loc_idx"), _i32(rw_idx, "rw_idx"), _i32(loc_off, "loc_off"), _i32(rw_off, "rw_off")
+    M, total_loc = loc_idx.shape
+    total_rw = rw_idx.shape[1]
+    assert rw_idx.shape[0] == M and loc_off.shape == rw_off.shape
+    out = torch.empty(total_loc + total_rw, dtype=torch.float64, device=src.device)
+    _check(load_library().bl_ensemble_combine(src.data_ptr(), src.numel(), loc_idx.data_ptr(), loc_off.data_ptr(), total_loc,
+                                              rw_idx.data_ptr(), rw_off.data_ptr(), total_rw, M, loc_off.shape[0] - 1,
+                                              ENSEMBLE_KINDS[kind], out.data_ptr(), out.data_ptr() + 8 * total_loc, _stream()),
+           "bl_ensemble_combine")
+    return out
+
+
+# ------------------------------------------------------------------------------------------------
+# self-supervision services (csrc/bl_selfsup.hip; include/buglab_hip.h::bl_score_targets, bl_selector_sample)
+SELECTOR_MAX_K = 32  # BL_SELECTOR_MAX_K
+
+
+def _f64(t, name="tensor"):
+    return _req(t, torch.float64, name)
+
+
+def score_targets(src, tgt_loc, tgt_rw) -> torch.Tensor:
+    """The log-probability a model's flat fp32 output `src` gives to each sample's true fix, float64 [B]:
+    src[tgt_loc[b]] + (src[tgt_rw[b]] if tgt_rw[b] >= 0).  tgt_loc / tgt_rw int32 [B].  No sync."""
+    _f32(src, "src"), _i32(tgt_loc, "tgt_loc"), _i32(tgt_rw, "tgt_rw")
+    if tgt_loc.dim() != 1 or tgt_loc.shape != tgt_rw.shape:
+        raise ValueError(f"score_targets: tgt_loc {tuple(tgt_loc.shape)} and tgt_rw {tuple(tgt_rw.shape)} must both be [B]")
+    out = torch.empty(tgt_loc.shape[0], dtype=torch.float64, device=src.device)
+    _check(load_library().bl_score_targets(src.data_ptr(), src.numel(), tgt_loc.data_ptr(), tgt_rw.data_ptr(), tgt_loc.shape[0],
+                                           out.data_ptr(), _stream()), "bl_score_targets")
+    return out
+
+
+def selector_sample(src, rw_idx, rw_loc_idx, rw_off, nobug_idx, u_eps, u, *, temperature: float, epsilon: float, k: int
+                    ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Bug selection on a model's flat fp32 output `src` -> (logprob, p, entropy, selected).  Sample b owns the entries
+    rw_off[b] + b .. rw_off[b + 1] + b (its rewrites by original index, then NO_BUG) of logprob / p / u (float64
+    [total_rw + B]); entropy float64 [B]; selected int32 [B, k]: entry indices within the sample (n_b = NO_BUG) in descending
+    Gumbel-key order, -1 padded.  rw_idx / rw_loc_idx int32 [total_rw], rw_off int32 [B + 1], nobug_idx int32 [B], u_eps
+    float64 [B], u float64 [total_rw + B] in (0, 1).  No sync."""
+    _f32(src, "src")
+    _i32(rw_idx, "rw_idx"), _i32(rw_loc_idx, "rw_loc_idx"), _i32(rw_off, "rw_off"), _i32(nobug_idx, "nobug_idx")
+    _f64(u_eps, "u_eps"), _f64(u, "u")
+    B, total_rw = nobug_idx.shape[0], rw_idx.shape[0]
+    if rw_loc_idx.shape != rw_idx.shape or rw_off.shape[0] != B + 1 or u_eps.shape[0] != B or u.shape[0] != total_rw + B:
+        raise ValueError(f"selector_sample: inconsistent shapes (B {B}, total_rw {total_rw}, rw_loc_idx {tuple(rw_loc_idx.shape)}, "
+                         f"rw_off {tuple(rw_off.shape)}, u_eps {tuple(u_eps.shape)}, u {tuple(u.shape)})")
+    values = torch.empty(2 * (total_rw + B) + B, dtype=torch.float64, device=src.device)  # one buffer: [logprob | p | entropy]
+    selected = torch.empty((B, int(k)), dtype=torch.int32, device=src.device)
+    n = total_rw + B
+    _check(load_library().bl_selector_sample(src.data_ptr(), src.numel(), rw_idx.data_ptr(), rw_loc_idx.data_ptr(), rw_off.data_ptr(),
+                                             total_rw, nobug_idx.data_ptr(), B, u_eps.data_ptr(), u.data_ptr(), float(temperature),
+                                             float(epsilon), int(k), values.data_ptr(), values.data_ptr() + 8 * n,
+                                             values.data_ptr() + 16 * n, selected.data_ptr(), _stream()), "bl_selector_sample")
+    return values[:n], values[n:2 * n], values[2 * n:], selected
+
+
+# ------------------------------------------------------------------------------------------------
+# bug reports (csrc/bl_report.hip; include/buglab_hip.h::bl_report_summarize, bl_report_order)
+REPORT_MAX_SAMPLES = 1 << 20  # BL_REPORT_MAX_SAMPLES
+REPORT_INDEX_FIELDS = ("loc_idx", "loc_off", "rw_idx", "rw_off", "rw_eq_target", "grp_rw", "grp_rw_off", "grp_loc", "grp_shown",
+                       "grp_off", "tgt_grp", "ground_loc", "nobug_idx")
+
+
+def report_summarize(src, ix) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """The verdicts of one predict minibatch from a model's flat fp32 output `src` -> (best_rw int32 [total_grp],
+    best_range_logprob float64 [total_grp], sample_i int32 [3, B] = pred_loc | pred_is_nobug | is_wrong, sample_d float64
+    [2, B] = prediction_logprob | no_bug_logprob).  `ix`: a mapping with the int32 tensors of REPORT_INDEX_FIELDS
+    (buglab/models/_report.py::report_indices).  No sync."""
+    _f32(src, "src")
+    t = {name: _i32(ix[name], name) for name in REPORT_INDEX_FIELDS}
+    B, total_loc, total_rw, total_grp = t["nobug_idx"].shape[0], t["loc_idx"].shape[0], t["rw_idx"].shape[0], t["grp_loc"].shape[0]
+    sizes = {"loc_off": B + 1, "rw_off": B + 1, "grp_off": B + 1, "tgt_grp": B, "ground_loc": B, "rw_eq_target": total_rw,
+             "grp_rw": total_rw, "grp_rw_off": total_grp + 1, "grp_shown": total_grp}
+    bad = {name: tuple(t[name].shape) for name, n in sizes.items() if t[name].dim() != 1 or t[name].shape[0] != n}
+    if bad:
+        raise ValueError(f"report_summarize: inconsistent shapes (B {B}, total_loc {total_loc}, total_rw {total_rw}, "
+                         f"total_grp {total_grp}): {bad}")
+    best_rw = torch.empty(total_grp, dtype=torch.int32, device=src.device)
+    best_range = torch.empty(total_grp, dtype=torch.float64, device=src.device)
+    sample_i = torch.empty((3, B), dtype=torch.int32, device=src.device)
+    sample_d = torch.empty((2, B), dtype=torch.float64, device=src.device)
+    p = lambda name: t[name].data_ptr()
+    _check(load_library().bl_report_summarize(
+        src.data_ptr(), src.numel(), p("loc_idx"), p("loc_off"), total_loc, p("rw_idx"), p("rw_off"), total_rw, p("rw_eq_target"),
+        p("grp_rw"), p("grp_rw_off"), p("grp_loc"), p("grp_shown"), p("grp_off"), total_grp, p("tgt_grp"), p("ground_loc"),
+        p("nobug_idx"), B, best_rw.data_ptr(), best_range.data_ptr(), sample_i.data_ptr(), sample_d.data_ptr(), _stream()),
+        "bl_report_summarize")
+    return best_rw, best_range, sample_i, sample_d
+
+
+def report_order(keys, keep, *, by_confidence: bool, k: int = 0) -> torch.Tensor:
+    """The indices of the samples with keep != 0, int32, in report order: as Python's stable sorted(key=-keys[i]) when
+    `by_confidence`, else input order; the first k when k > 0.  keys float64 [n], keep int32 [n].  Syncs (reads the count)."""
+    _f64(keys, "keys"), _i32(keep, "keep")
+    if keys.dim() != 1 or keys.shape != keep.shape:
+        raise ValueError(f"report_order: keys {tuple(keys.shape)} and keep {tuple(keep.shape)} must both be [n]")
+    n = keys.shape[0]
+    out = torch.full((n,), -1, dtype=torch.int32, device=keys.device)
+    count = torch.zeros(1, dtype=torch.int32, device=keys.device)
+    _check(load_library().bl_report_order(keys.data_ptr(), keep.data_ptr(), n, int(k), int(bool(by_confidence)), out.data_ptr(),
+                                          count.data_ptr(), _stream()), "bl_report_order")
+    return out[:int(count.item())]
+
+
+# ------------------------------------------------------------------------------------------------
+# near-duplicate detection (csrc/bl_dedup.hip; include/buglab_hip.h::bl_dedup_sha1_u32, bl_dedup_minhash,
+# bl_dedup_lsh_insert_query).  torch has no arithmetic on unsigned 32 / 64-bit tensors, so the unsigned buffers travel as
+# int32 / int64 tensors holding the same bits.
+DEDUP_MAX_PERM = 256  # BL_DEDUP_MAX_PERM
+DEDUP_EMPTY_SLOT = -1  # 0xFFFFFFFF
+
+
+def _i64(t, name="offsets"):
+    return _req(t, torch.int64, name)
+
+
+def dedup_sha1_u32(token_bytes, tok_off) -> torch.Tensor:
+    """One hash value per token: the first four bytes of SHA-1(token) as a little-endian uint32 (returned as the int32 with the
+    same bits).  token_bytes uint8 [nbytes]: the tokens' UTF-8 bytes back to back; tok_off int64 [ntokens + 1].  No sync."""
+    _req(token_bytes, torch.uint8, "token_bytes"), _i64(tok_off, "tok_off")
+    if token_bytes.dim() != 1 or tok_off.dim() != 1 or tok_off.shape[0] < 1:
+        raise ValueError(f"dedup_sha1_u32: token_bytes {tuple(token_bytes.shape)} must be [nbytes] and tok_off {tuple(tok_off.shape)} [ntokens + 1]")
+    n = tok_off.shape[0] - 1
+    out = torch.empty(n, dtype=torch.int32, device=token_bytes.device)
+    _check(load_library().bl_dedup_sha1_u32(token_bytes.data_ptr(), token_bytes.numel(), tok_off.data_ptr(), n, out.data_ptr(), _stream()),
+           "bl_dedup_sha1_u32")
+    return out
+
+
+def dedup_minhash(hashes, doc_off, perm_a, perm_b, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """MinHash signatures int32 [ndocs, num_perm] (uint32 bits) of documents given as token hashes int32 [nhashes] with doc_off
+    int64 [ndocs + 1]; perm_a / perm_b int64 [num_perm] (uint64 bits).  `out`: rows of a larger signature matrix to fill.  No sync."""
+    _i32(hashes, "hashes"), _i64(doc_off, "doc_off"), _i64(perm_a, "perm_a"), _i64(perm_b, "perm_b")
+    if hashes.dim() != 1 or doc_off.dim() != 1 or doc_off.shape[0] < 1 or perm_a.dim() != 1 or perm_a.shape != perm_b.shape:
+        raise ValueError(f"dedup_minhash: inconsistent shapes (hashes {tuple(hashes.shape)}, doc_off {tuple(doc_off.shape)}, "
+                         f"perm_a {tuple(perm_a.shape)}, perm_b {tuple(perm_b.shape)})")
+    ndocs, num_perm = doc_off.shape[0] - 1, perm_a.shape[0]
+    if out is None:
+        out = torch.empty((ndocs, num_perm), dtype=torch.int32, device=hashes.device)
+    elif tuple(_i32(out, "out").shape) != (ndocs, num_perm):
+        raise ValueError(f"dedup_minhash: out {tuple(out.shape)} must be [{ndocs}, {num_perm}]")
+    _check(load_library().bl_dedup_minhash(hashes.data_ptr(), hashes.numel(), doc_off.data_ptr(), ndocs, perm_a.data_ptr(),
+                                           perm_b.data_ptr(), num_perm, out.data_ptr(), _stream()), "bl_dedup_minhash")
+    return out
+
+
+def dedup_lsh_insert_query(sigs, bands: int, rows: int, table, status, *, insert_from: int, query_from: int, total: int
+                           ) -> Optional[torch.Tensor]:
+    """Files documents insert_from .. total - 1 of sigs (int32 [>= total, num_perm]) in the band index `table` (int32
+    [bands, slots], DEDUP_EMPTY_SLOT where empty) and answers for documents query_from .. total - 1: int32 [total - query_from],
+    1 = an earlier document shares a whole band (None when query_from == total).  `status` int32 [1], zeroed once by the
+    caller: non-zero after a call that broke the load bound (see include/buglab_hip.h).  No sync."""
+    _i32(sigs, "sigs"), _i32(table, "table"), _i32(status, "status")
+    if sigs.dim() != 2 or table.dim() != 2 or table.shape[0] != bands or sigs.shape[0] < total:
+        raise ValueError(f"dedup_lsh_insert_query: sigs {tuple(sigs.shape)} must hold {total} rows and table {tuple(table.shape)} "
+                         f"{bands} bands")
+    flags = torch.empty(total - query_from, dtype=torch.int32, device=sigs.device) if 0 <= query_from < total else None
+    _check(load_library().bl_dedup_lsh_insert_query(sigs.data_ptr(), sigs.shape[1], int(bands), int(rows), table.data_ptr(),
+                                                    table.shape[1], int(insert_from), int(query_from), int(total), _p(flags),
+                                                    status.data_ptr(), _stream()), "bl_dedup_lsh_insert_query")
+    return flags

@@ -118,11 +118,10 @@ def _check_bf16x6_image_rule(lib, hip_ops):
 
 def test_ctypes_structures_match_the_c_layout(tmp_path):
     """Every structure that crosses the boundary by value or by pointer: size and every field offset as gcc lays the header's
-    declaration out == what the ctypes mirror in hip_ops/_lib.py says (a mismatch would shift every later field silently)."""
+    declaration out == what the ctypes mirror in hip_ops/_cabi.py says (a mismatch would shift every later field silently)."""
     import ctypes
-    import importlib
 
-    L = importlib.import_module("buglab.models.hip_ops._lib")  # (hip_ops._lib itself resolves to the loaded library)
+    from buglab.models.hip_ops import _cabi as L
 
     names = ["bl_rows_t", "bl_rows_packed_t", "bl_dropout_t", "bl_mp_layer_t", "bl_pack_job_t", "bl_bug_loss_t", "bl_x6_epi_t", "bl_head_view_t",
              "bl_packed_head_view_t", "bl_great_layer_t", "bl_great_layer_grads_t"]

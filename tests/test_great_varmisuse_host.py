@@ -162,9 +162,7 @@ def test_new_symbols_in_header_exports_and_ctypes_table(built_lib):
 
 
 def test_descriptor_layout_matches_ctypes_mirror(tmp_path):
-    import importlib
-
-    L = importlib.import_module("buglab.models.hip_ops._lib")
+    from buglab.models.hip_ops import _cabi as L
     cls = L.bl_varmisuse_head_t
     lines = ["#include <stdio.h>", "#include <stddef.h>", f'#include "{HEADER}"', "int main(void) {",
              '  printf("%zu %d", sizeof(bl_varmisuse_head_t), BL_VARMISUSE_STATS);']
