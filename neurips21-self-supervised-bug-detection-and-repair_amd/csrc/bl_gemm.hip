@@ -27,6 +27,7 @@
 #include <stdlib.h>
 
 #include "bl_common.h"
+#include "bl_gemm_host.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
@@ -539,33 +540,12 @@ static int gemm_wgrad_impl(const bl_rows_t* a, const float* g_c, int32_t ld_g, c
   BL_CHECK_ARG(Ksum == K, "bl_gemm_wgrad: K (%d) != sum of source widths (%d)", K, Ksum);
   BL_CHECK_ARG(M > 0 && N > 0 && N % 4 == 0 && ld_g % 4 == 0, "bl_gemm_wgrad: N/ld_g multiples of 4 required");
   BL_CHECK_ARG(g_c && gw && bl_aligned16(g_c), "bl_gemm_wgrad: g_c/gw null or misaligned");
-  // chunk of rows reduced by one workgroup: large enough to amortise the 128x128 atomic epilogue,
-  // small enough that >= ~1000 workgroups exist at minibatch sizes
-  // Rows reduced by one workgroup.  The workgroup count should fill an INTEGER number of rounds of
-  // resident workgroups (1.24 rounds at the old fixed chunk cost 38 % of this kernel in tail), while
-  // staying >= 256 rows so that the 128x128 atomic flush is amortised.
-  static int resident_plain = 0, resident_masked = 0;
-  int& resident = g_mask ? resident_masked : resident_plain;
-  if (resident == 0) {
-    int per_cu = 0;
-    hipError_t oe = g_mask ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, gemm_wgrad_kernel<32, 1, 2, true>, 256, 0)
-                           : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, gemm_wgrad_kernel<32, 1, 2, false>, 256, 0);
-    if (oe != hipSuccess || per_cu <= 0) per_cu = 3;
-    resident = per_cu * bl_num_cus();
-  }
+  // rows reduced by one workgroup: an integer number of rounds of resident workgroups, at most 1024 rows (bl_wgrad_kchunk)
+  const int resident = g_mask ? bl_resident_workgroups<gemm_wgrad_kernel<32, 1, 2, true>>(256, 3)
+                              : bl_resident_workgroups<gemm_wgrad_kernel<32, 1, 2, false>>(256, 3);
   const int ntiles_all = ((K + BM - 1) / BM) * ((N + BN - 1) / BN);
   const int extra = (group_ptr ? G : 0) * ntiles_all;  // partial last pieces of the groups
-  int kchunk = 256;
-  for (int rounds = 1; rounds <= 64; ++rounds) {
-    const long long slots = (long long)resident * rounds - extra;
-    if (slots <= 0) continue;
-    const long long kc = ((long long)M * ntiles_all + slots - 1) / slots;
-    if (kc <= 1024 || rounds == 64) {
-      kchunk = (int)((kc + 31) / 32 * 32);
-      break;
-    }
-  }
-  if (kchunk < 256) kchunk = 256;
+  const int kchunk = bl_wgrad_kchunk(M, ntiles_all, extra, resident, 1024);
   const int ntiles_n = (N + BN - 1) / BN;
   dim3 grid((M + kchunk - 1) / kchunk + (group_ptr ? G : 0), ((K + BM - 1) / BM) * ntiles_n);
   // (groups that share a weight slice through group_w have no defined order among themselves: not ordered)

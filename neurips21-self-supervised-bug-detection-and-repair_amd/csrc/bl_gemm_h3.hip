@@ -33,6 +33,7 @@
 #include <stdlib.h>
 
 #include "bl_common.h"
+#include "bl_gemm_host.h"
 #include "bl_x6_locate.h"
 #include "bl_h3_image.h"
 
@@ -490,15 +491,8 @@ extern "C" int bl_gemm_rows_h3(const bl_rows_packed_t* a, const uint32_t* win_bi
                                int32_t K, float out_scale, const float* a_amax_dev, float* c, int32_t ldc, void* stream) {
   const char* who = "bl_gemm_rows_h3";
   if (M == 0) return BL_OK;
-  BL_CHECK_ARG(a && a->nsrc >= 1 && a->nsrc <= 3, "%s: rows descriptor needs 1..3 sources", who);
-  int off = 0, koff[3] = {0, 0, 0};
-  for (int j = 0; j < a->nsrc; ++j) {
-    BL_CHECK_ARG(a->xp[j] && bl_aligned16(a->xp[j]) && a->width[j] > 0 && a->width[j] % 32 == 0,
-                 "%s: source %d: packed pointer 16-byte aligned and width a multiple of 32 required", who, j);
-    koff[j] = off;
-    off += a->width[j];
-  }
-  BL_CHECK_ARG(off == K, "%s: K (%d) != sum of source widths (%d)", who, K, off);
+  BlPackedRows r;
+  if (int rc = bl_packed_rows(who, a, K, r)) return rc;
   BL_CHECK_ARG(M > 0 && N > 0 && N % 4 == 0 && ldc % 4 == 0 && bp && c && bl_aligned16(bp) && bl_aligned16(c),
                "%s: N/ldc multiples of 4, aligned pointers required", who);
   BL_CHECK_ARG(b_group_stride % 8 == 0 && (G <= 1 || b_group_stride >= bl_packed_weight_elems_h3(1, K, N)),
@@ -507,13 +501,9 @@ extern "C" int bl_gemm_rows_h3(const bl_rows_packed_t* a, const uint32_t* win_bi
                "%s: the routed form needs exactly one gathered source and ld_bits >= K / 32", who);
   BL_CHECK_ARG(out_scale > 0.f, "%s: out_scale must be positive", who);
   dim3 grid((M + HBM - 1) / HBM + (group_ptr ? G : 0), (N + HBN - 1) / HBN);
-  const uint4* x0 = reinterpret_cast<const uint4*>(a->xp[0]);
-  const uint4* x1 = a->nsrc > 1 ? reinterpret_cast<const uint4*>(a->xp[1]) : nullptr;
-  const uint4* x2 = a->nsrc > 2 ? reinterpret_cast<const uint4*>(a->xp[2]) : nullptr;
-#define H3_ARGS                                                                                                          \
-  x0, x1, x2, a->idx[0], a->nsrc > 1 ? a->idx[1] : nullptr, a->nsrc > 2 ? a->idx[2] : nullptr, a->width[0],              \
-      a->nsrc > 1 ? a->width[1] : 0, a->nsrc > 2 ? a->width[2] : 0, koff[1], koff[2], a->nsrc, win_bits, ld_bits,        \
-      reinterpret_cast<const uint4*>(bp), (long long)(b_group_stride / 8), group_ptr, group_w, G, M, N, K, c, ldc, 1, out_scale, a_amax_dev
+#define H3_ARGS                                                                                                               \
+  BL_PACKED_ROWS_ARGS(r), win_bits, ld_bits, reinterpret_cast<const uint4*>(bp), (long long)(b_group_stride / 8), group_ptr, \
+      group_w, G, M, N, K, c, ldc, 1, out_scale, a_amax_dev
   if (g_h3_one_term) {
     if (win_bits)
       hipLaunchKernelGGL((gemm_rows_h3_kernel<true, true>), grid, dim3(256), 0, (hipStream_t)stream, H3_ARGS);
@@ -528,19 +518,11 @@ extern "C" int bl_gemm_rows_h3(const bl_rows_packed_t* a, const uint32_t* win_bi
 }
 
 int g_h3_kchunk_cap = 4096;  // rows per workgroup flush; follows bl_set_wgrad_kchunk_cap (csrc/bl_gemm_x6.hip)
-namespace {
+// (a template, so that naming the kernel here does not instantiate it ahead of the dispatch chain: the chain orders the code object)
 template <bool ROUTED>
-int wgrad_h3_resident() {
-  static int resident = 0;
-  if (resident == 0) {
-    int per_cu = 0;
-    hipError_t oe = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, gemm_wgrad_h3_kernel<ROUTED, false>, 256, 0);
-    if (oe != hipSuccess || per_cu <= 0) per_cu = 2;
-    resident = per_cu * bl_num_cus();
-  }
-  return resident;
+static int wgrad_h3_resident() {
+  return bl_resident_workgroups<gemm_wgrad_h3_kernel<ROUTED, false>>(256, 2);
 }
-}  // namespace
 
 extern "C" int bl_gemm_wgrad_h3(const bl_rows_packed_t* a, const uint16_t* g_packed, const int32_t* g_idx, const uint32_t* win_bits,
                                 int32_t ld_bits, const int32_t* group_ptr, const int32_t* group_w, int32_t G, int32_t M, int32_t N,
@@ -548,15 +530,8 @@ extern "C" int bl_gemm_wgrad_h3(const bl_rows_packed_t* a, const uint16_t* g_pac
                                 void* stream) {
   const char* who = "bl_gemm_wgrad_h3";
   if (M == 0) return BL_OK;
-  BL_CHECK_ARG(a && a->nsrc >= 1 && a->nsrc <= 3, "%s: rows descriptor needs 1..3 sources", who);
-  int off = 0, koff[3] = {0, 0, 0};
-  for (int j = 0; j < a->nsrc; ++j) {
-    BL_CHECK_ARG(a->xp[j] && bl_aligned16(a->xp[j]) && a->width[j] > 0 && a->width[j] % 32 == 0,
-                 "%s: source %d: packed pointer 16-byte aligned and width a multiple of 32 required", who, j);
-    koff[j] = off;
-    off += a->width[j];
-  }
-  BL_CHECK_ARG(off == K, "%s: K (%d) != sum of source widths (%d)", who, K, off);
+  BlPackedRows r;
+  if (int rc = bl_packed_rows(who, a, K, r)) return rc;
   BL_CHECK_ARG(M > 0 && N > 0 && N % 32 == 0 && g_packed && gw && bl_aligned16(g_packed) && out_scale > 0.f,
                "%s: N a multiple of 32, aligned pointers and a positive out_scale required", who);
   const bool routed = win_bits != nullptr;
@@ -564,27 +539,13 @@ extern "C" int bl_gemm_wgrad_h3(const bl_rows_packed_t* a, const uint16_t* g_pac
   const int resident = routed ? wgrad_h3_resident<true>() : wgrad_h3_resident<false>();
   const int ntiles_n = (N + HBN - 1) / HBN;
   const int ntiles_all = ((K + HBM - 1) / HBM) * ntiles_n;
-  const int extra = (group_ptr ? G : 0) * ntiles_all;
-  int kchunk = 256;
-  for (int rounds = 1; rounds <= 64; ++rounds) {
-    const long long slots = (long long)resident * rounds - extra;
-    if (slots <= 0) continue;
-    const long long kc = ((long long)M * ntiles_all + slots - 1) / slots;
-    if (kc <= g_h3_kchunk_cap || rounds == 64) {
-      kchunk = (int)((kc + 31) / 32 * 32);
-      break;
-    }
-  }
-  if (kchunk < 256) kchunk = 256;
+  const int kchunk = bl_wgrad_kchunk(M, ntiles_all, (group_ptr ? G : 0) * ntiles_all, resident, g_h3_kchunk_cap);
   dim3 grid((M + kchunk - 1) / kchunk + (group_ptr ? G : 0), ntiles_all);
   unsigned* order_ctr = group_w ? nullptr : bl_order_counters((group_ptr ? G : 1) * ntiles_all, stream);
   const int xcd = order_ctr ? 0 : 1;
-#define HW_ARGS                                                                                                                \
-  reinterpret_cast<const uint4*>(a->xp[0]), a->nsrc > 1 ? reinterpret_cast<const uint4*>(a->xp[1]) : nullptr,                  \
-      a->nsrc > 2 ? reinterpret_cast<const uint4*>(a->xp[2]) : nullptr, a->idx[0], a->nsrc > 1 ? a->idx[1] : nullptr,          \
-      a->nsrc > 2 ? a->idx[2] : nullptr, a->width[0], a->nsrc > 1 ? a->width[1] : 0, a->nsrc > 2 ? a->width[2] : 0, koff[1],   \
-      koff[2], a->nsrc, reinterpret_cast<const uint4*>(g_packed), g_idx, win_bits, ld_bits, group_ptr, group_w, G, M, N, K,     \
-      kchunk, gw, (long long)gw_group_stride, ld_gw, ntiles_n, xcd, order_ctr, out_scale, g_amax_dev
+#define HW_ARGS                                                                                                                  \
+  BL_PACKED_ROWS_ARGS(r), reinterpret_cast<const uint4*>(g_packed), g_idx, win_bits, ld_bits, group_ptr, group_w, G, M, N, K, kchunk, \
+      gw, (long long)gw_group_stride, ld_gw, ntiles_n, xcd, order_ctr, out_scale, g_amax_dev
   if (g_h3_one_term) {
     if (routed)
       hipLaunchKernelGGL((gemm_wgrad_h3_kernel<true, true>), grid, dim3(256), 0, (hipStream_t)stream, HW_ARGS);

@@ -25,6 +25,7 @@
 #include <stdlib.h>
 
 #include "bl_common.h"
+#include "bl_gemm_host.h"
 #include "bl_x6_locate.h"
 #include "bl_x6w_image.h"
 #include "bl_h3_image.h"
@@ -828,28 +829,28 @@ __global__ __launch_bounds__(512) void gemm_wgrad_x6_wide_kernel(
 }
 
 // ================================================================================================
-extern "C" int bl_pack_bf16x3(const float* x, int32_t ld, int64_t R, int32_t D, uint16_t* out, void* stream) {
+// rows [R, D] of x into columns [col_off, col_off + D) of a packed [R, D_total] matrix; cols: which entry point's width rule to report
+static int pack_bf16x3_impl(const char* who, bool cols, const float* x, int32_t ld, int64_t R, int32_t D, int32_t D_total, int32_t col_off,
+                            uint16_t* out, void* stream) {
   if (R == 0) return BL_OK;
-  BL_CHECK_ARG(x && out && bl_aligned16(x) && bl_aligned16(out), "bl_pack_bf16x3: null or misaligned pointer");
-  BL_CHECK_ARG(D > 0 && D % 8 == 0 && ld % 4 == 0, "bl_pack_bf16x3: D must be a multiple of 8 (got %d)", D);
+  BL_CHECK_ARG(x && out && bl_aligned16(x) && bl_aligned16(out), "%s: null or misaligned pointer", who);
+  const bool ok = D > 0 && D % 8 == 0 && ld % 4 == 0 && D_total % 8 == 0 && col_off % 8 == 0 && col_off >= 0 && col_off + D <= D_total;
+  if (cols) BL_CHECK_ARG(ok, "%s: widths / offset must be multiples of 8 with col_off + D <= D_total", who);
+  BL_CHECK_ARG(ok, "%s: D must be a multiple of 8 (got %d)", who, D);
   const long long total = (long long)R * (D / 8);
   hipLaunchKernelGGL(pack_rows_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, ld,
-                     (long long)R, D, reinterpret_cast<uint4*>(out), D / 8, 0);
-  BL_LAUNCH_CHECK("bl_pack_bf16x3");
+                     (long long)R, D, reinterpret_cast<uint4*>(out), D_total / 8, col_off / 8);
+  BL_LAUNCH_CHECK(who);
   return BL_OK;
+}
+
+extern "C" int bl_pack_bf16x3(const float* x, int32_t ld, int64_t R, int32_t D, uint16_t* out, void* stream) {
+  return pack_bf16x3_impl("bl_pack_bf16x3", false, x, ld, R, D, D, 0, out, stream);
 }
 
 extern "C" int bl_pack_bf16x3_cols(const float* x, int32_t ld, int64_t R, int32_t D, int32_t D_total, int32_t col_off,
                                    uint16_t* out, void* stream) {
-  if (R == 0) return BL_OK;
-  BL_CHECK_ARG(x && out && bl_aligned16(x) && bl_aligned16(out), "bl_pack_bf16x3_cols: null or misaligned pointer");
-  BL_CHECK_ARG(D > 0 && D % 8 == 0 && ld % 4 == 0 && D_total % 8 == 0 && col_off % 8 == 0 && col_off >= 0 && col_off + D <= D_total,
-               "bl_pack_bf16x3_cols: widths / offset must be multiples of 8 with col_off + D <= D_total");
-  const long long total = (long long)R * (D / 8);
-  hipLaunchKernelGGL(pack_rows_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, ld,
-                     (long long)R, D, reinterpret_cast<uint4*>(out), D_total / 8, col_off / 8);
-  BL_LAUNCH_CHECK("bl_pack_bf16x3_cols");
-  return BL_OK;
+  return pack_bf16x3_impl("bl_pack_bf16x3_cols", true, x, ld, R, D, D_total, col_off, out, stream);
 }
 
 extern "C" int bl_pack_weights_x6(const float* w, int32_t G, int32_t K, int32_t N, int32_t w_is_kn, uint16_t* out,
@@ -884,15 +885,8 @@ int gemm_rows_x6_impl(const char* who, const bl_rows_packed_t* a, const uint32_t
                       int64_t b_group_stride, const int32_t* group_ptr, const int32_t* group_w, int32_t G, int32_t M, int32_t N,
                       int32_t K, const X6Epi* epi, float* c, int32_t ldc, void* stream) {
   if (M == 0) return BL_OK;
-  BL_CHECK_ARG(a && a->nsrc >= 1 && a->nsrc <= 3, "%s: rows descriptor needs 1..3 sources", who);
-  int off = 0, koff[3] = {0, 0, 0};
-  for (int j = 0; j < a->nsrc; ++j) {
-    BL_CHECK_ARG(a->xp[j] && bl_aligned16(a->xp[j]) && a->width[j] > 0 && a->width[j] % 32 == 0,
-                 "%s: source %d: packed pointer 16-byte aligned and width a multiple of 32 required", who, j);
-    koff[j] = off;
-    off += a->width[j];
-  }
-  BL_CHECK_ARG(off == K, "%s: K (%d) != sum of source widths (%d)", who, K, off);
+  BlPackedRows r;
+  if (int rc = bl_packed_rows(who, a, K, r)) return rc;
   BL_CHECK_ARG(M > 0 && N > 0 && N % 4 == 0 && ldc % 4 == 0 && bp && c && bl_aligned16(bp) && bl_aligned16(c),
                "%s: N/ldc multiples of 4, aligned pointers required", who);
   BL_CHECK_ARG(b_group_stride % 8 == 0 && (G <= 1 || b_group_stride >= (int64_t)((N + 127) / 128) * (K / 32) * 12288),
@@ -902,15 +896,11 @@ int gemm_rows_x6_impl(const char* who, const bl_rows_packed_t* a, const uint32_t
   BL_CHECK_ARG(!(win_bits && epi), "%s: the routed form has no epilogue", who);
   dim3 grid((M + XBM - 1) / XBM + (group_ptr ? G : 0), (N + XBN - 1) / XBN);
   const int xcd = 1;  // XCD-contiguous tile order (x6_locate)
-  const uint4* x0 = reinterpret_cast<const uint4*>(a->xp[0]);
-  const uint4* x1 = a->nsrc > 1 ? reinterpret_cast<const uint4*>(a->xp[1]) : nullptr;
-  const uint4* x2 = a->nsrc > 2 ? reinterpret_cast<const uint4*>(a->xp[2]) : nullptr;
   X6Epi e = {nullptr, BL_ACT_NONE, 0u, 0u, 1.f, 0, nullptr, 0, nullptr, 1.f, nullptr, nullptr};
   if (epi) e = *epi;
-#define X6_ARGS                                                                                                          \
-  x0, x1, x2, a->idx[0], a->nsrc > 1 ? a->idx[1] : nullptr, a->nsrc > 2 ? a->idx[2] : nullptr, a->width[0],              \
-      a->nsrc > 1 ? a->width[1] : 0, a->nsrc > 2 ? a->width[2] : 0, koff[1], koff[2], a->nsrc, win_bits, ld_bits,        \
-      reinterpret_cast<const uint4*>(bp), (long long)(b_group_stride / 8), group_ptr, group_w, G, M, N, K, c, ldc, xcd, e
+#define X6_ARGS                                                                                                               \
+  BL_PACKED_ROWS_ARGS(r), win_bits, ld_bits, reinterpret_cast<const uint4*>(bp), (long long)(b_group_stride / 8), group_ptr, \
+      group_w, G, M, N, K, c, ldc, xcd, e
   if (win_bits)
     hipLaunchKernelGGL((gemm_rows_x6_kernel<true, -1>), grid, dim3(256), 0, (hipStream_t)stream, X6_ARGS);
   else if (epi && e.form == BL_X6_EPI_ACT_PACK && e.act == BL_ACT_RELU)
@@ -952,31 +942,18 @@ bool g_wgrad_wide = true;  // bl_set_wgrad_tile: A/B switch between the 256 x 12
 // 8192, concat layer 0.921 / 0.863 / 0.824 / 0.829 / 0.908 ms at 1024 / 2048 / 4096 / 8192 / 16384.
 int g_wgrad_kchunk_cap = 4096;
 
+// (a template, so that naming the kernel here does not instantiate it ahead of the dispatch chain: the chain orders the code object)
 template <bool ROUTED>
 int wgrad_x6_resident() {
-  static int resident = 0;
-  if (resident == 0) {
-    int per_cu = 0;
-    hipError_t oe = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, gemm_wgrad_x6_kernel<ROUTED>, 256, 0);
-    if (oe != hipSuccess || per_cu <= 0) per_cu = 2;
-    resident = per_cu * bl_num_cus();
-  }
-  return resident;
+  return bl_resident_workgroups<gemm_wgrad_x6_kernel<ROUTED>>(256, 2);
 }
 
 int gemm_wgrad_x6_impl(const char* who, const bl_rows_packed_t* a, const uint16_t* g_packed, const int32_t* g_idx,
                        const uint32_t* win_bits, int32_t ld_bits, const int32_t* group_ptr, const int32_t* group_w, int32_t G,
                        int32_t M, int32_t N, int32_t K, float* gw, int64_t gw_group_stride, int32_t ld_gw, void* stream) {
   if (M == 0) return BL_OK;
-  BL_CHECK_ARG(a && a->nsrc >= 1 && a->nsrc <= 3, "%s: rows descriptor needs 1..3 sources", who);
-  int off = 0, koff[3] = {0, 0, 0};
-  for (int j = 0; j < a->nsrc; ++j) {
-    BL_CHECK_ARG(a->xp[j] && bl_aligned16(a->xp[j]) && a->width[j] > 0 && a->width[j] % 32 == 0,
-                 "%s: source %d: packed pointer 16-byte aligned and width a multiple of 32 required", who, j);
-    koff[j] = off;
-    off += a->width[j];
-  }
-  BL_CHECK_ARG(off == K, "%s: K (%d) != sum of source widths (%d)", who, K, off);
+  BlPackedRows r;
+  if (int rc = bl_packed_rows(who, a, K, r)) return rc;
   BL_CHECK_ARG(M > 0 && N > 0 && N % 32 == 0 && g_packed && gw && bl_aligned16(g_packed),
                "%s: N a multiple of 32 and aligned pointers required", who);
   const bool routed = win_bits != nullptr;
@@ -993,30 +970,16 @@ int gemm_wgrad_x6_impl(const char* who, const bl_rows_packed_t* a, const uint16_
   // plain (direct-row) weight gradients with few rows -- the sequence models' Linears, 16 384 token rows -- are faster on the
   // 128 x 128 tile (two workgroups per CU): 58 vs 64 us per launch at seq-great's shapes (profiles/r03q / r04m seq kernel stats)
   if (!gather && M < 65536) wide = false;
-  // rows reduced by one workgroup: an integer number of rounds of resident workgroups (see bl_gemm.hip)
+  // rows reduced by one workgroup: an integer number of rounds of resident workgroups (bl_wgrad_kchunk)
   const int resident = wide ? bl_num_cus() : (routed ? wgrad_x6_resident<true>() : wgrad_x6_resident<false>());
   const int ntiles_n = (N + XBN - 1) / XBN;
   const int ntiles_all = ((K + (wide ? 255 : XBM - 1)) / (wide ? 256 : XBM)) * ntiles_n;
-  const int extra = (group_ptr ? G : 0) * ntiles_all;
-  int kchunk = 256;
-  for (int rounds = 1; rounds <= 64; ++rounds) {
-    const long long slots = (long long)resident * rounds - extra;
-    if (slots <= 0) continue;
-    const long long kc = ((long long)M * ntiles_all + slots - 1) / slots;
-    if (kc <= g_wgrad_kchunk_cap || rounds == 64) {
-      kchunk = (int)((kc + 31) / 32 * 32);
-      break;
-    }
-  }
-  if (kchunk < 256) kchunk = 256;
+  const int kchunk = bl_wgrad_kchunk(M, ntiles_all, (group_ptr ? G : 0) * ntiles_all, resident, g_wgrad_kchunk_cap);
   dim3 grid((M + kchunk - 1) / kchunk + (group_ptr ? G : 0), ntiles_all);
   unsigned* order_ctr = group_w ? nullptr : bl_order_counters((group_ptr ? G : 1) * ntiles_all, stream);
   const int xcd = order_ctr ? 0 : 1;  // ordered flushes want "lower chunk = lower workgroup id"
-#define WX6_ARGS                                                                                                               \
-  reinterpret_cast<const uint4*>(a->xp[0]), a->nsrc > 1 ? reinterpret_cast<const uint4*>(a->xp[1]) : nullptr,                  \
-      a->nsrc > 2 ? reinterpret_cast<const uint4*>(a->xp[2]) : nullptr, a->idx[0], a->nsrc > 1 ? a->idx[1] : nullptr,          \
-      a->nsrc > 2 ? a->idx[2] : nullptr, a->width[0], a->nsrc > 1 ? a->width[1] : 0, a->nsrc > 2 ? a->width[2] : 0, koff[1],   \
-      koff[2], a->nsrc, reinterpret_cast<const uint4*>(g_packed), g_idx, win_bits, ld_bits, group_ptr, group_w, G, M, N, K,     \
+#define WX6_ARGS                                                                                                              \
+  BL_PACKED_ROWS_ARGS(r), reinterpret_cast<const uint4*>(g_packed), g_idx, win_bits, ld_bits, group_ptr, group_w, G, M, N, K, \
       kchunk, gw, (long long)gw_group_stride, ld_gw, ntiles_n, xcd, order_ctr
   if (wide && routed)
     hipLaunchKernelGGL((gemm_wgrad_x6_wide_kernel<true, true>), grid, dim3(512), 0, (hipStream_t)stream, WX6_ARGS);

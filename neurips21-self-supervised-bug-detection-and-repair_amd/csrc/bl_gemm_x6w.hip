@@ -42,6 +42,7 @@
 #include <atomic>
 
 #include "bl_common.h"
+#include "bl_gemm_host.h"
 #include "bl_x6_locate.h"
 #include "bl_x6w_image.h"
 
@@ -320,15 +321,8 @@ extern "C" int bl_gemm_rows_x6w(const bl_rows_packed_t* a, const uint32_t* win_b
                                 int32_t N, int32_t K, float* c, int32_t ldc, void* stream) {
   const char* who = "bl_gemm_rows_x6w";
   if (M == 0) return BL_OK;
-  BL_CHECK_ARG(a && a->nsrc >= 1 && a->nsrc <= 3, "%s: rows descriptor needs 1..3 sources", who);
-  int off = 0, koff[3] = {0, 0, 0};
-  for (int j = 0; j < a->nsrc; ++j) {
-    BL_CHECK_ARG(a->xp[j] && bl_aligned16(a->xp[j]) && a->width[j] > 0 && a->width[j] % 32 == 0,
-                 "%s: source %d: packed pointer 16-byte aligned and width a multiple of 32 required", who, j);
-    koff[j] = off;
-    off += a->width[j];
-  }
-  BL_CHECK_ARG(off == K, "%s: K (%d) != sum of source widths (%d)", who, K, off);
+  BlPackedRows r;
+  if (int rc = bl_packed_rows(who, a, K, r)) return rc;
   BL_CHECK_ARG(N > 0 && N % WBN == 0 && K >= 64 && K % 64 == 0, "%s: N must be a multiple of 256 and K of 64 (bl_gemm_rows_x6w_ok)", who);
   BL_CHECK_ARG(M > 0 && ldc % 4 == 0 && bp && c && bl_aligned16(bp) && bl_aligned16(c), "%s: ldc a multiple of 4, aligned pointers required", who);
   BL_CHECK_ARG(b_group_stride % 8 == 0 && (G <= 1 || b_group_stride >= bl_packed_weight_elems_x6w(1, K, N)),
@@ -346,10 +340,7 @@ extern "C" int bl_gemm_rows_x6w(const bl_rows_packed_t* a, const uint32_t* win_b
   }
   dim3 grid((M + WBM - 1) / WBM + (group_ptr ? G : 0), N / WBN);
 #define X6W_ARGS                                                                                                              \
-  reinterpret_cast<const uint4*>(a->xp[0]), a->nsrc > 1 ? reinterpret_cast<const uint4*>(a->xp[1]) : nullptr,                   \
-      a->nsrc > 2 ? reinterpret_cast<const uint4*>(a->xp[2]) : nullptr, a->idx[0], a->nsrc > 1 ? a->idx[1] : nullptr,           \
-      a->nsrc > 2 ? a->idx[2] : nullptr, a->width[0], a->nsrc > 1 ? a->width[1] : 0, a->nsrc > 2 ? a->width[2] : 0, koff[1],    \
-      koff[2], a->nsrc, win_bits, ld_bits, reinterpret_cast<const uint4*>(bp), (long long)(b_group_stride / 8), group_ptr,      \
+  BL_PACKED_ROWS_ARGS(r), win_bits, ld_bits, reinterpret_cast<const uint4*>(bp), (long long)(b_group_stride / 8), group_ptr, \
       group_w, G, M, N, K, c, ldc
   if (win_bits)
     hipLaunchKernelGGL((gemm_rows_x6w_kernel<true>), grid, dim3(512), lds, (hipStream_t)stream, X6W_ARGS);

@@ -20,6 +20,7 @@
 // the partner wave through LDS.  Workgroups are persistent (grid = resident workgroups) and keep their column sums in LDS
 // across tiles: one flush per workgroup.
 #include "bl_common.h"
+#include "bl_gemm_host.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
@@ -343,19 +344,11 @@ __global__ __launch_bounds__(256, 2) void node_bwd_kernel(
   }
 }
 
-int g_node_bwd_resident[3] = {0, 0, 0};
-
 template <int NT>
 int node_bwd_launch(const float* g_out, const float* h_out, int nrows, int K, bl_drop_dev drop, uint16_t* gz_packed, float* g_bias,
                     const uint16_t* wd_packed_bwd, const float* agg, const float* mean, const float* rstd, const float* gamma,
                     const float* dact, float* gq_f32, uint16_t* gq_packed, float* g_gamma, float* g_beta, float* gq_amax, hipStream_t st) {
-  int& resident = g_node_bwd_resident[NT];
-  if (resident == 0) {
-    int per_cu = 0;
-    hipError_t oe = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, node_bwd_kernel<NT>, 256, 0);
-    if (oe != hipSuccess || per_cu <= 0) per_cu = 1;
-    resident = per_cu * bl_num_cus();
-  }
+  const int resident = bl_resident_workgroups<node_bwd_kernel<NT>>(256, 1);
   const int ntiles = (nrows + NB_ROWS - 1) / NB_ROWS;
   const int grid = ntiles < resident ? ntiles : resident;
   hipLaunchKernelGGL((node_bwd_kernel<NT>), dim3(grid), dim3(256), 0, st, g_out, h_out, nrows, K, drop,
