@@ -752,6 +752,39 @@ int bl_report_order(const double* keys, const int32_t* keep, int64_t n, int64_t 
                     int32_t* out_count, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Evaluation (buglab/models/evaluate.py:60-140: `judge_sample`, what one sample contributes to the metrics and the threshold
+ * curves), in csrc/bl_evaluate.hip.  Same conventions as the bug reports: src = a model's flat fp32 output (n_src floats), int32
+ * indices, DOUBLE confidence, no atomics, bit-identical from run to run, an index outside [0, n_src) reads as NaN, "first
+ * maximum" is Python's max().
+ *
+ * bl_eval_judge, one launch per predict minibatch of B samples, no synchronisation.  Sample b owns
+ *   loc_idx[loc_off[b] : loc_off[b + 1]]   its location entries in the key order of the dict `predict` yields, NO_BUG last, and
+ *                                          key_node alongside: the dense id of the entry's node within the sample (its index in
+ *                                          np.unique(reference_nodes)), -1 for NO_BUG;
+ *   rw_idx [rw_off[b]  : rw_off[b + 1]]    its rewrites by original index (as PredictionLayout), rw_node alongside: the dense id
+ *                                          of the rewrite's reference node;
+ *   tgt_rw[b]                              target_fix_action_idx (an index within the sample's rewrites), -1 without a bug.
+ * Everything is decided by node identity, as the host compares node ids: two entries that share a flat index stay two keys, and
+ * a target whose node has no entry can never be "location correct".
+ *   predicted entry  the first maximum over the location entries; with assume_buggy != 0 over all but the last (NO_BUG);
+ *   best rewrite at a node (the predicted one, the target's one): the greatest log-probability STRICTLY above -inf among the
+ *                    rewrites at that node, lowest index among equals, NaN never; "none" if there is no such rewrite or the
+ *                    node is NO_BUG.
+ * Results go to sample offset + b of buffers the caller keeps for the whole run (capacity samples; offset + B <= capacity):
+ *   out_conf    [capacity]     src[predicted entry], exact; with assume_buggy minus the log-sum-exp of the entries the maximum
+ *                              was taken over, in fp64: shifted by their maximum, exp summed over a fixed tree;
+ *   out_verdict [4, capacity]  warned (the predicted entry is not NO_BUG) | location_correct (predicted node == the target's
+ *                              node; NO_BUG predicted without a bug) | repair_given_location (best rewrite at the target's node ==
+ *                              tgt_rw; -1 without a bug) | repaired (location_correct and best rewrite at the predicted node ==
+ *                              tgt_rw, "none" == the -1 of a sample without a bug).
+ * A sample with no entry to choose from gets confidence NaN and "NO_BUG predicted"; the host refuses such a sample first.
+ * BL_EINVAL: null pointers, negative sizes, offset + B > capacity.  BL_ERANGE: n_src, total_loc or total_rw beyond int32. */
+int bl_eval_judge(const float* src, int64_t n_src, const int32_t* loc_idx, const int32_t* loc_off, const int32_t* key_node,
+                  int64_t total_loc, const int32_t* rw_idx, const int32_t* rw_off, const int32_t* rw_node, int64_t total_rw,
+                  const int32_t* tgt_rw, int32_t B, int32_t assume_buggy, double* out_conf, int32_t* out_verdict, int64_t offset,
+                  int64_t capacity, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Near-duplicate detection (buglab/data/deduplication/index.py:15-70: `DuplicationIndex.check_if_duplicate_and_add`, which
  * updates a 256-permutation MinHash one token at a time and keeps one Python dict per LSH band), in csrc/bl_dedup.hip.  The
  * arithmetic is the written specification of DESIGN.md "Near-duplicate detection"; all of it is integer work and every result is

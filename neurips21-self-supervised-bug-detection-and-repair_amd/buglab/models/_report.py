@@ -120,15 +120,14 @@ def assemble(loc_idx: np.ndarray, loc_off: np.ndarray, rw_idx: np.ndarray, rw_of
                          i32(grp_off), i32([s.tgt_grp for s in groups]), i32([s.ground_loc for s in groups]), i32(nobug))
 
 
-def report_indices(layout, datapoints: Sequence[Any], node_mappings: Optional[Sequence[Dict[int, int]]] = None
-                   ) -> Tuple[ReportIndices, List[SampleGroups], List[List[int]]]:
-    """-> (the minibatch's arrays, each sample's groups, each sample's location keys).  `layout`: the minibatch's
-    `PredictionLayout` (canonical location order: np.unique(reference_nodes), NO_BUG); `node_mappings`: the sequence
-    models' node -> token maps (`mb["node_mappings"]`), None for graph models."""
-    B = layout.num_samples
-    assert len(datapoints) == B
+def location_entries(layout, datapoints: Sequence[Any], node_mappings: Optional[Sequence[Dict[int, int]]] = None
+                     ) -> Tuple[np.ndarray, List[List[int]]]:
+    """-> (`layout.loc_idx` with every sample's entries in the key order of the dict `predict` yields, each sample's location
+    keys in that order).  The layout's own order is canonical (np.unique(reference_nodes), NO_BUG): graph models keep it, the
+    sequence models' keys go token by token (`location_keys`).  Shared by the report and the evaluation index arrays."""
+    assert len(datapoints) == layout.num_samples
     loc_idx = layout.loc_idx.copy()
-    groups, all_keys = [], []
+    all_keys = []
     for b, point in enumerate(datapoints):
         keys = location_keys(point, None if node_mappings is None else node_mappings[b])
         lo, hi = int(layout.loc_off[b]), int(layout.loc_off[b + 1])
@@ -136,8 +135,17 @@ def report_indices(layout, datapoints: Sequence[Any], node_mappings: Optional[Se
         if node_mappings is not None:
             canonical = {n: i for i, n in enumerate(sorted(keys[:-1]))}
             loc_idx[lo:hi - 1] = layout.loc_idx[lo:hi - 1][[canonical[k] for k in keys[:-1]]]
-        groups.append(sample_groups(point, keys))
         all_keys.append(keys)
+    return loc_idx, all_keys
+
+
+def report_indices(layout, datapoints: Sequence[Any], node_mappings: Optional[Sequence[Dict[int, int]]] = None
+                   ) -> Tuple[ReportIndices, List[SampleGroups], List[List[int]]]:
+    """-> (the minibatch's arrays, each sample's groups, each sample's location keys).  `layout`: the minibatch's
+    `PredictionLayout` (canonical location order: np.unique(reference_nodes), NO_BUG); `node_mappings`: the sequence
+    models' node -> token maps (`mb["node_mappings"]`), None for graph models."""
+    loc_idx, all_keys = location_entries(layout, datapoints, node_mappings)
+    groups = [sample_groups(point, keys) for point, keys in zip(datapoints, all_keys)]
     return assemble(loc_idx, layout.loc_off, layout.rw_idx, layout.rw_off, groups), groups, all_keys
 
 

@@ -8,6 +8,8 @@ Options:
     --eval-only-no-bug         Evaluate only NO_BUG samples.
     --limit-num-elements=<num> Limit the number of elements to evaluate on.
     --sequential               Do not parallelize data loading. Makes debugging easier.
+    --on-device                Judge every predict minibatch on the device (single models only; same report).
+    --report-json=<path>       Also write the report as data: summary, per-scout tables and curves.
     --minibatch-size=<size>    Accepted for command-line compatibility (the reference parses and ignores it too).
     --restore-path=<path>      Accepted for command-line compatibility (unused by the reference's run()).
     --quiet                    Accepted for command-line compatibility.
@@ -20,13 +22,20 @@ joint / detection / localization / repair-given-location accuracies, the per-sco
 threshold curves (false-discovery rate, detection precision / recall, NO_BUG precision, detect-and-repair precision /
 recall) sampled at 100 thresholds.  tests/test_evaluate_golden.py compares the report with the one the reference's
 own loop prints for the same predictions.
+
+Two paths give the same report.  The default one walks the `(datapoint, location_logprobs, rewrite_logprobs)` triples of
+`model.predict` on the host, one sample at a time (`judge_sample`).  `--on-device` (`evaluate_on_device`) leaves the model's flat
+output on the device, judges each predict minibatch there in one launch (hip_ops.eval_judge, csrc/bl_evaluate.hip, through the
+index arrays of buglab/models/_evaluate.py), keeps the outcome columns on the device for the whole run and copies them back once;
+the counts and curves are then the same NumPy code on columns (`ColumnarEvaluationReport`).
 """
 import argparse
+import json
 import math
 import sys
 from collections import defaultdict
 from pathlib import Path
-from typing import Dict, Iterable, List, NamedTuple, Optional
+from typing import Any, Dict, Iterable, List, NamedTuple, Optional, Sequence
 
 if __package__ in (None, ""):
     sys.path.insert(0, str(Path(__file__).resolve().parents[2]))
@@ -86,6 +95,32 @@ def judge_sample(datapoint, location_logprobs: Dict[int, float], rewrite_logprob
                          repair_given_location, location_correct and predicted_rewrite == target, scout)
 
 
+def _curves_of_ranked(has_bug: np.ndarray, warned: np.ndarray, loc_ok: np.ndarray, repair_ok: np.ndarray, confidence: np.ndarray
+                      ) -> Dict[str, np.ndarray]:
+    """The threshold curves from boolean columns and confidences that are already in ranking order."""
+    num_buggy = int(has_bug.sum())
+    det_true = np.cumsum(has_bug & loc_ok)
+    det_false = np.cumsum(warned & ~loc_ok)
+    full_true = np.cumsum(has_bug & loc_ok & repair_ok)
+    full_false = np.cumsum(warned & (~loc_ok | ~repair_ok))
+    false_alarms = np.cumsum(warned & ~has_bug)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        running = {
+            "fdr": det_false / (det_true + det_false),
+            "detection_precision": det_true / (det_true + det_false),
+            "detection_recall": det_true / num_buggy,
+            "no_bug_precision": 1 - false_alarms / (num_buggy + 1e-10),
+            "precision": full_true / (full_true + full_false),
+            "recall": full_true / num_buggy,
+        }
+    x = np.linspace(0, 1, num=CURVE_POINTS)
+    prob = np.exp(confidence)
+    out = {"x": x}
+    for name, values in running.items():  # np.interp wants increasing abscissae: walk the ranking backwards
+        out[name] = np.interp(x, prob[::-1], values[::-1], right=0)
+    return out
+
+
 class EvaluationReport:
     """Aggregates SampleOutcomes; `summary()` = the scalar metrics, `curves()` = the threshold curves, `format()` =
     the text the reference prints."""
@@ -142,29 +177,8 @@ class EvaluationReport:
         correct code counts as a wrong location; NO_BUG precision is 1 - false alarms / (number of buggy samples)."""
         ranked = sorted(self.outcomes, key=lambda o: tuple(o[:5]), reverse=True)
         col = lambda f: np.array([f(o) for o in ranked], dtype=bool)
-        has_bug, warned, loc_ok = col(lambda o: o.has_bug), col(lambda o: o.warned), col(lambda o: o.location_correct)
-        repair_ok = col(lambda o: bool(o.repair_given_location))
-        num_buggy = int(has_bug.sum())
-        det_true = np.cumsum(has_bug & loc_ok)
-        det_false = np.cumsum(warned & ~loc_ok)
-        full_true = np.cumsum(has_bug & loc_ok & repair_ok)
-        full_false = np.cumsum(warned & (~loc_ok | ~repair_ok))
-        false_alarms = np.cumsum(warned & ~has_bug)
-        with np.errstate(divide="ignore", invalid="ignore"):
-            running = {
-                "fdr": det_false / (det_true + det_false),
-                "detection_precision": det_true / (det_true + det_false),
-                "detection_recall": det_true / num_buggy,
-                "no_bug_precision": 1 - false_alarms / (num_buggy + 1e-10),
-                "precision": full_true / (full_true + full_false),
-                "recall": full_true / num_buggy,
-            }
-        x = np.linspace(0, 1, num=CURVE_POINTS)
-        prob = np.exp(np.array([o.confidence for o in ranked]))
-        out = {"x": x}
-        for name, values in running.items():  # np.interp wants increasing abscissae: walk the ranking backwards
-            out[name] = np.interp(x, prob[::-1], values[::-1], right=0)
-        return out
+        return _curves_of_ranked(col(lambda o: o.has_bug), col(lambda o: o.warned), col(lambda o: o.location_correct),
+                                 col(lambda o: bool(o.repair_given_location)), np.array([o.confidence for o in ranked]))
 
     # ---- text -------------------------------------------------------------------------------------
     def format(self) -> str:
@@ -211,6 +225,157 @@ def evaluate_predictions(predictions, assume_buggy: bool = False, eval_only_no_b
     return EvaluationReport(outcomes)
 
 
+class ColumnarEvaluationReport(EvaluationReport):
+    """The same report from outcome COLUMNS (one NumPy array per SampleOutcome field) instead of a list of tuples: what
+    `evaluate_on_device` copies back.  `repair_given_location`: 1 / 0, -1 = the host's None (no bug); `scout`: ids into
+    `scout_names`, where id 0 is "NoBug".  Counts and curves are vectorised; `format()` is inherited, so the text is the host
+    path's text."""
+
+    def __init__(self, confidence, has_bug, warned, location_correct, repair_given_location, repaired, scout,
+                 scout_names: Sequence[str] = ("NoBug",), eval_only_no_bug: bool = False):
+        has_bug = np.asarray(has_bug, dtype=bool)
+        keep = ~has_bug if eval_only_no_bug else np.ones(has_bug.shape[0], dtype=bool)
+        self.confidence = np.asarray(confidence, dtype=np.float64)[keep]
+        self.has_bug = has_bug[keep]
+        self.warned = np.asarray(warned, dtype=bool)[keep]
+        self.location_correct = np.asarray(location_correct, dtype=bool)[keep]
+        self.repair_given_location = np.asarray(repair_given_location, dtype=np.int8)[keep]
+        self.repaired = np.asarray(repaired, dtype=bool)[keep]
+        self.scout = np.asarray(scout, dtype=np.int64)[keep]
+        self.scout_names = list(scout_names)
+        assert self.scout_names and self.scout_names[0] == "NoBug"
+        assert all(c.shape == self.confidence.shape for c in (self.has_bug, self.warned, self.location_correct,
+                                                                self.repair_given_location, self.repaired, self.scout))
+
+    @classmethod
+    def from_outcomes(cls, outcomes: Iterable[SampleOutcome], eval_only_no_bug: bool = False) -> "ColumnarEvaluationReport":
+        outcomes = list(outcomes)
+        names = ["NoBug"] + sorted({o.scout for o in outcomes} - {"NoBug"})
+        ids = {n: i for i, n in enumerate(names)}
+        return cls([o.confidence for o in outcomes], [o.has_bug for o in outcomes], [o.warned for o in outcomes],
+                   [o.location_correct for o in outcomes], [-1 if o.repair_given_location is None else int(o.repair_given_location)
+                                                            for o in outcomes],
+                   [o.repaired for o in outcomes], [ids[o.scout] for o in outcomes], names, eval_only_no_bug)
+
+    @property
+    def outcomes(self) -> List[SampleOutcome]:
+        rgl = [None if r < 0 else bool(r) for r in self.repair_given_location.tolist()]
+        return [SampleOutcome(*t) for t in zip(self.confidence.tolist(), self.has_bug.tolist(), self.warned.tolist(),
+                                               self.location_correct.tolist(), rgl, self.repaired.tolist(),
+                                               (self.scout_names[i] for i in self.scout.tolist()))]
+
+    def summary(self) -> Dict[str, float]:
+        count = lambda mask: int(np.count_nonzero(mask))
+        n = int(self.confidence.shape[0])
+        buggy = count(self.has_bug)
+        correct_code = n - buggy
+        warned_buggy = count(self.has_bug & self.warned)
+        silent_correct = count(~self.has_bug & ~self.warned)
+        repaired, located, repair_ok = count(self.repaired), count(self.location_correct), count(self.repair_given_location == 1)
+        div = lambda a, b: a / b if b else float("nan")
+        return {
+            "num_samples": n,
+            "num_buggy_samples": buggy,
+            "num_repaired_correct": repaired,
+            "num_location_correct": located,
+            "num_repaired_given_location_correct": repair_ok,
+            "num_detection_correct": warned_buggy + silent_correct,
+            "accuracy": div(repaired, n),
+            "bug_detection_accuracy": div(warned_buggy + silent_correct, n),
+            "bug_detection_false_negatives": 1 - div(warned_buggy, buggy),
+            "bug_detection_false_positives": 1 - div(silent_correct, correct_code),
+            "localization_accuracy": div(located, n),
+            "repair_accuracy_given_location": div(repair_ok, buggy),
+            "repair_accuracy": div(count(self.repaired & self.has_bug), buggy),
+            "bug_detection_recall": div(warned_buggy, buggy),
+            "no_bug_precision": div(silent_correct, correct_code),
+        }
+
+    def per_scout(self) -> Dict[str, Dict[str, List[int]]]:
+        k = len(self.scout_names)
+
+        def table(rows, ok):
+            total = np.bincount(self.scout[rows], minlength=k)
+            good = np.bincount(self.scout[rows & ok], minlength=k)
+            return {name: [int(good[i]), int(total[i])] for name, i in sorted((n, i) for i, n in enumerate(self.scout_names)) if total[i]}
+
+        everything = np.ones(self.scout.shape[0], dtype=bool)
+        return {"localization": table(everything, self.location_correct), "repair": table(self.has_bug, self.repair_given_location == 1)}
+
+    def curves(self) -> Dict[str, np.ndarray]:
+        # the descending stable sort of (confidence, has_bug, warned, location_correct, repair_given_location) the host path does
+        # on tuples; np.lexsort takes its LAST key first.  None only ever meets None there (has_bug is compared before it).
+        neg = lambda c: -c.astype(np.int8)
+        order = np.lexsort((neg(self.repair_given_location), neg(self.location_correct), neg(self.warned), neg(self.has_bug),
+                            -self.confidence))
+        return _curves_of_ranked(self.has_bug[order], self.warned[order], self.location_correct[order],
+                                 self.repair_given_location[order] == 1, self.confidence[order])
+
+
+def evaluate_on_device(model, nn, data: Iterable[Any], device, *, assume_buggy: bool = False, eval_only_no_bug: bool = False,
+                       parallelize: bool = True) -> ColumnarEvaluationReport:
+    """`evaluate_predictions(model.predict(data, nn, device, parallelize), ...)` without the per-sample host work: the
+    minibatches `predict` forms (same `tensorize`, same 50 samples), the same forward, and one hip_ops.eval_judge launch per
+    minibatch that writes the verdicts into outcome buffers kept on the device until the end (24 bytes per sample, one copy
+    back).  `has_bug` and the scout names never go to the device.  With `eval_only_no_bug` every sample still runs, as in
+    `predict`, so that a sequence model's minibatches -- and with them its fp32 values -- are those of the host path; the buggy
+    samples are left out of the report.  Single models only: an ensemble keeps the host path."""
+    from buglab.controllers import _batching as Bt
+    from buglab.models import _evaluate as E
+    from buglab.models import hip_ops
+
+    Bt.require_single_model(model, "evaluate_on_device")
+    device = torch.device(device)
+    names, ids = ["NoBug"], {"NoBug": 0}
+    has_bug: List[bool] = []
+    scout: List[int] = []
+
+    def extend(layout, points, dev, mb):
+        ix = E.eval_indices(layout, points, mb.get("node_mappings"))
+        if assume_buggy:
+            E.check_assume_buggy(ix)
+        targets = [p["target_fix_action_idx"] for p in points]
+        scouts = ["NoBug" if t is None else p["candidate_rewrite_metadata"][t][0] for p, t in zip(points, targets)]
+        return {"ix": dict(zip(hip_ops.EVAL_INDEX_FIELDS, Bt.to_device_i32([getattr(ix, f) for f in hip_ops.EVAL_INDEX_FIELDS], dev))),
+                "scouts": scouts}
+
+    def buffers(capacity):  # [confidence | the four verdict rows] in one allocation: one copy back
+        blob = torch.empty(3 * capacity, dtype=torch.float64, device=device)
+        return blob, blob[:capacity], blob[capacity:].view(torch.int32).view(4, capacity)
+
+    capacity = max(len(data), 1) if hasattr(data, "__len__") else 1 << 14
+    blob, conf, verdict = buffers(capacity)
+    n = 0
+    nn.eval()
+    with torch.no_grad(), model._tensorize_all_location_rewrites():
+        for mb, _tags in Bt.prediction_minibatches(model, ((d, None) for d in data), device, parallelize, extend, lambda tag: None,
+                                                   extend_sees_minibatch=True):
+            flat = Bt.flat_prediction_output(nn, mb)
+            B = len(mb["selfsup"]["scouts"])
+            if n + B > capacity:  # a stream of unknown length: double, on the device
+                capacity = max(2 * capacity, n + B)
+                _, new_conf, new_verdict = grown = buffers(capacity)
+                new_conf[:n].copy_(conf[:n]), new_verdict[:, :n].copy_(verdict[:, :n])
+                blob, conf, verdict = grown
+            hip_ops.eval_judge(flat, mb["selfsup"]["ix"], conf, verdict, n, assume_buggy=assume_buggy)
+            for name in mb["selfsup"]["scouts"]:
+                has_bug.append(name != "NoBug")
+                scout.append(ids.setdefault(name, len(ids)))
+                if scout[-1] == len(names):
+                    names.append(name)
+            n += B
+    host = blob.cpu()  # the one copy (and the one synchronisation) of the run
+    conf, verdict = host[:capacity][:n].numpy(), host[capacity:].view(torch.int32).view(4, capacity)[:, :n].numpy()
+    return ColumnarEvaluationReport(conf, has_bug, verdict[0] != 0, verdict[1] != 0, verdict[2], verdict[3] != 0, scout, names,
+                                    eval_only_no_bug)
+
+
+def report_to_json(report: EvaluationReport) -> str:
+    """summary, per-scout tables and curves as data (NaN where the text says NaN)."""
+    return json.dumps({"summary": report.summary(), "per_scout": report.per_scout(),
+                       "curves": {k: v.tolist() for k, v in report.curves().items()}}, indent=1, sort_keys=True) + "\n"
+
+
 def run(arguments):
     data_path = RichPath.create(arguments["TEST_DATA_PATH"])
     lim = None if arguments["--limit-num-elements"] is None else int(arguments["--limit-num-elements"])
@@ -219,9 +384,16 @@ def run(arguments):
         raise RuntimeError("evaluate.py: no ROCm GPU visible; the BugLab hot path has no CPU fallback")
     device = torch.device("cuda")
     model, nn = GnnBugLabModel.restore_model(Path(arguments["MODEL_FILENAME"]), device)
-    predictions = model.predict(data, nn, device, parallelize=not arguments["--sequential"])
-    report = evaluate_predictions(predictions, arguments["--assume-buggy"], arguments["--eval-only-no-bug"])
+    if arguments.get("--on-device"):
+        report = evaluate_on_device(model, nn, data, device, assume_buggy=arguments["--assume-buggy"],
+                                    eval_only_no_bug=arguments["--eval-only-no-bug"], parallelize=not arguments["--sequential"])
+    else:
+        predictions = model.predict(data, nn, device, parallelize=not arguments["--sequential"])
+        report = evaluate_predictions(predictions, arguments["--assume-buggy"], arguments["--eval-only-no-bug"])
     sys.stdout.write(report.format())
+    if arguments.get("--report-json") is not None:
+        with open(arguments["--report-json"], "w", encoding="utf-8") as f:
+            f.write(report_to_json(report))
     return report.summary()
 
 
@@ -233,10 +405,13 @@ if __name__ == "__main__":
     p.add_argument("--eval-only-no-bug", action="store_true")
     p.add_argument("--limit-num-elements", default=None)
     p.add_argument("--sequential", action="store_true")
+    p.add_argument("--on-device", action="store_true")
+    p.add_argument("--report-json", default=None)
     p.add_argument("--minibatch-size", default=300)
     p.add_argument("--restore-path", default=None)
     p.add_argument("--quiet", action="store_true")
     p.add_argument("--debug", action="store_true")
     ns = p.parse_args()
     run({"MODEL_FILENAME": ns.MODEL_FILENAME, "TEST_DATA_PATH": ns.TEST_DATA_PATH, "--assume-buggy": ns.assume_buggy,
-         "--eval-only-no-bug": ns.eval_only_no_bug, "--limit-num-elements": ns.limit_num_elements, "--sequential": ns.sequential})
+         "--eval-only-no-bug": ns.eval_only_no_bug, "--limit-num-elements": ns.limit_num_elements, "--sequential": ns.sequential,
+         "--on-device": ns.on_device, "--report-json": ns.report_json})

@@ -193,6 +193,8 @@ _SIGNATURES = {
                              c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p,
                              c_void_p], ctypes.c_int),
     "bl_report_order": ([c_void_p, c_void_p, c_int64, c_int64, c_int32, c_void_p, c_void_p, c_void_p], ctypes.c_int),
+    "bl_eval_judge": ([c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int32,
+                       c_int32, c_void_p, c_void_p, c_int64, c_int64, c_void_p], ctypes.c_int),
     "bl_dedup_sha1_u32": ([c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p], ctypes.c_int),
     "bl_dedup_minhash": ([c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int32, c_void_p, c_void_p], ctypes.c_int),
     "bl_dedup_lsh_insert_query": ([c_void_p, c_int32, c_int32, c_int32, c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p,

@@ -1,4 +1,5 @@
-"""Forward-only device services: ensemble combine, self-supervision scoring / sampling, bug reports, near-duplicate detection."""
+"""Forward-only device services: ensemble combine, self-supervision scoring / sampling, bug reports, evaluation, near-duplicate
+detection."""
 from __future__ import annotations
 
 from typing import Optional, Tuple
@@ -8,7 +9,8 @@ import torch
 from ._cabi import _check, _f32, _i32, load_library, _p, _req, _stream
 
 __all__ = ["ENSEMBLE_KINDS", "ENSEMBLE_MAX_MEMBERS", "ensemble_combine", "SELECTOR_MAX_K", "_f64", "score_targets",
-           "selector_sample", "REPORT_MAX_SAMPLES", "REPORT_INDEX_FIELDS", "report_summarize", "report_order", "DEDUP_MAX_PERM",
+           "selector_sample", "REPORT_MAX_SAMPLES", "REPORT_INDEX_FIELDS", "report_summarize", "report_order", "EVAL_INDEX_FIELDS", "eval_judge",
+           "DEDUP_MAX_PERM",
            "DEDUP_EMPTY_SLOT", "_i64", "dedup_sha1_u32", "dedup_minhash", "dedup_lsh_insert_query"]
 
 
@@ -128,6 +130,37 @@ def report_order(keys, keep, *, by_confidence: bool, k: int = 0) -> torch.Tensor
     _check(load_library().bl_report_order(keys.data_ptr(), keep.data_ptr(), n, int(k), int(bool(by_confidence)), out.data_ptr(),
                                           count.data_ptr(), _stream()), "bl_report_order")
     return out[:int(count.item())]
+
+
+# ------------------------------------------------------------------------------------------------
+# evaluation (csrc/bl_evaluate.hip; include/buglab_hip.h::bl_eval_judge)
+EVAL_INDEX_FIELDS = ("loc_idx", "loc_off", "key_node", "rw_idx", "rw_off", "rw_node", "tgt_rw")
+
+
+def eval_judge(src, ix, out_conf, out_verdict, offset: int, *, assume_buggy: bool = False) -> None:
+    """The verdicts of one predict minibatch of B samples from a model's flat fp32 output `src`, written to samples offset ..
+    offset + B - 1 of the run-long buffers out_conf (float64 [N]) and out_verdict (int32 [4, N] = warned | location_correct |
+    repair_given_location (-1 without a bug) | repaired).  `ix`: a mapping with the int32 tensors of EVAL_INDEX_FIELDS
+    (buglab/models/_evaluate.py::eval_indices).  No sync."""
+    _f32(src, "src"), _f64(out_conf, "out_conf"), _i32(out_verdict, "out_verdict")
+    t = {name: _i32(ix[name], name) for name in EVAL_INDEX_FIELDS}
+    B, total_loc, total_rw = t["tgt_rw"].shape[0], t["loc_idx"].shape[0], t["rw_idx"].shape[0]
+    sizes = {"loc_idx": total_loc, "loc_off": B + 1, "key_node": total_loc, "rw_idx": total_rw, "rw_off": B + 1, "rw_node": total_rw,
+             "tgt_rw": B}
+    bad = {name: tuple(t[name].shape) for name, n in sizes.items() if t[name].dim() != 1 or t[name].shape[0] != n}
+    if bad:
+        raise ValueError(f"eval_judge: inconsistent shapes (B {B}, total_loc {total_loc}, total_rw {total_rw}): {bad}")
+    N = out_conf.shape[0]
+    if out_conf.dim() != 1 or tuple(out_verdict.shape) != (4, N) or out_conf.device != src.device or out_verdict.device != src.device:
+        raise ValueError(f"eval_judge: out_conf {tuple(out_conf.shape)} must be [N] and out_verdict {tuple(out_verdict.shape)} [4, N], "
+                         f"both on {src.device}")
+    offset = int(offset)
+    if not 0 <= offset <= N - B:
+        raise ValueError(f"eval_judge: samples {offset} .. {offset + B} do not fit the outcome buffers of {N} samples")
+    p = lambda name: t[name].data_ptr()
+    _check(load_library().bl_eval_judge(src.data_ptr(), src.numel(), p("loc_idx"), p("loc_off"), p("key_node"), total_loc, p("rw_idx"),
+                                        p("rw_off"), p("rw_node"), total_rw, p("tgt_rw"), B, int(bool(assume_buggy)),
+                                        out_conf.data_ptr(), out_verdict.data_ptr(), offset, N, _stream()), "bl_eval_judge")
 
 
 # ------------------------------------------------------------------------------------------------

@@ -25,34 +25,11 @@
 //   comparisons, exact, no atomics.  Without by_confidence the rank is the number of kept samples in front: a compaction.
 // Plain vector loads and stores only; bit-identical from run to run.
 #include "bl_common.h"
+#include "bl_first_max.h"  // rp_load, rp_at, rp_better, rp_wave_argmax
 
 namespace {
 constexpr int RP_THREADS = 256;
 constexpr int RP_WAVES = RP_THREADS / BL_WAVE;
-
-__device__ __forceinline__ double rp_load(const float* src, int64_t n_src, int32_t j) {
-  // an index outside src (the host never sends one) reads as NaN instead of out of bounds
-  return (j >= 0 && (int64_t)j < n_src) ? (double)src[j] : __builtin_nan("");
-}
-
-__device__ __forceinline__ int32_t rp_at(const int32_t* a, int64_t n, int64_t i, int32_t otherwise) {
-  return (i >= 0 && i < n) ? a[i] : otherwise;
-}
-
-// Candidate (value, index) a replaces b in a first-maximum search: greater value, or the same value earlier.  NaNs never enter.
-__device__ __forceinline__ bool rp_better(double va, int ia, double vb, int ib) { return ib < 0 || va > vb || (va == vb && ia < ib); }
-
-__device__ __forceinline__ void rp_wave_argmax(double& v, int& i) {
-#pragma unroll
-  for (int o = BL_WAVE / 2; o > 0; o >>= 1) {
-    const double ov = __shfl_xor(v, o, BL_WAVE);
-    const int oi = __shfl_xor(i, o, BL_WAVE);
-    if (oi >= 0 && rp_better(ov, oi, v, i)) {
-      v = ov;
-      i = oi;
-    }
-  }
-}
 
 __global__ __launch_bounds__(RP_THREADS) void report_summarize_kernel(
     const float* __restrict__ src, int64_t n_src, const int32_t* __restrict__ loc_idx, const int32_t* __restrict__ loc_off,
