@@ -8,7 +8,13 @@
  *   - the CALLER owns every buffer (PyTorch-ROCm tensors -> data_ptr()); nothing here allocates;
  *   - all index arrays are int32, all values float32, matrices row-major with an explicit
  *     leading dimension where one is given; pointers must be 16-byte aligned and every leading
- *     dimension / width a multiple of 4 floats;
+ *     dimension / width a multiple of 4 floats -- except where an entry point says "any width": bl_segment_max_fwd,
+ *     bl_mp_scatter_grad / _split and bl_gru_cell_fwd / _bwd address their rows element by element and take any width
+ *     and any leading dimension >= the width, with pointers that need only be 4-byte aligned (the heads run the segmented
+ *     max over [*, 1] columns); bl_segment_max_bwd is NOT one of them, see there;
+ *   - no entry point writes outside [rows, width] of an output or outside the bytes its *_bytes / *_elems function reports,
+ *     and nothing outside an input's [rows, width] (the columns width .. ld, the rows around it) influences a result
+ *     (tests/test_abi_strides_gpu.py);
  *   - the last argument is the hipStream_t to launch on
  *     (torch.cuda.current_stream().cuda_stream); entry points never synchronise.
  *
@@ -273,6 +279,7 @@ int bl_gemm_wgrad_routed(const bl_rows_t* a, const float* g_node, int32_t ld_g, 
  *   words per item: the routing table in the form the bf16x6 routed GEMMs read;
  *   seg_order (optional): a permutation of 0..nseg-1 = the order segments are processed in (the collator puts
  *   high-degree nodes first: one wave works through a 512-item hub for about as long as the whole launch takes).
+ * Any width: D in 1..512 and ldx >= D need not be multiples of 4 (out, arg, dact are [nseg, D] without padding).
  * Replaces torch_scatter.scatter_max at ptgnn's "max" aggregation (gnnlayerdefs.py:11,21) and at
  * buglab/models/layers/localizationmodule.py:56-58, plus ptgnn's nn.LayerNorm. */
 int bl_segment_max_fwd(const float* x, int32_t ldx, const int32_t* seg_ptr, const int32_t* seg_items, int32_t nseg,
@@ -281,7 +288,9 @@ int bl_segment_max_fwd(const float* x, int32_t ldx, const int32_t* seg_ptr, cons
                        const int32_t* seg_order, void* stream);
 
 /* backward of the segmented max, gather form (deterministic, no atomics):
- *   g_x[i, d] = (arg[seg_of[i], d] == i) ? g_out[seg_of[i], d] * act'(x[i, d]) : 0      (g_x may alias x) */
+ *   g_x[i, d] = (arg[seg_of[i], d] == i) ? g_out[seg_of[i], d] * act'(x[i, d]) : 0      (g_x may alias x)
+ * Unlike bl_segment_max_fwd this one moves float4s: D and ldx (shared by x and g_x) must be multiples of 4 and g_out, x and
+ * g_x 16-byte aligned -- a forward call at an odd width has no backward call here. */
 int bl_segment_max_bwd(const float* g_out, const int32_t* arg, const float* x, int32_t ldx, const int32_t* seg_of,
                        int32_t nitems, int32_t D, int32_t act, float* g_x, void* stream);
 
@@ -315,7 +324,8 @@ int bl_act_bwd_packed(const float* g_y, const float* y, int32_t nrows, int32_t N
 /* M1 backward, last step: gradient w.r.t. node states from the per-message input gradients
  *   g_h[n, 0:Din] (+)= sum_{e in src CSR of n} g_a[e, 0:Din] + sum_{e in tgt CSR of n} g_a[e, Din:2Din]
  * (deterministic segmented sums; replaces autograd's index_add of the two h[...] gathers).
- * tgt_ptr == tgt_msgs == NULL: source half only (messages built from h[src] alone, `ggnn`). */
+ * tgt_ptr == tgt_msgs == NULL: source half only (messages built from h[src] alone, `ggnn`).
+ * Any width: Din in 1..512; ld_ga >= 2 Din (Din without the target half) and ld_gh >= Din need not be multiples of 4. */
 int bl_mp_scatter_grad(const float* g_a, int32_t ld_ga, const int32_t* src_ptr, const int32_t* src_msgs,
                        const int32_t* tgt_ptr, const int32_t* tgt_msgs, int32_t N, int32_t Din, int32_t accumulate,
                        float* g_h, int32_t ld_gh, const int32_t* node_order,
@@ -361,7 +371,8 @@ int bl_routed_dgrad_nodes_rows(const float* gq, int32_t ld_gq, const int32_t* ms
  * r | z | n) after gi = x W_i + b_i and gh = h W_h + b_h [N, 3D] were produced by bl_gemm_rows:
  *   h' = drop((1 - z) * tanh(gi_n + r * gh_n) + z * h).  Replaces ptgnn GatedMessagePassingLayer's
  * nn.GRUCell state update (reference call site buglab/models/gnnlayerdefs.py:42-68).
- * bwd writes g_gi, g_gh [N, 3D] and the direct part of g_h (z * g_out) [N, D]. */
+ * bwd writes g_gi, g_gh [N, 3D] and the direct part of g_h (z * g_out) [N, D].  Any width: D and ld_h >= D need not be
+ * multiples of 4; gi, gh, out and the gradients are contiguous. */
 int bl_gru_cell_fwd(const float* gi, const float* gh, const float* h, int32_t ld_h, int32_t N, int32_t D,
                     bl_dropout_t drop, float* out, void* stream);
 int bl_gru_cell_bwd(const float* g_out, const float* gi, const float* gh, const float* h, int32_t ld_h, int32_t N,

@@ -1002,6 +1002,7 @@ int bl_segment_max_fwd_impl(const float* x, int32_t ldx, const int32_t* seg_ptr,
   // arg (the winner table) is optional; so are out / mean / rstd when only the LayerNorm output is wanted (forward-only calls)
   BL_CHECK_ARG(seg_ptr && (out || ln_g), "bl_segment_max_fwd: null pointer");
   BL_CHECK_ARG(D > 0 && D <= 512, "bl_segment_max_fwd: D must be in 1..512 (got %d)", D);
+  BL_CHECK_ARG(ldx >= D, "bl_segment_max_fwd: ldx (%d) must be >= D (%d)", ldx, D);  // (scalar loads: any D / ldx, the heads pass D = 1)
   BL_CHECK_ARG(act == BL_ACT_NONE || act == BL_ACT_GELU || act == BL_ACT_GELU_AGG, "bl_segment_max_fwd: act must be NONE, GELU or GELU_AGG");
   const bool has_ln = ln_g != nullptr;
   BL_CHECK_ARG(!has_ln || (ln_b && (ln_out || ln_out_packed) && (mean == nullptr) == (rstd == nullptr)), "bl_segment_max_fwd: LayerNorm outputs missing");
@@ -1162,6 +1163,7 @@ extern "C" int bl_mp_scatter_grad(const float* g_a, int32_t ld_ga, const int32_t
   if (N == 0) return BL_OK;
   BL_CHECK_ARG(g_a && src_ptr && src_msgs && g_h && (tgt_ptr == nullptr) == (tgt_msgs == nullptr), "bl_mp_scatter_grad: null pointer");
   BL_CHECK_ARG(Din > 0 && Din <= 512 && ld_ga >= (tgt_ptr ? 2 : 1) * Din, "bl_mp_scatter_grad: Din in 1..512, ld_ga >= (1 or 2)*Din");
+  BL_CHECK_ARG(ld_gh >= Din, "bl_mp_scatter_grad: ld_gh (%d) must be >= Din (%d)", ld_gh, Din);
   return mp_scatter_launch("bl_mp_scatter_grad", g_a, ld_ga, src_ptr, src_msgs, tgt_ptr, tgt_msgs, N, Din, accumulate, g_h, ld_gh, node_order,
                            Din, nullptr, 0, 0, stream);
 }
@@ -1207,6 +1209,7 @@ extern "C" int bl_gru_cell_fwd(const float* gi, const float* gh, const float* h,
                                bl_dropout_t drop, float* out, void* stream) {
   if (N == 0) return BL_OK;
   BL_CHECK_ARG(gi && gh && h && out && D > 0, "bl_gru_cell_fwd: null pointer");
+  BL_CHECK_ARG(ld_h >= D, "bl_gru_cell_fwd: ld_h (%d) must be >= D (%d)", ld_h, D);
   const long long total = (long long)N * D;
   hipLaunchKernelGGL(gru_cell_fwd_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, gi, gh, h,
                      ld_h, (long long)N, D, bl_make_drop(drop), out);
@@ -1219,6 +1222,7 @@ extern "C" int bl_gru_cell_bwd(const float* g_out, const float* gi, const float*
                                void* stream) {
   if (N == 0) return BL_OK;
   BL_CHECK_ARG(g_out && gi && gh && h && g_gi && g_gh && g_h && D > 0, "bl_gru_cell_bwd: null pointer");
+  BL_CHECK_ARG(ld_h >= D, "bl_gru_cell_bwd: ld_h (%d) must be >= D (%d)", ld_h, D);
   const long long total = (long long)N * D;
   hipLaunchKernelGGL(gru_cell_bwd_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, g_out, gi,
                      gh, h, ld_h, (long long)N, D, bl_make_drop(drop), g_gi, g_gh, g_h);
