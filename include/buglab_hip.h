@@ -670,6 +670,24 @@ int bl_varmisuse_head_fwd(const bl_varmisuse_head_t* d, float* logits, float* me
 int bl_varmisuse_head_bwd(const bl_varmisuse_head_t* d, const float* logits, const float* mean, const float* rstd, const float* lse,
                           const float* loss, const float* g_loss, void* workspace, float* g_x, float* g_W, float* g_bias,
                           float* g_ln_g, float* g_ln_b, void* stream);
+/* The head forward-only, every sample judged on the device: the inference counterpart of greatreimplementation.py:176-214 (the
+ * reference has no predict), in csrc/bl_varmisuse_predict.hip.  Same descriptor; error_location and target_mask are always given
+ * (zeros for unlabelled data).  Reads or writes no mean / rstd, workspace, loss or stats; no synchronisation.
+ * logits [B * L, 2]: the masked logits of bl_varmisuse_head_fwd for the same inputs, bit for bit.  Sample b's record goes to
+ * sample offset + b of buffers the caller keeps for the whole run (capacity samples; offset + B <= capacity), with
+ * la = lens_att[b] clamped to [0, L], "candidates" = positions i < la with candidate_mask set, and log-probability =
+ * double(logit) - lse:
+ *   out_d [7, capacity] (double)  0 localization log-sum-exp over i < la | 1 pointer log-sum-exp over the candidates (-inf without
+ *       one) | 2 log-probability of the predicted location | 3 of position 0 ("no bug") | 4 of error_location[b] (-inf outside
+ *       [0, la)) | 5 pointer log-probability of the predicted repair (NaN without a candidate) | 6 log-sum-exp of the pointer
+ *       log-probabilities over candidates that are targets, the repair log-probability of :161 (-inf without one);
+ *   out_i [4, capacity] (int32)   0 predicted location | 1 predicted repair position (-1 without a candidate) | 2 predicted
+ *       location == error_location[b] | 3 target_mask at the predicted repair (0 without one).
+ * Predictions are first maxima of the fp32 logits (lower index on a tie, as torch.argmax; a NaN never wins).  Each log-sum-exp is
+ * max + log(sum exp(double(v) - double(max))) in fp64, summed in a fixed order: results are bit-identical from run to run.
+ * BL_EINVAL: null pointers, negative sizes, offset + B > capacity, D not a multiple of 4 or above 1024. */
+int bl_varmisuse_predict(const bl_varmisuse_head_t* d, float* logits, double* out_d, int32_t* out_i, int64_t offset, int64_t capacity,
+                         void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Ensemble combine (buglab/models/ensemble/wrapper.py:33-89: `EnsembleWrapper.predict`'s avg / consensus and

@@ -78,6 +78,11 @@ class EnsembleWrapper:
             raise ValueError("An ensemble needs at least one member.")
         if not all(hasattr(m, "predict") for m in models):
             raise ValueError("One of the models doesn't have a predict function.")  # reference :26 (an assert there)
+        from buglab.models.greatreimplementation import GreatVarMisuse
+
+        if any(isinstance(m, GreatVarMisuse) for m in models):  # its predict yields a VarMisusePrediction per record
+            raise ValueError("The GREAT var-misuse model's predict does not yield the location / rewrite log-probabilities an "
+                             "ensemble combines.")
         if kind not in ("avg", "consensus"):
             raise ValueError(f"Unrecognized ensemble kind `{kind}`: expected `avg` or `consensus`.")
         if len(models) > hip_ops.ENSEMBLE_MAX_MEMBERS:

@@ -184,6 +184,7 @@ _SIGNATURES = {
                               ctypes.c_int),
     "bl_varmisuse_head_bwd": ([POINTER(bl_varmisuse_head_t), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                               c_void_p, c_void_p, c_void_p, c_void_p, c_void_p], ctypes.c_int),
+    "bl_varmisuse_predict": ([POINTER(bl_varmisuse_head_t), c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p], ctypes.c_int),
     "bl_ensemble_combine": ([c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int32, c_int32, c_int32, c_void_p,
                              c_void_p, c_void_p], ctypes.c_int),
     "bl_score_targets": ([c_void_p, c_int64, c_void_p, c_void_p, c_int32, c_void_p, c_void_p], ctypes.c_int),

@@ -14,7 +14,8 @@ from .gemm import segment_max, segment_max_bwd
 
 __all__ = ["_SegmentLogSoftmax", "segment_log_softmax", "_SegmentMaxPool", "segment_max_pool", "_MlpScore", "mlp_score",
            "_LocalizationScores", "localization_scores", "BUG_LOSS_STATS", "BugLossIndex", "_bug_loss_desc", "_BugLoss",
-           "bug_loss", "_byte_mask", "_varmisuse_desc", "_varmisuse_workspace", "_VarMisuseHead", "varmisuse_head"]
+           "bug_loss", "_byte_mask", "_varmisuse_desc", "_varmisuse_workspace", "_VarMisuseHead", "varmisuse_head",
+           "VARMISUSE_RECORD_D", "VARMISUSE_RECORD_I", "varmisuse_predict"]
 
 
 class _SegmentLogSoftmax(torch.autograd.Function):
@@ -323,3 +324,37 @@ def varmisuse_head(x, ln_g, ln_b, W, bias, lens_att, error_location, candidate_m
     -> (loss scalar, logits [B * L, 2], number of buggy samples as a device scalar); nothing is read back to the host."""
     return _VarMisuseHead.apply(x.contiguous(), ln_g, ln_b, W.contiguous(), bias, lens_att.contiguous(), error_location.contiguous(),
                                 candidate_mask.reshape(-1).contiguous(), target_mask.reshape(-1).contiguous(), stats, float(eps))
+
+
+VARMISUSE_RECORD_D, VARMISUSE_RECORD_I = 7, 4  # rows of a sample's fp64 / int32 prediction record (include/buglab_hip.h)
+
+
+def varmisuse_predict(x, ln_g, ln_b, W, bias, lens_att, error_locations, candidate_mask, target_mask, out_d, out_i, offset: int,
+                      eps: float = 1e-5):
+    """The head forward-only (csrc/bl_varmisuse_predict.hip): the masked logits of `varmisuse_head` for the same tensors, bit for
+    bit, and every sample judged on the device.  Sample b's record is written at sample offset + b of the run-long buffers
+    out_d (float64 [VARMISUSE_RECORD_D, N]: localization lse | pointer lse | log-probabilities of the predicted location, of
+    position 0, of the error location, of the predicted repair | repair log-probability over the targets) and out_i (int32
+    [VARMISUSE_RECORD_I, N]: predicted location | predicted repair, -1 without a candidate | location correct | repair is a
+    target); see include/buglab_hip.h.  error_locations / target_mask: zeros for unlabelled data.  No autograd, no sync.
+    -> logits [B * L, 2]."""
+    x, W = x.detach(), W.detach()
+    if not x.is_contiguous() or not W.is_contiguous():
+        raise ValueError("varmisuse_predict: x and W must be contiguous")
+    d = _varmisuse_desc(x, ln_g.detach(), ln_b.detach(), W, bias.detach(), lens_att, error_locations, candidate_mask.reshape(-1),
+                        target_mask.reshape(-1), eps)
+    if d.D % 4 != 0 or d.D > 1024:
+        raise ValueError(f"varmisuse_predict: unsupported shape B={d.B} L={d.L} D={d.D} (D: a multiple of 4, at most 1024)")
+    _req(out_d, torch.float64, "out_d"), _i32(out_i, "out_i")
+    N = out_d.shape[-1]
+    if tuple(out_d.shape) != (VARMISUSE_RECORD_D, N) or tuple(out_i.shape) != (VARMISUSE_RECORD_I, N) or out_d.device != x.device \
+            or out_i.device != x.device:
+        raise ValueError(f"varmisuse_predict: out_d {tuple(out_d.shape)} must be [{VARMISUSE_RECORD_D}, N] and out_i "
+                         f"{tuple(out_i.shape)} [{VARMISUSE_RECORD_I}, N], both on {x.device}")
+    offset = int(offset)
+    if not 0 <= offset <= N - d.B:
+        raise ValueError(f"varmisuse_predict: samples {offset} .. {offset + d.B} do not fit the record buffers of {N} samples")
+    logits = torch.empty((x.shape[0], 2), dtype=torch.float32, device=x.device)
+    _check(load_library().bl_varmisuse_predict(ctypes.byref(d), logits.data_ptr(), out_d.data_ptr(), out_i.data_ptr(), offset, N,
+                                               _stream()), "bl_varmisuse_predict")
+    return logits

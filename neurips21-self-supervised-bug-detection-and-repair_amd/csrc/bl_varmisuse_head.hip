@@ -19,21 +19,17 @@
 //   vm_bwd_reduce   the partials summed in workgroup order.
 // Every sum runs in a fixed order, so results are bit-identical from run to run whatever bl_get_deterministic() says.
 #include "bl_common.h"
+#include "bl_varmisuse_rows.h"  // vm_row_logits, vm_masked_logits, block_argmax, vm_check (shared with bl_varmisuse_predict.hip)
 
 namespace {
-constexpr int VM_ROW_THREADS = 256;     // forward rows: 4 waves, one row each
-constexpr int VM_SAMPLE_THREADS = 256;  // one workgroup per sample
-constexpr int VM_SAMPLE_WAVES = VM_SAMPLE_THREADS / 64;
 constexpr int VM_BWD_THREADS = 512;     // backward rows: 8 waves
 constexpr int VM_BWD_WAVES = VM_BWD_THREADS / 64;
 constexpr int VM_BWD_MAX_BLOCKS = 512;
 constexpr int VM_RED_THREADS = 1024;    // partial reduction: 16 waves x 64 columns
 constexpr int VM_RED_WAVES = VM_RED_THREADS / 64;
-constexpr int VM_MAX_D = 1024;
 constexpr int VM_PS = 8;                // per-sample slots in the workspace
 constexpr int VM_COUNTER_BYTES = 16;    // ticket counter at the front of the workspace
 enum { PS_LOC_LOSS = 0, PS_REP_LOSS, PS_LOC_HIT, PS_REP_HIT, PS_BUGGY };
-#define VM_NEG_INF (-__builtin_huge_valf())
 
 inline int vm_bwd_blocks(int64_t nrows) {
   const int64_t w = (nrows + VM_BWD_WAVES - 1) / VM_BWD_WAVES;
@@ -41,41 +37,6 @@ inline int vm_bwd_blocks(int64_t nrows) {
 }
 // partial row of one backward workgroup: [g_W (2 D, interleaved as W) | g_ln_g (D) | g_ln_b (D) | g_bias (2) | pad (2)]
 __host__ __device__ inline int vm_partial_cols(int D) { return 4 * D + 4; }
-
-__device__ __forceinline__ float4 f4(float a) { return make_float4(a, a, a, a); }
-__device__ __forceinline__ float hsum(const float4& v) { return (v.x + v.y) + (v.z + v.w); }
-
-// (value, index) arg-max across a wave: larger value wins, a tie goes to the smaller index (torch.argmax's first index)
-__device__ __forceinline__ void wave_argmax(float& v, int& i) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float ov = __shfl_xor(v, o, 64);
-    const int oi = __shfl_xor(i, o, 64);
-    if (ov > v || (ov == v && oi < i)) {
-      v = ov;
-      i = oi;
-    }
-  }
-}
-
-// the same over the workgroup, combined in wave order; every thread gets the result
-__device__ __forceinline__ void block_argmax(float& v, int& i, float* sv, int* si) {
-  wave_argmax(v, i);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (lane == 0) {
-    sv[wave] = v;
-    si[wave] = i;
-  }
-  __syncthreads();
-  v = sv[0];
-  i = si[0];
-  for (int w = 1; w < VM_SAMPLE_WAVES; ++w)
-    if (sv[w] > v || (sv[w] == v && si[w] < i)) {
-      v = sv[w];
-      i = si[w];
-    }
-  __syncthreads();
-}
 
 __device__ __forceinline__ float block_sum(float s, float* sv) {
   s = bl_wave_sum(s);
@@ -99,50 +60,10 @@ __global__ __launch_bounds__(VM_ROW_THREADS) void vm_fwd_rows(bl_varmisuse_head_
   const int64_t row = (int64_t)blockIdx.x * (VM_ROW_THREADS / 64) + (threadIdx.x >> 6);
   const int64_t nrows = (int64_t)d.B * d.L;
   if (row >= nrows) return;  // (whole wave)
-  const int D = d.D, D4 = D >> 2;
-  const float4* xr = reinterpret_cast<const float4*>(d.x + row * D);
-  float4 v[NK];
-  float s = 0.f;
-#pragma unroll
-  for (int k = 0; k < NK; ++k) {
-    const int j = lane + 64 * k;
-    v[k] = j < D4 ? xr[j] : f4(0.f);
-    s += hsum(v[k]);
-  }
-  const float mu = bl_wave_sum(s) / (float)D;
-  float q = 0.f;
-#pragma unroll
-  for (int k = 0; k < NK; ++k) {
-    if (lane + 64 * k < D4) {
-      const float4 c = make_float4(v[k].x - mu, v[k].y - mu, v[k].z - mu, v[k].w - mu);
-      q += (c.x * c.x + c.y * c.y) + (c.z * c.z + c.w * c.w);
-    }
-  }
-  const float rs = 1.0f / sqrtf(bl_wave_sum(q) / (float)D + d.ln_eps);
-  const float4* g4 = reinterpret_cast<const float4*>(d.ln_g);
-  const float4* b4 = reinterpret_cast<const float4*>(d.ln_b);
-  const float4* w4 = reinterpret_cast<const float4*>(d.W);  // W [D, 2]: float4 2j = rows 4j, 4j+1; 2j+1 = rows 4j+2, 4j+3
-  float a0 = 0.f, a1 = 0.f;
-#pragma unroll
-  for (int k = 0; k < NK; ++k) {
-    const int j = lane + 64 * k;
-    if (j < D4) {
-      const float4 g = g4[j], bb = b4[j], wa = w4[2 * j], wb = w4[2 * j + 1];
-      const float y0 = (v[k].x - mu) * rs * g.x + bb.x, y1 = (v[k].y - mu) * rs * g.y + bb.y;
-      const float y2 = (v[k].z - mu) * rs * g.z + bb.z, y3 = (v[k].w - mu) * rs * g.w + bb.w;
-      a0 += (y0 * wa.x + y1 * wa.z) + (y2 * wb.x + y3 * wb.z);
-      a1 += (y0 * wa.y + y1 * wa.w) + (y2 * wb.y + y3 * wb.w);
-    }
-  }
-  a0 = bl_wave_sum(a0);
-  a1 = bl_wave_sum(a1);
+  float mu, rs, a0, a1;
+  vm_row_logits<NK>(d, row, lane, mu, rs, a0, a1);
   if (lane == 0) {
-    const int b = (int)(row / d.L), i = (int)(row - (int64_t)b * d.L);
-    // token mask `arange(L) > length` (greatreimplementation.py:198, :203): the caller passes lens_att = min(length + 1, L)
-    const bool valid = i < d.lens_att[b];
-    const float l0 = valid ? a0 + d.bias[0] : VM_NEG_INF;
-    const float l1 = (valid && d.candidate_mask[row]) ? a1 + d.bias[1] : VM_NEG_INF;  // :211
-    reinterpret_cast<float2*>(logits)[row] = make_float2(l0, l1);
+    reinterpret_cast<float2*>(logits)[row] = vm_masked_logits(d, row, a0, a1);
     mean_out[row] = mu;
     rstd_out[row] = rs;
   }
@@ -381,18 +302,6 @@ __global__ __launch_bounds__(VM_RED_THREADS) void vm_bwd_reduce(const float* __r
   else g_bias[col - 4 * D] = t;
 }
 
-int vm_check(const bl_varmisuse_head_t* d, const char* who) {
-  BL_CHECK_ARG(d != nullptr, "%s: null descriptor", who);
-  BL_CHECK_ARG(d->B >= 1 && d->L >= 1, "%s: B (%d) and L (%d) must be >= 1", who, d->B, d->L);
-  BL_CHECK_ARG((int64_t)d->B * d->L <= 0x7fffffff, "%s: B * L (%lld) exceeds int32", who, (long long)d->B * d->L);
-  BL_CHECK_ARG(d->D >= 4 && d->D <= VM_MAX_D && d->D % 4 == 0, "%s: D (%d) must be a multiple of 4 in [4, %d]", who, d->D, VM_MAX_D);
-  BL_CHECK_ARG(d->ln_eps > 0.f, "%s: ln_eps must be positive", who);
-  BL_CHECK_ARG(d->x && d->ln_g && d->ln_b && d->W && d->bias && d->lens_att && d->error_location && d->candidate_mask && d->target_mask,
-               "%s: null input pointer", who);
-  BL_CHECK_ARG(bl_aligned16(d->x) && bl_aligned16(d->ln_g) && bl_aligned16(d->ln_b) && bl_aligned16(d->W),
-               "%s: x, ln_g, ln_b and W must be 16-byte aligned", who);
-  return BL_OK;
-}
 }  // namespace
 
 extern "C" int64_t bl_varmisuse_head_workspace_bytes(int32_t B, int32_t L, int32_t D) {
