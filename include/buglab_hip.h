@@ -528,6 +528,19 @@ double bl_prof_read_bytes(int32_t kind); /* algorithmic bytes recorded with a me
  * Returns the previous mode.  bl_mp_layer_weight_image returns 2 (f16x3 image) in modes 1 and 2. */
 int32_t bl_set_msg_gemm_mode(int32_t mode);
 int32_t bl_get_msg_gemm_mode(void);
+/* Operand split of the packed-row GEMMs behind the sequence models' Linear layers -- bl_gemm_rows_x6, bl_gemm_rows_x6_epi,
+ * bl_gemm_rows_x6_epi2, bl_gemm_rows_x6w and bl_gemm_wgrad_x6, op by op and inside bl_great_layer_fwd / _bwd:
+ *   0  bf16x6 (default): three bf16 planes per operand, six MFMA terms, fp32-equivalent;
+ *   1  bf16x1: the same packed images, HIGH PLANES ONLY -- the other two are neither loaded nor staged -- one bf16 MFMA term per
+ *      16 k's, fp32 accumulation, every epilogue unchanged (a packed result stays a full three-plane image).  The reduced-precision
+ *      mode behind the reference's `train.py --amp` (reference buglab/models/train.py:8,106: autocast) for seq-great, seq-rat,
+ *      seq-transformer and seq-gru's input projections; attention products, LayerNorm, heads, losses, the GRU recurrence and the
+ *      optimiser stay fp32.  Never the default and never the benchmarked headline.
+ * BL_SEQ_GEMM=x1 / bf16x1 / amp in the environment sets the initial value.  bl_set_seq_gemm_mode returns the previous mode, or
+ * BL_EINVAL for any other value (the mode is then unchanged).  bl_great_layer_fwd records the mode its `saved` was written in (a host-side
+ * table keyed by the pointer: nothing is read back from the device); bl_great_layer_bwd returns BL_EINVAL when the current mode differs.  bl_gemm_wgrad_routed_x6 (a message GEMM) does not follow this switch. */
+int32_t bl_set_seq_gemm_mode(int32_t mode);
+int32_t bl_seq_gemm_mode(void);
 /* packing threads that had to saturate a finite value at +-65504 since the last reset, on the current device (synchronises; -1 if
  * the counter is unavailable): 0 in a healthy run -- the trainer checks it once per epoch (runtime/trainer.py). */
 int64_t bl_h3_saturation_events(int32_t reset);

@@ -2,11 +2,34 @@
 gradient is accumulated."""
 from __future__ import annotations
 
+import contextlib
+
 import torch
 
+from ._cabi import load_library
 from ._streams import _direct_small
 
-__all__ = ["_take_saved", "_grad_target"]
+__all__ = ["_take_saved", "_grad_target", "_seq_gemm_mode_code", "_in_seq_gemm_mode"]
+
+
+def _seq_gemm_mode_code() -> int:
+    """bl_seq_gemm_mode() now: what a Function's forward keeps for its backward."""
+    return int(load_library().bl_seq_gemm_mode())
+
+
+@contextlib.contextmanager
+def _in_seq_gemm_mode(code: int):
+    """Run a Function's backward in the sequence GEMM mode its forward ran in: the saved packed activations and the gradients
+    belong to one arithmetic, so a set_seq_gemm_mode between the two passes changes nothing for graphs already built."""
+    lib = load_library()
+    now = int(lib.bl_seq_gemm_mode())
+    if now != code:
+        lib.bl_set_seq_gemm_mode(code)
+    try:
+        yield
+    finally:
+        if now != code:
+            lib.bl_set_seq_gemm_mode(now)
 
 
 def _take_saved(ctx):

@@ -250,6 +250,8 @@ _SIGNATURES = {
                           c_int32, c_float, c_void_p, c_void_p, c_int64, c_int32, c_void_p], ctypes.c_int),
     "bl_set_msg_gemm_mode": ([c_int32], c_int32),
     "bl_get_msg_gemm_mode": ([], c_int32),
+    "bl_set_seq_gemm_mode": ([c_int32], c_int32),
+    "bl_seq_gemm_mode": ([], c_int32),
     "bl_calib_mfma_bf16": ([c_int32, c_int32, c_void_p, POINTER(ctypes.c_double), c_void_p], ctypes.c_int),
     "bl_calib_stream_copy": ([c_void_p, c_void_p, c_int64, c_void_p], ctypes.c_int),
     "bl_prof_enable": ([c_int32], ctypes.c_int),

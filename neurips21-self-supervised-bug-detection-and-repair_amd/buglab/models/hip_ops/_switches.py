@@ -20,6 +20,10 @@ WINNER_SINK: Optional[list] = None
 GEMM_MODE = os.environ.get("BL_GEMM_MODE", "bf16x6")  # "bf16x6" | "fp32"
 WGRAD_X6 = os.environ.get("BL_WGRAD_X6", "1") != "0"   # bf16x6 weight gradient of the message layers
 
+# Operand splits of the sequence models' projection GEMMs, in the order of bl_set_seq_gemm_mode's codes (the mode itself lives in
+# the library: hip_ops.set_seq_gemm_mode / seq_gemm_mode in runtime.py; BL_SEQ_GEMM=bf16x1 sets the initial value there)
+_SEQ_GEMM_MODES = ("bf16x6", "bf16x1")
+
 # One C call per message-passing layer and direction (bl_mp_layer_fwd / bl_mp_layer_bwd).
 FUSED_LAYER = os.environ.get("BL_FUSED_LAYER", "1") != "0"
 

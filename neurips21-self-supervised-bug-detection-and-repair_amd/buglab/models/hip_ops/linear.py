@@ -8,7 +8,7 @@ import torch
 from . import _switches
 from ._cabi import (ACT_NONE, ACT_RELU, ACT_SIGMOID, ACT_TANH, _ACTS, _check, Dropout, _f32, _i32, load_library, NO_DROPOUT, _p,
                     RowSource, _stream)
-from ._autograd import _grad_target, _take_saved
+from ._autograd import _grad_target, _in_seq_gemm_mode, _seq_gemm_mode_code, _take_saved
 from .gemm import act_bwd, gemm_rows, gemm_rows_x6, gemm_wgrad, gemm_wgrad_x6, pack_bf16x3, scatter_add_rows
 from .weights import _packed_layer_weights
 
@@ -74,6 +74,7 @@ class _GatherLinear(torch.autograd.Function):
             # ~1 GiB per seq-great step until the device was full)
             ctx.save_for_backward(out)
             ctx.saved = (W, bias, act, sources, drop, xp if need_bwd else None, wnk)
+            ctx.seq_mode = _seq_gemm_mode_code()
             return out
         out = gemm_rows(sources, _f32(W, "W"), R, W.shape[1], bias=bias, act=act, drop=drop)
         ctx.save_for_backward(out)
@@ -94,8 +95,9 @@ class _GatherLinear(torch.autograd.Function):
         g_bias, r_bias = _grad_target(bias_p) if has_bias else (None, None)
         if xp is not None:  # bf16x6 path
             gzp = act_bwd_packed(g_out.contiguous(), out, act, drop, g_bias)
-            gemm_wgrad_x6([(xp, None, K)], gzp, R, N, g_W)
-            g_x = gemm_rows_x6([(gzp, None, N)], wnk, R, K, kind="linear_dgrad_x6") if ctx.needs_input_grad[4] else None
+            with _in_seq_gemm_mode(ctx.seq_mode):
+                gemm_wgrad_x6([(xp, None, K)], gzp, R, N, g_W)
+                g_x = gemm_rows_x6([(gzp, None, N)], wnk, R, K, kind="linear_dgrad_x6") if ctx.needs_input_grad[4] else None
             return (r_W, r_bias, None, None, g_x, None) + ((None,) if drop is not NO_DROPOUT else ())
         g_z = act_bwd(g_out.contiguous(), out, act, drop, g_bias)
         gemm_wgrad(sources, g_z, R, N, g_W)

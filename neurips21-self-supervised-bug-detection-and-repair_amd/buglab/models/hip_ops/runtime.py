@@ -3,9 +3,10 @@ from __future__ import annotations
 
 import os
 
+from . import _switches
 from ._cabi import load_library
 
-__all__ = ["set_deterministic", "_MSG_GEMM_MODES", "set_msg_gemm_mode", "msg_gemm_mode", "set_wgrad_tile",
+__all__ = ["set_deterministic", "_MSG_GEMM_MODES", "set_msg_gemm_mode", "msg_gemm_mode", "set_seq_gemm_mode", "seq_gemm_mode", "set_wgrad_tile",
            "set_wgrad_kchunk_cap", "set_fused_node_bwd", "deterministic"]
 
 
@@ -34,6 +35,24 @@ def set_msg_gemm_mode(mode: str) -> str:
 
 def msg_gemm_mode() -> str:
     return _MSG_GEMM_MODES[load_library().bl_get_msg_gemm_mode()]
+
+
+def set_seq_gemm_mode(mode: str) -> str:
+    """'bf16x6' (default) or 'bf16x1': the operand split of the packed-row GEMMs behind the sequence models' Linear layers (QKV,
+    output, linear1 / linear2 and seq-gru's input projections; forward, input gradient, weight gradient; op by op and inside the
+    one-call GREAT layer -- bl_set_seq_gemm_mode).  'bf16x1' is the reduced-precision mode of `train.py --amp` for those models
+    (reference train.py:8,106: autocast): the bf16x3 images with the high planes only -- bf16 operands, fp32 accumulation, fp32
+    results; attention, LayerNorm, heads, losses and the optimiser stay fp32.  Outside the 1e-4 parity bound by construction and
+    never the benchmarked headline.  Returns the previous mode.  A backward pass runs in the mode of its forward pass whatever
+    the switch says by then (the autograd Functions capture it)."""
+    if mode not in _switches._SEQ_GEMM_MODES:
+        raise ValueError(f"mode must be one of {_switches._SEQ_GEMM_MODES}")
+    prev = load_library().bl_set_seq_gemm_mode(_switches._SEQ_GEMM_MODES.index(mode))
+    return _switches._SEQ_GEMM_MODES[prev]
+
+
+def seq_gemm_mode() -> str:
+    return _switches._SEQ_GEMM_MODES[load_library().bl_seq_gemm_mode()]
 
 
 def set_wgrad_tile(rows: int) -> int:

@@ -9,7 +9,7 @@ import torch
 from . import _switches, _streams
 from ._cabi import bl_great_layer_grads_t, bl_great_layer_t, _check, Dropout, _f32, _i32, load_library, NO_DROPOUT, _p, _stream
 from ._streams import _timed
-from ._autograd import _grad_target, _take_saved
+from ._autograd import _grad_target, _in_seq_gemm_mode, _seq_gemm_mode_code, _take_saved
 from .gemm import gemm_rows, gemm_wgrad, layernorm_bwd
 from .weights import _packed_layer_weights
 
@@ -31,9 +31,16 @@ class _AddLayerNorm(torch.autograd.Function):
         y = torch.empty_like(x)
         mean = torch.empty((n,), dtype=torch.float32, device=dev)
         rstd = torch.empty((n,), dtype=torch.float32, device=dev)
-        _check(load_library().bl_add_layernorm_fwd(x.data_ptr(), _p(r), _f32(gamma).data_ptr(), _f32(beta).data_ptr(), float(eps), n, D,
-                                                   z.data_ptr() if r is not None else None, y.data_ptr(), mean.data_ptr(), rstd.data_ptr(),
-                                                   _stream()), "bl_add_layernorm_fwd")
+        lib = load_library()
+        ptrs = (x.data_ptr(), _p(r), _f32(gamma).data_ptr(), _f32(beta).data_ptr(), float(eps), n, D, z.data_ptr() if r is not None else None,
+                y.data_ptr(), mean.data_ptr(), rstd.data_ptr())
+        if _seq_gemm_mode_code() == 1 and D % 4 == 0 and all(t is None or t.data_ptr() % 16 == 0 for t in (x, r, gamma, beta, y, z)):
+            # bf16x1: the next Linear rounds this output to its bf16 high plane, where an ulp decides between two neighbours 2^-8
+            # apart.  The one-call GREAT layer normalises with the four-channels-per-lane kernel (other order of the row sums, an
+            # ulp apart); the same kernel here keeps the op-by-op path equal to it to fp32 rounding in this mode as well.
+            _check(lib.bl_add_layernorm_fwd_packed(*ptrs, None, _stream()), "bl_add_layernorm_fwd_packed")
+        else:
+            _check(lib.bl_add_layernorm_fwd(*ptrs, _stream()), "bl_add_layernorm_fwd")
         ctx.saved = (z, mean, rstd, gamma, beta, r is not None)
         return y
 
@@ -293,6 +300,7 @@ class _GreatLayer(torch.autograd.Function):
         if chain is not None:
             chain["packed"], chain["of"] = outp, (out.data_ptr(), out._version)
         ctx.saved = (qkv_W, out_W, bias_f, bias_r, lin1_W, lin1_b, lin2_W, lin2_b, norm_g, norm_b, lens, edges, dims, drops, xp, saved, packs)
+        ctx.seq_mode = _seq_gemm_mode_code()
         return out
 
     @staticmethod
@@ -311,8 +319,10 @@ class _GreatLayer(torch.autograd.Function):
         ws = torch.empty((lib.bl_great_layer_workspace_bytes(B, L, H, dk, FF, 1),), dtype=torch.uint8, device=dev)
         g_x = torch.empty((B * L, H * dk), dtype=torch.float32, device=dev)
         side = _streams.side_stream_for_current_device()
-        _check(lib.bl_great_layer_bwd(ctypes.byref(d), _p(xp), _f32(g_out.contiguous()).data_ptr(), saved.data_ptr(), ws.data_ptr(), g_x.data_ptr(),
-                                      ctypes.byref(g), _stream(), side.cuda_stream if side is not None else None), "bl_great_layer_bwd")
+        with _in_seq_gemm_mode(ctx.seq_mode):
+            _check(lib.bl_great_layer_bwd(ctypes.byref(d), _p(xp), _f32(g_out.contiguous()).data_ptr(), saved.data_ptr(), ws.data_ptr(),
+                                          g_x.data_ptr(), ctypes.byref(g), _stream(), side.cuda_stream if side is not None else None),
+                   "bl_great_layer_bwd")
         r = {id(p): t[1] for p, t in zip(params, targets)}
         return (g_x, r[id(qkv_W)], r[id(out_W)], r[id(bias_f)], r[id(bias_r)], r[id(lin1_W)], r[id(lin1_b)], r[id(lin2_W)], r[id(lin2_b)],
                 r[id(norm_g)], r[id(norm_b)], None, None, None, None, None)

@@ -123,13 +123,29 @@ class ModelTrainer:
         # --amp (reference train.py:8,106 -> ptgnn's autocast + GradScaler): on this path the message GEMMs -- half of a step --
         # run with fp16 operands (one MFMA term instead of f16x3's three, half the operand bytes), fp32 accumulation and fp32
         # results; the gradient operand is scaled by its device-side amax, so no GradScaler and no skipped steps.  Everything
-        # else stays fp32.  Applied when training starts (`train`), undone when it ends.
+        # else stays fp32.  The sequence models have no message GEMMs: their Linear layers (QKV / output / feed-forward projections,
+        # seq-gru's input projections) run with bf16 operands instead (hip_ops.set_seq_gemm_mode("bf16x1"): the high plane of the
+        # bf16x3 images, one MFMA term instead of six, fp32 accumulation and results); attention, LayerNorm, the GRU recurrence,
+        # heads, losses and the optimiser stay fp32.  Each switch is set only for a model that has the GEMMs it governs (the
+        # packed-row launchers also carry gnn-mlp's dense node update, which --amp never reduced).  Applied when training starts
+        # (`train`), undone when it ends.
         self._enable_amp = bool(enable_amp)
         self._nn = None
         self._use_multiprocessing = False
         self._train_epoch_end_hooks: List[Callable] = []
         self._validation_epoch_end_hooks: List[Callable] = []
         self._training_start_hooks: List[Callable] = []
+
+    def _amp_targets(self):
+        """(has MLP message GEMMs, has sequence projections): what --amp can reduce in this model."""
+        from buglab.models.layers.gru import BiGRULayer
+        from buglab.models.layers.messagepassing import MlpMessagePassingLayer
+        from buglab.models.layers.relational_transformer import RelationalTransformerEncoderLayer
+        from buglab.models.layers.transformer import TransformerEncoderLayer
+
+        mods = list(self._nn.modules())
+        seq_layers = (BiGRULayer, RelationalTransformerEncoderLayer, TransformerEncoderLayer)
+        return any(isinstance(m, MlpMessagePassingLayer) for m in mods), any(isinstance(m, seq_layers) for m in mods)
 
     # -- contract ---------------------------------------------------------------------------------
     @property
@@ -475,9 +491,19 @@ class ModelTrainer:
         rank, _ = self._world()
         best = float("-inf") if (self._target_metric is not None and self._target_higher_better) else float("inf")
         bad_epochs = 0
-        prev_gemm_mode = hip_ops.set_msg_gemm_mode("f16x1") if self._enable_amp else None
+        prev_gemm_mode = prev_seq_mode = None
         if self._enable_amp:
-            LOGGER.info("--amp: message GEMMs with fp16 operands (one MFMA term, fp32 accumulation); was %s", prev_gemm_mode)
+            has_msg, has_seq = self._amp_targets()
+            if has_msg:
+                prev_gemm_mode = hip_ops.set_msg_gemm_mode("f16x1")
+                LOGGER.info("--amp: message GEMMs with fp16 operands (one MFMA term, fp32 accumulation); was %s", prev_gemm_mode)
+            if has_seq:
+                prev_seq_mode = hip_ops.set_seq_gemm_mode("bf16x1")
+                LOGGER.info("--amp: QKV / output / feed-forward projections with bf16 operands (one MFMA term, fp32 accumulation); "
+                            "attention, LayerNorm, heads, losses and the optimiser stay fp32; was %s", prev_seq_mode)
+            if not (has_msg or has_seq):
+                LOGGER.warning("--amp: this model has neither MLP message GEMMs nor sequence projections -- nothing is reduced, "
+                               "every GEMM stays fp32-accurate.")
         try:
             for epoch in range(self._max_num_epochs):
                 metrics = self._run_training(training_data, epoch, device, optimizer, scheduler, parallelize)
@@ -500,4 +526,6 @@ class ModelTrainer:
             self._drop_prestarted_pool()
             if prev_gemm_mode is not None:
                 hip_ops.set_msg_gemm_mode(prev_gemm_mode)
+            if prev_seq_mode is not None:
+                hip_ops.set_seq_gemm_mode(prev_seq_mode)
         return best

@@ -23,6 +23,7 @@
 // (winner-masked) left operand for the input-gradient GEMM.
 #include <stdio.h>
 #include <stdlib.h>
+#include <string.h>
 
 #include "bl_common.h"
 #include "bl_gemm_host.h"
@@ -166,7 +167,10 @@ struct X6Epi {
 #define X6_PLAIN_WGS 3
 // (ablation builds of this kernel -- rows not gathered, no MFMAs, no result stores, term-major MFMA order, direct stores -- are made
 // from tools/experiments/bl_gemm_x6_switches.hip; their numbers are in tools/experiments/README.md)
-template <bool MASKED, int EPI>
+// ONE: the reduced-precision form behind bl_set_seq_gemm_mode(1) ("bf16x1", `train.py --amp` on the sequence models): the same
+// packed images, high planes only -- the mid / lo planes are neither loaded nor staged (LDS rows of 64 B, padded to 80 B in the
+// plain form), one MFMA term per 16 k's, fp32 accumulation; every epilogue as in the six-term form.
+template <bool MASKED, int EPI, bool ONE>
 __global__ __launch_bounds__(256, MASKED ? X6_MASKED_WGS : X6_PLAIN_WGS) void gemm_rows_x6_kernel(
     const uint4* __restrict__ xp0, const uint4* __restrict__ xp1, const uint4* __restrict__ xp2,
     const int* __restrict__ idx0, const int* __restrict__ idx1, const int* __restrict__ idx2, int w0, int w1, int w2,
@@ -179,9 +183,12 @@ __global__ __launch_bounds__(256, MASKED ? X6_MASKED_WGS : X6_PLAIN_WGS) void ge
   constexpr bool E_ACT = EPI >= 0 && EPI < 32, E_PACK = EPI >= 16 && (EPI < 32 || EPI == 64), E_RES = EPI == 32, E_MASK = EPI == 64;
   constexpr int ACT = EPI >= 0 ? (EPI & 15) : 0;
   constexpr bool SWZ = X6_SWIZZLED(MASKED);
-  constexpr int XROW = SWZ ? 12 : 13;
+  constexpr int NP = ONE ? 1 : 3;                                   // planes loaded, staged and multiplied
+  constexpr int XROW = ONE ? (SWZ ? 4 : 5) : (SWZ ? 12 : 13);        // (ONE, padded: 80-byte rows -- 16 rows' b128 reads on 64 different banks)
+  constexpr int XEPI = 4 * 32 * 68 / 4;                              // uint4 the four waves' result tiles take on their way out
+  constexpr int XLDS = (XBM + XBN) * XROW > XEPI ? (XBM + XBN) * XROW : XEPI;
 #define XSLOT(row_, kg_) (SWZ ? ((kg_) ^ (((row_) >> 2) & 3)) : (kg_))
-  __shared__ uint4 ABs[(XBM + XBN) * XROW];
+  __shared__ uint4 ABs[XLDS];
   uint4* As = ABs;
   uint4* Bs = ABs + XBM * XROW;
 
@@ -204,7 +211,7 @@ __global__ __launch_bounds__(256, MASKED ? X6_MASKED_WGS : X6_PLAIN_WGS) void ge
     gr1[i] = nsrc > 1 ? (idx1 ? idx1[r] : r) : 0;
     gr2[i] = nsrc > 2 ? (idx2 ? idx2[r] : r) : 0;
   }
-  uint4 ra[2][3], rb[2][3];
+  uint4 ra[2][NP], rb[2][NP];
   uint32_t ma[2];
   const int nk = (K + 31) / 32;
 
@@ -223,13 +230,17 @@ __global__ __launch_bounds__(256, MASKED ? X6_MASKED_WGS : X6_PLAIN_WGS) void ge
       const int gr_ = j_ == 0 ? gr0[i] : (j_ == 1 ? gr1[i] : gr2[i]);                                         \
       const uint4* src_ = base_ + (size_t)gr_ * 3 * (wj_ >> 3) + (kl_ >> 3);                                  \
       ra[i][0] = src_[0];                                                                                     \
-      ra[i][1] = src_[wj_ >> 3];                                                                              \
-      ra[i][2] = src_[2 * (wj_ >> 3)];                                                                        \
+      if constexpr (!ONE) {                                                                                   \
+        ra[i][1] = src_[wj_ >> 3];                                                                            \
+        ra[i][2] = src_[2 * (wj_ >> 3)];                                                                      \
+      }                                                                                                       \
       if (MASKED) ma[i] = win_bits[(size_t)(row0 + min(row_, nrows - 1)) * ld_bits + (kc_ >> 5)];              \
       const uint4* bsrc_ = Bt + (size_t)((k0_) >> 5) * 1536 + i * 768;                                        \
       rb[i][0] = bsrc_[0];                                                                                    \
-      rb[i][1] = bsrc_[256];                                                                                  \
-      rb[i][2] = bsrc_[512];                                                                                  \
+      if constexpr (!ONE) {                                                                                   \
+        rb[i][1] = bsrc_[256];                                                                                \
+        rb[i][2] = bsrc_[512];                                                                                \
+      }                                                                                                       \
     }                                                                                                         \
   }
 #define X6_STORE_STAGE(k0_)                                                                                   \
@@ -241,7 +252,7 @@ __global__ __launch_bounds__(256, MASKED ? X6_MASKED_WGS : X6_PLAIN_WGS) void ge
       if (MASKED) keep_ = keep_from_bits(ma[i] >> (8 * p_kg)); /* k0 is a multiple of 32 */                  \
       if (!kok_) keep_ = make_uint4(0u, 0u, 0u, 0u);                                                          \
       const bool nok_ = kok_ && (n0 + row_ < N);                                                              \
-      _Pragma("unroll") for (int p = 0; p < 3; ++p) {                                                         \
+      _Pragma("unroll") for (int p = 0; p < NP; ++p) {                                                        \
         uint4 a_ = ra[i][p];                                                                                  \
         a_.x &= keep_.x; a_.y &= keep_.y; a_.z &= keep_.z; a_.w &= keep_.w;                                   \
         As[row_ * XROW + p * 4 + XSLOT(row_, p_kg)] = a_;                                                     \
@@ -268,38 +279,51 @@ __global__ __launch_bounds__(256, MASKED ? X6_MASKED_WGS : X6_PLAIN_WGS) void ge
 #pragma unroll
     for (int s = 0; s < 2; ++s) {  // two 16-k MFMA steps per stage; this lane's 8 k's = group 2s + half
       const int kg = 2 * s + half;
-      bf16x8 ah[2], am[2], al[2], bh[2], bm[2], bl[2];
+      if constexpr (ONE) {
+        bf16x8 ah[2], bh[2];
 #pragma unroll
-      for (int ti = 0; ti < 2; ++ti) {
-        const uint4* p = &As[(wm * 64 + ti * 32 + li) * XROW + XSLOT(li, kg)];
-        ah[ti] = __builtin_bit_cast(bf16x8, p[0]);
-        am[ti] = __builtin_bit_cast(bf16x8, p[4]);
-        al[ti] = __builtin_bit_cast(bf16x8, p[8]);
-      }
+        for (int t = 0; t < 2; ++t) {
+          ah[t] = __builtin_bit_cast(bf16x8, As[(wm * 64 + t * 32 + li) * XROW + XSLOT(li, kg)]);
+          bh[t] = __builtin_bit_cast(bf16x8, Bs[(wn * 64 + t * 32 + li) * XROW + XSLOT(li, kg)]);
+        }
 #pragma unroll
-      for (int tj = 0; tj < 2; ++tj) {
-        const uint4* p = &Bs[(wn * 64 + tj * 32 + li) * XROW + XSLOT(li, kg)];
-        bh[tj] = __builtin_bit_cast(bf16x8, p[0]);
-        bm[tj] = __builtin_bit_cast(bf16x8, p[4]);
-        bl[tj] = __builtin_bit_cast(bf16x8, p[8]);
-      }
-      // swapped operands (B fragment in the A slot): the accumulator holds the transposed tile, so
-      // a lane owns 4 consecutive columns of one row.  Small terms first.  The six terms of one accumulator are written back to
-      // back (hipcc alternates between two accumulators); letting the four accumulators take turns instead measured equal
-      // (profiles/r04y_term_major.log): a dependent MFMA two issue slots later does not stall
+        for (int ti = 0; ti < 2; ++ti)
 #pragma unroll
-      for (int ti = 0; ti < 2; ++ti)
+          for (int tj = 0; tj < 2; ++tj) acc[ti][tj] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bh[tj], ah[ti], acc[ti][tj], 0, 0, 0);
+      } else {
+        bf16x8 ah[2], am[2], al[2], bh[2], bm[2], bl[2];
+#pragma unroll
+        for (int ti = 0; ti < 2; ++ti) {
+          const uint4* p = &As[(wm * 64 + ti * 32 + li) * XROW + XSLOT(li, kg)];
+          ah[ti] = __builtin_bit_cast(bf16x8, p[0]);
+          am[ti] = __builtin_bit_cast(bf16x8, p[4]);
+          al[ti] = __builtin_bit_cast(bf16x8, p[8]);
+        }
 #pragma unroll
         for (int tj = 0; tj < 2; ++tj) {
-          f32x16 a = acc[ti][tj];
-          a = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bm[tj], am[ti], a, 0, 0, 0);
-          a = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bl[tj], ah[ti], a, 0, 0, 0);
-          a = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bh[tj], al[ti], a, 0, 0, 0);
-          a = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bm[tj], ah[ti], a, 0, 0, 0);
-          a = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bh[tj], am[ti], a, 0, 0, 0);
-          a = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bh[tj], ah[ti], a, 0, 0, 0);
-          acc[ti][tj] = a;
+          const uint4* p = &Bs[(wn * 64 + tj * 32 + li) * XROW + XSLOT(li, kg)];
+          bh[tj] = __builtin_bit_cast(bf16x8, p[0]);
+          bm[tj] = __builtin_bit_cast(bf16x8, p[4]);
+          bl[tj] = __builtin_bit_cast(bf16x8, p[8]);
         }
+        // swapped operands (B fragment in the A slot): the accumulator holds the transposed tile, so
+        // a lane owns 4 consecutive columns of one row.  Small terms first.  The six terms of one accumulator are written back to
+        // back (hipcc alternates between two accumulators); letting the four accumulators take turns instead measured equal
+        // (profiles/r04y_term_major.log): a dependent MFMA two issue slots later does not stall
+#pragma unroll
+        for (int ti = 0; ti < 2; ++ti)
+#pragma unroll
+          for (int tj = 0; tj < 2; ++tj) {
+            f32x16 a = acc[ti][tj];
+            a = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bm[tj], am[ti], a, 0, 0, 0);
+            a = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bl[tj], ah[ti], a, 0, 0, 0);
+            a = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bh[tj], al[ti], a, 0, 0, 0);
+            a = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bm[tj], ah[ti], a, 0, 0, 0);
+            a = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bh[tj], am[ti], a, 0, 0, 0);
+            a = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bh[tj], ah[ti], a, 0, 0, 0);
+            acc[ti][tj] = a;
+          }
+      }
     }
     __syncthreads();
     if (kt + 1 < nk) {
@@ -414,7 +438,8 @@ __device__ __forceinline__ bf16x8 tr_frag(const short* p) {
   return __builtin_bit_cast(bf16x8, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
 }
 
-template <bool ROUTED>
+// ONE: the high planes only (bl_set_seq_gemm_mode(1)), as in gemm_rows_x6_kernel
+template <bool ROUTED, bool ONE>
 __global__ __launch_bounds__(256, 2) void gemm_wgrad_x6_kernel(
     const uint4* __restrict__ xp0, const uint4* __restrict__ xp1, const uint4* __restrict__ xp2,
     const int* __restrict__ idx0, const int* __restrict__ idx1, const int* __restrict__ idx2, int w0, int w1, int w2,
@@ -422,8 +447,9 @@ __global__ __launch_bounds__(256, 2) void gemm_wgrad_x6_kernel(
     const uint32_t* __restrict__ win_bits, int ld_bits, const int* __restrict__ group_ptr, const int* __restrict__ group_w, int G,
     int M, int N, int K, int kchunk, float* __restrict__ gw_base, long long strideW, int ldw, int ntiles_n, int xcd_remap,
     unsigned* __restrict__ order_ctr) {
-  __shared__ __attribute__((aligned(16))) short As[WOPER];
-  __shared__ __attribute__((aligned(16))) short Bs[WOPER];
+  constexpr int NP = ONE ? 1 : 3;
+  __shared__ __attribute__((aligned(16))) short As[NP * WPLANE];
+  __shared__ __attribute__((aligned(16))) short Bs[NP * WPLANE];
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   int g, e0, ne, tile_y;
@@ -449,7 +475,7 @@ __global__ __launch_bounds__(256, 2) void gemm_wgrad_x6_kernel(
   const uint32_t* __restrict__ mbase = ROUTED ? win_bits + (nnc >> 5) : nullptr;
   const int mshift = nnc & 31;
 
-  uint4 ra[2][3], rb[2][3];
+  uint4 ra[2][NP], rb[2][NP];
   uint32_t mk[2];
   int arow[2], grow[2], mrow[2];  // gathered rows / message ids of the NEXT stage to load
 
@@ -468,12 +494,16 @@ __global__ __launch_bounds__(256, 2) void gemm_wgrad_x6_kernel(
     _Pragma("unroll") for (int i = 0; i < 2; ++i) {                                              \
       const uint4* a_ = abase + (size_t)arow[i] * 3 * awg;                                       \
       ra[i][0] = a_[0];                                                                          \
-      ra[i][1] = a_[awg];                                                                        \
-      ra[i][2] = a_[2 * awg];                                                                    \
+      if constexpr (!ONE) {                                                                      \
+        ra[i][1] = a_[awg];                                                                      \
+        ra[i][2] = a_[2 * awg];                                                                  \
+      }                                                                                          \
       const uint4* g_ = gbase + (size_t)grow[i] * 3 * gwg;                                       \
       rb[i][0] = g_[0];                                                                          \
-      rb[i][1] = g_[gwg];                                                                        \
-      rb[i][2] = g_[2 * gwg];                                                                    \
+      if constexpr (!ONE) {                                                                      \
+        rb[i][1] = g_[gwg];                                                                      \
+        rb[i][2] = g_[2 * gwg];                                                                  \
+      }                                                                                          \
       mk[i] = ROUTED ? mbase[(size_t)mrow[i] * ld_bits] : 0u;                                    \
     }                                                                                            \
   }
@@ -485,7 +515,7 @@ __global__ __launch_bounds__(256, 2) void gemm_wgrad_x6_kernel(
       uint4 keep_ = ROUTED ? keep_from_bits(mk[i] >> mshift) : make_uint4(~0u, ~0u, ~0u, ~0u);   \
       if (!(eok_ && b_ok)) keep_ = make_uint4(0u, 0u, 0u, 0u);                                   \
       const int slot_ = (msg0 + 16 * i) * WRS + 8 * fg;                                          \
-      _Pragma("unroll") for (int p = 0; p < 3; ++p) {                                            \
+      _Pragma("unroll") for (int p = 0; p < NP; ++p) {                                           \
         *reinterpret_cast<uint4*>(&As[p * WPLANE + slot_]) = (eok_ && a_ok) ? ra[i][p] : make_uint4(0u, 0u, 0u, 0u); \
         uint4 b_ = rb[i][p];                                                                     \
         b_.x &= keep_.x; b_.y &= keep_.y; b_.z &= keep_.z; b_.w &= keep_.w;                      \
@@ -522,18 +552,22 @@ __global__ __launch_bounds__(256, 2) void gemm_wgrad_x6_kernel(
     }
 #pragma unroll
     for (int s = 0; s < 2; ++s) {  // two 16-message MFMA steps per stage
-      bf16x8 af[2][3], bf[2][3];
+      bf16x8 af[2][NP], bf[2][NP];
 #pragma unroll
       for (int t = 0; t < 2; ++t)
 #pragma unroll
-        for (int p = 0; p < 3; ++p) {
+        for (int p = 0; p < NP; ++p) {
           af[t][p] = tr_frag(a_tr + p * WPLANE + s * 16 * WRS + t * 32);
           bf[t][p] = tr_frag(b_tr + p * WPLANE + s * 16 * WRS + t * 32);
         }
 #define WX6_TERM(pa_, pb_)                                                                            \
   _Pragma("unroll") for (int ti = 0; ti < 2; ++ti) _Pragma("unroll") for (int tj = 0; tj < 2; ++tj)   \
       acc[ti][tj] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[ti][pa_], bf[tj][pb_], acc[ti][tj], 0, 0, 0);
-      WX6_TERM(1, 1) WX6_TERM(2, 0) WX6_TERM(0, 2) WX6_TERM(1, 0) WX6_TERM(0, 1) WX6_TERM(0, 0)
+      if constexpr (ONE) {
+        WX6_TERM(0, 0)
+      } else {
+        WX6_TERM(1, 1) WX6_TERM(2, 0) WX6_TERM(0, 2) WX6_TERM(1, 0) WX6_TERM(0, 1) WX6_TERM(0, 0)
+      }
     }
     __syncthreads();
     if (kt + 1 < nk) {
@@ -880,10 +914,30 @@ extern "C" int bl_pack_weights_multi(const bl_pack_job_t* jobs_device, int32_t n
   return BL_OK;
 }
 
+// Operand split of the packed-row GEMMs the sequence models' projections run on (bl_gemm_rows_x6 / _epi / _epi2 / x6w,
+// bl_gemm_wgrad_x6): 0 = bf16x6 (six MFMA terms, fp32-equivalent; the default), 1 = bf16x1 (the ONE forms: high planes only --
+// bf16 operands, fp32 accumulation and results; `train.py --amp`).  BL_SEQ_GEMM=x1 / bf16x1 / amp in the environment sets
+// the initial value.
+static int g_seq_gemm_mode = -1;
+extern "C" int32_t bl_seq_gemm_mode(void) {
+  if (g_seq_gemm_mode < 0) {
+    const char* e = getenv("BL_SEQ_GEMM");
+    g_seq_gemm_mode = (e && (strcmp(e, "x1") == 0 || strcmp(e, "bf16x1") == 0 || strcmp(e, "amp") == 0)) ? 1 : 0;
+  }
+  return g_seq_gemm_mode;
+}
+extern "C" int32_t bl_set_seq_gemm_mode(int32_t mode) {
+  const int32_t prev = bl_seq_gemm_mode();
+  BL_CHECK_ARG(mode == 0 || mode == 1, "bl_set_seq_gemm_mode: mode must be 0 (bf16x6) or 1 (bf16x1), got %d", mode);
+  g_seq_gemm_mode = mode;
+  return prev;
+}
+
 namespace {
 int gemm_rows_x6_impl(const char* who, const bl_rows_packed_t* a, const uint32_t* win_bits, int32_t ld_bits, const uint16_t* bp,
                       int64_t b_group_stride, const int32_t* group_ptr, const int32_t* group_w, int32_t G, int32_t M, int32_t N,
                       int32_t K, const X6Epi* epi, float* c, int32_t ldc, void* stream) {
+  const bool one = bl_seq_gemm_mode() == 1;
   if (M == 0) return BL_OK;
   BlPackedRows r;
   if (int rc = bl_packed_rows(who, a, K, r)) return rc;
@@ -901,27 +955,34 @@ int gemm_rows_x6_impl(const char* who, const bl_rows_packed_t* a, const uint32_t
 #define X6_ARGS                                                                                                               \
   BL_PACKED_ROWS_ARGS(r), win_bits, ld_bits, reinterpret_cast<const uint4*>(bp), (long long)(b_group_stride / 8), group_ptr, \
       group_w, G, M, N, K, c, ldc, xcd, e
+#define X6_LAUNCH(masked_, epi_)                                                                                        \
+  {                                                                                                                    \
+    if (one)                                                                                                           \
+      hipLaunchKernelGGL((gemm_rows_x6_kernel<masked_, epi_, true>), grid, dim3(256), 0, (hipStream_t)stream, X6_ARGS);  \
+    else                                                                                                               \
+      hipLaunchKernelGGL((gemm_rows_x6_kernel<masked_, epi_, false>), grid, dim3(256), 0, (hipStream_t)stream, X6_ARGS); \
+  }
   if (win_bits)
-    hipLaunchKernelGGL((gemm_rows_x6_kernel<true, -1>), grid, dim3(256), 0, (hipStream_t)stream, X6_ARGS);
+    X6_LAUNCH(true, -1)
   else if (epi && e.form == BL_X6_EPI_ACT_PACK && e.act == BL_ACT_RELU)
-    hipLaunchKernelGGL((gemm_rows_x6_kernel<false, 16 + BL_ACT_RELU>), grid, dim3(256), 0, (hipStream_t)stream, X6_ARGS);
+    X6_LAUNCH(false, 16 + BL_ACT_RELU)
   else if (epi && e.form == BL_X6_EPI_RES)
-    hipLaunchKernelGGL((gemm_rows_x6_kernel<false, 32>), grid, dim3(256), 0, (hipStream_t)stream, X6_ARGS);
+    X6_LAUNCH(false, 32)
   else if (epi && e.form == BL_X6_EPI_MASK_PACK)
-    hipLaunchKernelGGL((gemm_rows_x6_kernel<false, 64>), grid, dim3(256), 0, (hipStream_t)stream, X6_ARGS);
+    X6_LAUNCH(false, 64)
   else if (epi && e.form != BL_X6_EPI_ACT) {
     bl_set_error("%s: epilogue form %d with activation %d is not built (packed result: relu only)", who, e.form, e.act);
     return BL_EINVAL;
   } else if (epi == nullptr)
-    hipLaunchKernelGGL((gemm_rows_x6_kernel<false, -1>), grid, dim3(256), 0, (hipStream_t)stream, X6_ARGS);
+    X6_LAUNCH(false, -1)
   else if (e.act == BL_ACT_TANH)
-    hipLaunchKernelGGL((gemm_rows_x6_kernel<false, BL_ACT_TANH>), grid, dim3(256), 0, (hipStream_t)stream, X6_ARGS);
+    X6_LAUNCH(false, BL_ACT_TANH)
   else if (e.act == BL_ACT_RELU)
-    hipLaunchKernelGGL((gemm_rows_x6_kernel<false, BL_ACT_RELU>), grid, dim3(256), 0, (hipStream_t)stream, X6_ARGS);
+    X6_LAUNCH(false, BL_ACT_RELU)
   else if (e.act == BL_ACT_SIGMOID)
-    hipLaunchKernelGGL((gemm_rows_x6_kernel<false, BL_ACT_SIGMOID>), grid, dim3(256), 0, (hipStream_t)stream, X6_ARGS);
+    X6_LAUNCH(false, BL_ACT_SIGMOID)
   else if (e.act == BL_ACT_NONE)
-    hipLaunchKernelGGL((gemm_rows_x6_kernel<false, BL_ACT_NONE>), grid, dim3(256), 0, (hipStream_t)stream, X6_ARGS);
+    X6_LAUNCH(false, BL_ACT_NONE)
   else {
     bl_set_error("%s: activation %d has no bf16x6 epilogue (none / relu / sigmoid / tanh)", who, e.act);
     return BL_EINVAL;
@@ -943,14 +1004,14 @@ bool g_wgrad_wide = true;  // bl_set_wgrad_tile: A/B switch between the 256 x 12
 int g_wgrad_kchunk_cap = 4096;
 
 // (a template, so that naming the kernel here does not instantiate it ahead of the dispatch chain: the chain orders the code object)
-template <bool ROUTED>
+template <bool ROUTED, bool ONE>
 int wgrad_x6_resident() {
-  return bl_resident_workgroups<gemm_wgrad_x6_kernel<ROUTED>>(256, 2);
+  return bl_resident_workgroups<gemm_wgrad_x6_kernel<ROUTED, ONE>>(256, 2);
 }
 
 int gemm_wgrad_x6_impl(const char* who, const bl_rows_packed_t* a, const uint16_t* g_packed, const int32_t* g_idx,
                        const uint32_t* win_bits, int32_t ld_bits, const int32_t* group_ptr, const int32_t* group_w, int32_t G,
-                       int32_t M, int32_t N, int32_t K, float* gw, int64_t gw_group_stride, int32_t ld_gw, void* stream) {
+                       int32_t M, int32_t N, int32_t K, float* gw, int64_t gw_group_stride, int32_t ld_gw, bool one, void* stream) {
   if (M == 0) return BL_OK;
   BlPackedRows r;
   if (int rc = bl_packed_rows(who, a, K, r)) return rc;
@@ -970,8 +1031,10 @@ int gemm_wgrad_x6_impl(const char* who, const bl_rows_packed_t* a, const uint16_
   // plain (direct-row) weight gradients with few rows -- the sequence models' Linears, 16 384 token rows -- are faster on the
   // 128 x 128 tile (two workgroups per CU): 58 vs 64 us per launch at seq-great's shapes (profiles/r03q / r04m seq kernel stats)
   if (!gather && M < 65536) wide = false;
+  if (one) wide = false;  // bf16x1 has the 128 x 128 tile only
   // rows reduced by one workgroup: an integer number of rounds of resident workgroups (bl_wgrad_kchunk)
-  const int resident = wide ? bl_num_cus() : (routed ? wgrad_x6_resident<true>() : wgrad_x6_resident<false>());
+  const int resident = wide ? bl_num_cus() : (one ? (routed ? wgrad_x6_resident<true, true>() : wgrad_x6_resident<false, true>())
+                                                        : (routed ? wgrad_x6_resident<true, false>() : wgrad_x6_resident<false, false>()));
   const int ntiles_n = (N + XBN - 1) / XBN;
   const int ntiles_all = ((K + (wide ? 255 : XBM - 1)) / (wide ? 256 : XBM)) * ntiles_n;
   const int kchunk = bl_wgrad_kchunk(M, ntiles_all, (group_ptr ? G : 0) * ntiles_all, resident, g_wgrad_kchunk_cap);
@@ -987,10 +1050,14 @@ int gemm_wgrad_x6_impl(const char* who, const bl_rows_packed_t* a, const uint16_
     hipLaunchKernelGGL((gemm_wgrad_x6_wide_kernel<false, true>), grid, dim3(512), 0, (hipStream_t)stream, WX6_ARGS);
   else if (wide)
     hipLaunchKernelGGL((gemm_wgrad_x6_wide_kernel<false, false>), grid, dim3(512), 0, (hipStream_t)stream, WX6_ARGS);
+  else if (routed && one)
+    hipLaunchKernelGGL((gemm_wgrad_x6_kernel<true, true>), grid, dim3(256), 0, (hipStream_t)stream, WX6_ARGS);
+  else if (one)
+    hipLaunchKernelGGL((gemm_wgrad_x6_kernel<false, true>), grid, dim3(256), 0, (hipStream_t)stream, WX6_ARGS);
   else if (routed)
-    hipLaunchKernelGGL((gemm_wgrad_x6_kernel<true>), grid, dim3(256), 0, (hipStream_t)stream, WX6_ARGS);
+    hipLaunchKernelGGL((gemm_wgrad_x6_kernel<true, false>), grid, dim3(256), 0, (hipStream_t)stream, WX6_ARGS);
   else
-    hipLaunchKernelGGL((gemm_wgrad_x6_kernel<false>), grid, dim3(256), 0, (hipStream_t)stream, WX6_ARGS);
+    hipLaunchKernelGGL((gemm_wgrad_x6_kernel<false, false>), grid, dim3(256), 0, (hipStream_t)stream, WX6_ARGS);
   BL_LAUNCH_CHECK(who);
   return BL_OK;
 }
@@ -1057,12 +1124,12 @@ extern "C" int bl_gemm_wgrad_routed_x6(const bl_rows_packed_t* a, const uint16_t
                                        int64_t gw_group_stride, int32_t ld_gw, void* stream) {
   BL_CHECK_ARG(M == 0 || (g_idx && win_bits), "bl_gemm_wgrad_routed_x6: needs g_idx and the winner bitmask");
   return gemm_wgrad_x6_impl("bl_gemm_wgrad_routed_x6", a, g_node_packed, g_idx, win_bits, ld_bits, group_ptr, group_w, G, M, N, K, gw,
-                            gw_group_stride, ld_gw, stream);
+                            gw_group_stride, ld_gw, false, stream);  // (a message GEMM: bl_set_msg_gemm_mode's, not the sequence switch's)
 }
 
 extern "C" int bl_gemm_wgrad_x6(const bl_rows_packed_t* a, const uint16_t* g_packed, const int32_t* g_idx, const int32_t* group_ptr,
                                 const int32_t* group_w, int32_t G, int32_t M, int32_t N, int32_t K, float* gw,
                                 int64_t gw_group_stride, int32_t ld_gw, void* stream) {
   return gemm_wgrad_x6_impl("bl_gemm_wgrad_x6", a, g_packed, g_idx, nullptr, 0, group_ptr, group_w, G, M, N, K, gw, gw_group_stride, ld_gw,
-                            stream);
+                            bl_seq_gemm_mode() == 1, stream);
 }

@@ -66,6 +66,7 @@ __device__ __forceinline__ void glds16(const uint4* g, uint4* l) {
 // all fragment reads issued so far have landed; the operands tie the MFMAs behind the wait
 #define LDS_WAIT6(a_, b_, c_, d_, e_, f_) \
   asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a_), "+v"(b_), "+v"(c_), "+v"(d_), "+v"(e_), "+v"(f_)::"memory")
+#define LDS_WAIT2(a_, b_) asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a_), "+v"(b_)::"memory")
 
 #define MF(b_, a_, acc_) \
   acc_ = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, b_), __builtin_bit_cast(bf16x8, a_), acc_, 0, 0, 0)
@@ -78,14 +79,18 @@ __device__ __forceinline__ void glds16(const uint4* g, uint4* l) {
   MF(B_[s_][0], A_[s_][1], acc_); \
   MF(B_[s_][0], A_[s_][0], acc_);
 
-template <bool MASKED>
+// ONE (bl_set_seq_gemm_mode(1), "bf16x1"): the high planes only.  A stage image is [A: 128 x 4 | B: 256 x 4] x 16 B = 24 KB: one DMA piece
+// of A and two of the weight block's first 16 KB (its plane 0) per wave; one MFMA per 16 k's and quadrant.  Same schedule and epilogue.
+template <bool MASKED, bool ONE>
 __global__ __launch_bounds__(512, 2) void gemm_rows_x6w_kernel(
     const uint4* __restrict__ xp0, const uint4* __restrict__ xp1, const uint4* __restrict__ xp2, const int* __restrict__ idx0,
     const int* __restrict__ idx1, const int* __restrict__ idx2, int w0, int w1, int w2, int koff1, int koff2, int nsrc,
     const uint32_t* __restrict__ win_bits, int ld_bits, const uint4* __restrict__ bp, long long strideB,
     const int* __restrict__ group_ptr, const int* __restrict__ group_w, int G, int M, int N, int K, float* __restrict__ c,
     int ldc) {
-  extern __shared__ __attribute__((aligned(16))) uint4 smem[];  // [2 buffers][A: 3 x 128 x 4 | B: 3 x 256 x 4]
+  extern __shared__ __attribute__((aligned(16))) uint4 smem[];  // [2 buffers][A: 3 x 128 x 4 | B: 3 x 256 x 4]  (ONE: 1 x ...)
+  constexpr int NP = ONE ? 1 : 3;
+  constexpr int STAGE_UINT4 = (WBM + WBN) * 4 * NP, B_OFF_UINT4 = WBM * 4 * NP;  // (= W_STAGE_UINT4, W_B_OFF_BYTES / 16 at NP = 3)
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   int g, row0, nrows, tile_y;
   if (!x6_locate(group_ptr, G, M, WBM, 1, tile_y, g, row0, nrows)) return;
@@ -117,13 +122,14 @@ __global__ __launch_bounds__(512, 2) void gemm_rows_x6w_kernel(
 #define W_DMA_A(kt_, As_) /* 3 pieces: row block `wave`, planes 0..2 */                                 \
   {                                                                                                     \
     W_A_SRC(kt_, src_, wq_)                                                                             \
-    _Pragma("unroll") for (int p = 0; p < 3; ++p) glds16(src_ + p * wq_, (As_) + (p * WBM + wave * 16) * 4); \
+    _Pragma("unroll") for (int p = 0; p < NP; ++p) glds16(src_ + p * wq_, (As_) + (p * WBM + wave * 16) * 4); \
   }
-#define W_DMA_B(kt_, As_, q0_) /* 3 of this wave's 6 pieces of the 48 KB weight block */                 \
+#define W_DMA_B(kt_, As_, q0_) /* 3 of this wave's 6 pieces of the 48 KB weight block (ONE: 1 of its 2 of plane 0's 16 KB) */ \
   {                                                                                                     \
     const uint4* bsrc_ = Bt + (size_t)(kt_) * W_BLK + lane;                                             \
-    uint4* Bs_ = (As_) + WBM * 12;                                                                      \
-    _Pragma("unroll") for (int q = (q0_); q < (q0_) + 3; ++q) glds16(bsrc_ + (wave * 6 + q) * 64, Bs_ + (wave * 6 + q) * 64); \
+    uint4* Bs_ = (As_) + B_OFF_UINT4;                                                                   \
+    _Pragma("unroll") for (int q = (q0_) / 3 * NP; q < (q0_) / 3 * NP + NP; ++q)                        \
+      glds16(bsrc_ + (wave * 2 * NP + q) * 64, Bs_ + (wave * 2 * NP + q) * 64);                         \
   }
   uint4 ra0, ra1, ra2;  // routed form: the next stage's A piece and its routing word
   uint32_t ma = 0;
@@ -132,8 +138,10 @@ __global__ __launch_bounds__(512, 2) void gemm_rows_x6w_kernel(
   {                                    \
     W_A_SRC(kt_, src_, wq_)            \
     ra0 = src_[0];                     \
-    ra1 = src_[wq_];                   \
-    ra2 = src_[2 * wq_];               \
+    if constexpr (!ONE) {              \
+      ra1 = src_[wq_];                 \
+      ra2 = src_[2 * wq_];             \
+    }                                  \
     ma = mrow[kt_];                    \
   }
 #define W_STORE_A(As_)                                                              \
@@ -141,8 +149,10 @@ __global__ __launch_bounds__(512, 2) void gemm_rows_x6w_kernel(
     const uint4 keep_ = keep_from_bits(ma >> (8 * a_kg));                           \
     uint4* dst_ = (As_) + a_row * 4 + (a_kg ^ ((a_row >> 2) & 3));                  \
     dst_[0] = make_uint4(ra0.x & keep_.x, ra0.y & keep_.y, ra0.z & keep_.z, ra0.w & keep_.w);           \
-    dst_[WBM * 4] = make_uint4(ra1.x & keep_.x, ra1.y & keep_.y, ra1.z & keep_.z, ra1.w & keep_.w);     \
-    dst_[WBM * 8] = make_uint4(ra2.x & keep_.x, ra2.y & keep_.y, ra2.z & keep_.z, ra2.w & keep_.w);     \
+    if constexpr (!ONE) {                                                                               \
+      dst_[WBM * 4] = make_uint4(ra1.x & keep_.x, ra1.y & keep_.y, ra1.z & keep_.z, ra1.w & keep_.w);   \
+      dst_[WBM * 8] = make_uint4(ra2.x & keep_.x, ra2.y & keep_.y, ra2.z & keep_.z, ra2.w & keep_.w);   \
+    }                                                                                                   \
   }
 
   const int wm = wave & 1, wn = wave >> 1;  // partners on a SIMD (w, w + 4) share the row block, not the columns
@@ -156,9 +166,9 @@ __global__ __launch_bounds__(512, 2) void gemm_rows_x6w_kernel(
     for (int s = 0; s < 2; ++s) {
       const int kg = (2 * s + half) ^ swz;
       aa[0][t][s] = lds0 + ((wm * 64 + t * 32 + li) * 4 + kg) * 16;
-      ab[0][t][s] = lds0 + W_B_OFF_BYTES + ((wn * 64 + t * 32 + li) * 4 + kg) * 16;
-      aa[1][t][s] = aa[0][t][s] + W_STAGE_BYTES;
-      ab[1][t][s] = ab[0][t][s] + W_STAGE_BYTES;
+      ab[0][t][s] = lds0 + B_OFF_UINT4 * 16 + ((wn * 64 + t * 32 + li) * 4 + kg) * 16;
+      aa[1][t][s] = aa[0][t][s] + STAGE_UINT4 * 16;
+      ab[1][t][s] = ab[0][t][s] + STAGE_UINT4 * 16;
     }
 
   f32x16 acc00, acc01, acc10, acc11;
@@ -182,29 +192,41 @@ __global__ __launch_bounds__(512, 2) void gemm_rows_x6w_kernel(
   const bool late = wave >= 4;
   if (late) __builtin_amdgcn_s_barrier();  // group 1 runs one barrier behind group 0
 
-  u32x4 A0[2][3], A1[2][3], B0[2][3], B1[2][3];  // [k-step][plane]
+  u32x4 A0[2][NP], A1[2][NP], B0[2][NP], B1[2][NP];  // [k-step][plane]
 
 #define RD_A(dst_, t_, BUF_)                                  \
   _Pragma("unroll") for (int s = 0; s < 2; ++s) {             \
     LDS_RD(dst_[s][0], aa[BUF_][t_][s], 0);                   \
-    LDS_RD(dst_[s][1], aa[BUF_][t_][s], W_A_PLANE_BYTES);     \
-    LDS_RD(dst_[s][2], aa[BUF_][t_][s], 2 * W_A_PLANE_BYTES); \
+    if constexpr (!ONE) {                                     \
+      LDS_RD(dst_[s][1], aa[BUF_][t_][s], W_A_PLANE_BYTES);   \
+      LDS_RD(dst_[s][2], aa[BUF_][t_][s], 2 * W_A_PLANE_BYTES); \
+    }                                                         \
   }
 #define RD_B(dst_, t_, BUF_)                                  \
   _Pragma("unroll") for (int s = 0; s < 2; ++s) {             \
     LDS_RD(dst_[s][0], ab[BUF_][t_][s], 0);                   \
-    LDS_RD(dst_[s][1], ab[BUF_][t_][s], W_B_PLANE_BYTES);     \
-    LDS_RD(dst_[s][2], ab[BUF_][t_][s], 2 * W_B_PLANE_BYTES); \
+    if constexpr (!ONE) {                                     \
+      LDS_RD(dst_[s][1], ab[BUF_][t_][s], W_B_PLANE_BYTES);     \
+      LDS_RD(dst_[s][2], ab[BUF_][t_][s], 2 * W_B_PLANE_BYTES); \
+    }                                                         \
   }
-#define WAIT_FRAG(F_) LDS_WAIT6(F_[0][0], F_[0][1], F_[0][2], F_[1][0], F_[1][1], F_[1][2])
+#define WAIT_FRAG(F_)                                                                        \
+  if constexpr (ONE) LDS_WAIT2(F_[0][0], F_[1][0]);                                           \
+  else LDS_WAIT6(F_[0][0], F_[0][1], F_[0][2], F_[1][0], F_[1][1], F_[1][2])
+#define TERMS(acc_, A_, B_, s_)                        \
+  if constexpr (ONE) {                                 \
+    MF(B_[s_][0], A_[s_][0], acc_);                    \
+  } else {                                             \
+    SIX(acc_, A_, B_, s_)                              \
+  }
 #define SEG_MFMA(acc_, A_, B_)       \
   __builtin_amdgcn_s_barrier();      \
   WAIT_FRAG(A_);                     \
   WAIT_FRAG(B_);                     \
   __builtin_amdgcn_sched_barrier(0); \
   __builtin_amdgcn_s_setprio(1);     \
-  SIX(acc_, A_, B_, 0)               \
-  SIX(acc_, A_, B_, 1)               \
+  TERMS(acc_, A_, B_, 0)             \
+  TERMS(acc_, A_, B_, 1)             \
   __builtin_amdgcn_s_setprio(0);     \
   __builtin_amdgcn_sched_barrier(0); \
   __builtin_amdgcn_s_barrier();
@@ -212,7 +234,7 @@ __global__ __launch_bounds__(512, 2) void gemm_rows_x6w_kernel(
   // BUF_ = buffer this stage reads (literal 0 / 1); the next stage's pieces go to the other one
 #define STAGE(kt_, BUF_)                                                                                   \
   {                                                                                                        \
-    uint4* nxt_ = smem + (1 - (BUF_)) * W_STAGE_UINT4;                                                     \
+    uint4* nxt_ = smem + (1 - (BUF_)) * STAGE_UINT4;                                                       \
     const bool more_ = (kt_) + 1 < nk;                                                                     \
     /* phase 0: quadrant 00 */                                                                             \
     RD_A(A0, 0, BUF_)                                                                                      \
@@ -329,12 +351,17 @@ extern "C" int bl_gemm_rows_x6w(const bl_rows_packed_t* a, const uint32_t* win_b
                "%s: packed group stride must cover one group's weight image (bl_pack_weights_x6w)", who);
   BL_CHECK_ARG(win_bits == nullptr || (a->nsrc == 1 && a->idx[0] && ld_bits * 32 >= K),
                "%s: the routed form needs exactly one gathered source and ld_bits >= K / 32", who);
-  const size_t lds = (size_t)2 * W_STAGE_BYTES;
+  const bool one = bl_seq_gemm_mode() == 1;
+  // two stage images; the bf16x1 form's 2 x 24 KB are less than what the eight waves' result tiles take on their way out
+  const size_t lds = one ? (size_t)8 * 32 * 68 * 4 : (size_t)2 * W_STAGE_BYTES;
   static bool attr_plain[BL_MAX_DEVICES] = {false}, attr_routed[BL_MAX_DEVICES] = {false};  // (calls come from one thread per process)
+  static bool attr_plain1[BL_MAX_DEVICES] = {false}, attr_routed1[BL_MAX_DEVICES] = {false};
   BL_CHECK_ARG(bl_max_lds_per_block() >= (int)lds, "%s: the device offers %d B of LDS per workgroup, %d needed (bl_gemm_rows_x6w_ok)", who,
                bl_max_lds_per_block(), (int)lds);
-  if (bl_raise_lds_limit_once((const void*)gemm_rows_x6w_kernel<false>, (int)lds, attr_plain) != BL_OK ||
-      bl_raise_lds_limit_once((const void*)gemm_rows_x6w_kernel<true>, (int)lds, attr_routed) != BL_OK) {
+  if (one ? (bl_raise_lds_limit_once((const void*)gemm_rows_x6w_kernel<false, true>, (int)lds, attr_plain1) != BL_OK ||
+             bl_raise_lds_limit_once((const void*)gemm_rows_x6w_kernel<true, true>, (int)lds, attr_routed1) != BL_OK)
+          : (bl_raise_lds_limit_once((const void*)gemm_rows_x6w_kernel<false, false>, (int)lds, attr_plain) != BL_OK ||
+             bl_raise_lds_limit_once((const void*)gemm_rows_x6w_kernel<true, false>, (int)lds, attr_routed) != BL_OK)) {
     bl_set_error("%s: cannot raise the dynamic LDS limit to %d B", who, (int)lds);
     return BL_EINVAL;
   }
@@ -342,10 +369,14 @@ extern "C" int bl_gemm_rows_x6w(const bl_rows_packed_t* a, const uint32_t* win_b
 #define X6W_ARGS                                                                                                              \
   BL_PACKED_ROWS_ARGS(r), win_bits, ld_bits, reinterpret_cast<const uint4*>(bp), (long long)(b_group_stride / 8), group_ptr, \
       group_w, G, M, N, K, c, ldc
-  if (win_bits)
-    hipLaunchKernelGGL((gemm_rows_x6w_kernel<true>), grid, dim3(512), lds, (hipStream_t)stream, X6W_ARGS);
+  if (win_bits && one)
+    hipLaunchKernelGGL((gemm_rows_x6w_kernel<true, true>), grid, dim3(512), lds, (hipStream_t)stream, X6W_ARGS);
+  else if (one)
+    hipLaunchKernelGGL((gemm_rows_x6w_kernel<false, true>), grid, dim3(512), lds, (hipStream_t)stream, X6W_ARGS);
+  else if (win_bits)
+    hipLaunchKernelGGL((gemm_rows_x6w_kernel<true, false>), grid, dim3(512), lds, (hipStream_t)stream, X6W_ARGS);
   else
-    hipLaunchKernelGGL((gemm_rows_x6w_kernel<false>), grid, dim3(512), lds, (hipStream_t)stream, X6W_ARGS);
+    hipLaunchKernelGGL((gemm_rows_x6w_kernel<false, false>), grid, dim3(512), lds, (hipStream_t)stream, X6W_ARGS);
   BL_LAUNCH_CHECK(who);
   return BL_OK;
 }

@@ -23,6 +23,8 @@
 //             GEMMs on the side stream when one is given (each is one round of 128 x 128 tiles at these shapes -- a third of
 //             what a CU can hold -- and depends only on its Linear's packed output gradient), joined before the call returns
 // The caller owns every buffer (`saved` lives from forward to backward, `ws` during the call); nothing is allocated here.
+#include <mutex>
+
 #include "bl_common.h"
 
 namespace {
@@ -158,6 +160,35 @@ SideEvents* ensure_events() {
   return &e;
 }
 
+// The operand split (bl_seq_gemm_mode) a forward call's `saved` was written in, by pointer: the backward's GEMMs read packed
+// activations and produce gradients that belong to that arithmetic, so a backward in the other mode is refused.  Host side (the
+// blob is device memory and the backward does not wait for the device); a fixed ring -- an entry leaves when its backward has
+// run, when the same address is saved to again, or as the oldest of kSavedModes (its backward is then not checked).
+constexpr int kSavedModes = 1024;
+struct SavedMode { const void* p; int mode; };
+SavedMode g_saved_modes[kSavedModes];
+int g_saved_next = 0;
+std::mutex g_saved_mutex;
+void note_saved_mode(const void* saved, int mode) {
+  std::lock_guard<std::mutex> lock(g_saved_mutex);
+  for (SavedMode& e : g_saved_modes)
+    if (e.p == saved) {
+      e.mode = mode;
+      return;
+    }
+  g_saved_modes[g_saved_next] = SavedMode{saved, mode};
+  g_saved_next = (g_saved_next + 1) % kSavedModes;
+}
+int take_saved_mode(const void* saved) {  // -1: unknown
+  std::lock_guard<std::mutex> lock(g_saved_mutex);
+  for (SavedMode& e : g_saved_modes)
+    if (e.p == saved) {
+      e.p = nullptr;
+      return e.mode;
+    }
+  return -1;
+}
+
 int check_desc(const char* who, const bl_great_layer_t* d) {
   BL_CHECK_ARG(d, "%s: null layer description", who);
   BL_CHECK_ARG(bl_great_layer_ok(d->B, d->L, d->H, d->dk, d->T, d->FF), "%s: shape B=%d L=%d H=%d dk=%d T=%d FF=%d is outside bl_great_layer_ok "
@@ -200,6 +231,7 @@ extern "C" int bl_great_layer_fwd(const bl_great_layer_t* d, const float* x, con
   // forward-only call (saved == NULL): what a backward pass would read lives in the workspace instead
   const Saved sv = saved ? carve_saved(saved, s, x_packed == nullptr) : carve_saved(static_cast<char*>(ws) + w.bytes, s, true);
   const float scale = 1.0f / sqrtf((float)dk);
+  if (saved) note_saved_mode(saved, bl_seq_gemm_mode());
 
   const uint16_t* xp = x_packed;
   if (xp == nullptr) {
@@ -264,6 +296,9 @@ extern "C" int bl_great_layer_bwd(const bl_great_layer_t* d, const uint16_t* x_p
   BL_CHECK_ARG(g->qkv_w && g->out_w && g->lin1_w && g->lin1_b && g->lin2_w && g->lin2_b && g->norm_g && g->norm_b,
                "bl_great_layer_bwd: null gradient buffer");
   BL_CHECK_ARG(d->row_ptr == nullptr || (g->bias_f && g->bias_r), "bl_great_layer_bwd: edge entries need the edge-bias gradient buffers");
+  const int fwd_mode = take_saved_mode(saved);
+  BL_CHECK_ARG(fwd_mode < 0 || fwd_mode == bl_seq_gemm_mode(), "bl_great_layer_bwd: `saved` was written in sequence GEMM mode %d, the current "
+               "mode is %d (bl_set_seq_gemm_mode)", fwd_mode, bl_seq_gemm_mode());
   const Shape s = shape_of(d->B, d->L, d->H, d->dk, d->FF, d->T);
   const int R = (int)s.R, D = (int)s.D, FF = s.FF, dk = s.dk;
   const Saved sv = carve_saved(const_cast<void*>(saved), s, x_packed == nullptr);
