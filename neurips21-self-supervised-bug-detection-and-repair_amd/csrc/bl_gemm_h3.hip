@@ -28,33 +28,16 @@
 // operands (transposed accumulators), LDS-staged epilogue, XCD-aware work order (bl_x6_locate.h).  LDS stage row:
 // [plane (2)][k-group slot (4)] x 16 B + 16 B of padding = 144 B (36 r mod 64 walks all sixteen 4-bank groups over 16 rows:
 // fragment reads conflict-free).
-#include <float.h>
 #include <stdio.h>
 #include <stdlib.h>
 
 #include "bl_common.h"
 #include "bl_gemm_host.h"
+#include "bl_gemm_split.h"
 #include "bl_x6_locate.h"
 #include "bl_h3_image.h"
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-
-#define HBM 128
-#define HBN 128
-#define HROW 9  // uint4 per LDS stage row: 2 planes x 4 k-groups + 1 pad
-
 // ---- packing ------------------------------------------------------------------------------------
-// scale from a device-resident amax (gradient tensors): s = 2^(14 - e) with 2^(e-1) < amax <= 2^e; amax == 0 (or non-finite) -> 1
-__device__ __forceinline__ float h3_scale_from_amax(float amax) {
-  if (!(amax > 0.f) || amax > FLT_MAX) return 1.f;
-  int e;
-  (void)frexpf(amax, &e);  // amax = m 2^e, m in [0.5, 1)
-  int k = 14 - e;
-  k = k > 100 ? 100 : (k < -100 ? -100 : k);
-  return ldexpf(1.f, k);
-}
-
 // rows: out[r][plane][kg][j] = plane(x[r, 8 kg + j] * scale), planes back to back (row = 2 D halves)
 // (kg_total, kg_off) as in pack_rows_kernel: a ConcatResidual pair is packed without a concatenated copy
 __global__ __launch_bounds__(256) void pack_rows_h_kernel(const float* __restrict__ x, int ld, long long R, int D, uint4* __restrict__ out,
@@ -77,7 +60,6 @@ __global__ __launch_bounds__(256) void pack_rows_h_kernel(const float* __restric
   for (int j = 0; j < 8; ++j) split2h(v[j] * scale, h[j], l[j], sat);
   if (sat && sat_counter) atomicAdd(sat_counter, 1u);  // (rare by construction: the scales leave 2^6 - 2^8 of headroom)
   uint4* o = out + r * 2 * kgn + kg;
-#define PK(a_, b_) ((uint32_t)(a_) | ((uint32_t)(b_) << 16))
   o[0] = make_uint4(PK(h[0], h[1]), PK(h[2], h[3]), PK(h[4], h[5]), PK(h[6], h[7]));
   o[kgn] = make_uint4(PK(l[0], l[1]), PK(l[2], l[3]), PK(l[4], l[5]), PK(l[6], l[7]));
 }
@@ -88,11 +70,10 @@ __global__ __launch_bounds__(256) void pack_weights_h_kernel(const float* __rest
 }
 
 // ---- row GEMM --------------------------------------------------------------------------------------
-// C[rows of g] = out_scale * rows(a) . B_g, rows gathered from <= 3 packed sources; MASKED: the routed left operand (one source,
-// winner bitmask) of the input-gradient GEMM.  out_scale = 1 / (s_a s_b) (host part) x *out_scale_dev (when the left operand's
-// scale lives in device memory: the reciprocal of h3_scale_from_amax(*amax)).
-// ONE: the reduced-precision form behind `train.py --amp` (bl_set_msg_gemm_mode(2)): the high planes only -- one fp16 MFMA term with
-// fp32 accumulation, what torch.cuda.amp.autocast makes of a Linear -- from the same packed images (the low planes are not read).
+// gemm_rows_body (bl_gemm_split.h) on the two-plane fp16 split, epilogue-free: C[rows of g] = out_scale * rows(a) . B_g with
+// out_scale = 1 / (s_a s_b) (host part) x the reciprocal of h3_scale_from_amax(*a_amax_dev) when the left operand's scale lives in
+// device memory.  ONE (bl_set_msg_gemm_mode(2), `train.py --amp`): one fp16 MFMA term with fp32 accumulation, what
+// torch.cuda.amp.autocast makes of a Linear.
 template <bool MASKED, bool ONE>
 __global__ __launch_bounds__(256, MASKED ? 2 : 3) void gemm_rows_h3_kernel(
     const uint4* __restrict__ xp0, const uint4* __restrict__ xp1, const uint4* __restrict__ xp2,
@@ -100,161 +81,12 @@ __global__ __launch_bounds__(256, MASKED ? 2 : 3) void gemm_rows_h3_kernel(
     int koff1, int koff2, int nsrc, const uint32_t* __restrict__ win_bits, int ld_bits, const uint4* __restrict__ bp,
     long long strideB, const int* __restrict__ group_ptr, const int* __restrict__ group_w, int G, int M, int N, int K,
     float* __restrict__ c, int ldc, int xcd_remap, float out_scale, const float* __restrict__ a_amax_dev) {
-  __shared__ uint4 ABs[(HBM + HBN) * HROW];  // 36 KB; after the last stage the waves' result tiles are staged in it (4 x 8.5 KB)
-  uint4* As = ABs;
-  uint4* Bs = ABs + HBM * HROW;
-
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  int g, row0, nrows, tile_y;
-  if (!x6_locate(group_ptr, G, M, HBM, xcd_remap, tile_y, g, row0, nrows)) return;
-  const int n0 = tile_y * HBN;
-  const int wsel = group_w ? group_w[g] : g;
-  const uint4* __restrict__ Bt = bp + (long long)wsel * strideB + (size_t)tile_y * (K >> 5) * 1024 + tid;
-
-  const int p_kg = tid & 3, p_row0 = tid >> 2;  // rows p_row0 and p_row0 + 64
-  int gr0[2], gr1[2], gr2[2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    const int r = row0 + min(p_row0 + 64 * i, nrows - 1);
-    gr0[i] = idx0 ? idx0[r] : r;
-    gr1[i] = nsrc > 1 ? (idx1 ? idx1[r] : r) : 0;
-    gr2[i] = nsrc > 2 ? (idx2 ? idx2[r] : r) : 0;
-  }
-  uint4 ra[2][2], rb[2][2];
-  uint32_t ma[2];
-  const int nk = (K + 31) / 32;
-
-#define H3_LOAD_STAGE(k0_)                                                                                    \
-  {                                                                                                           \
-    const int k_ = (k0_) + 8 * p_kg;                                                                          \
-    const int kc_ = k_ < K ? k_ : 0;                                                                          \
-    int j_ = 0;                                                                                               \
-    if (nsrc > 1 && kc_ >= koff1) j_ = 1;                                                                     \
-    if (nsrc > 2 && kc_ >= koff2) j_ = 2;                                                                     \
-    const int kl_ = kc_ - (j_ == 0 ? 0 : (j_ == 1 ? koff1 : koff2));                                          \
-    const uint4* base_ = j_ == 0 ? xp0 : (j_ == 1 ? xp1 : xp2);                                               \
-    const int wj_ = j_ == 0 ? w0 : (j_ == 1 ? w1 : w2);                                                       \
-    _Pragma("unroll") for (int i = 0; i < 2; ++i) {                                                           \
-      const int row_ = p_row0 + 64 * i;                                                                       \
-      const int gr_ = j_ == 0 ? gr0[i] : (j_ == 1 ? gr1[i] : gr2[i]);                                         \
-      const uint4* src_ = base_ + (size_t)gr_ * 2 * (wj_ >> 3) + (kl_ >> 3);                                  \
-      ra[i][0] = src_[0];                                                                                     \
-      if (!ONE) ra[i][1] = src_[wj_ >> 3];                                                                    \
-      if (MASKED) ma[i] = win_bits[(size_t)(row0 + min(row_, nrows - 1)) * ld_bits + (kc_ >> 5)];              \
-      const uint4* bsrc_ = Bt + (size_t)((k0_) >> 5) * 1024 + i * 512;                                        \
-      rb[i][0] = bsrc_[0];                                                                                    \
-      if (!ONE) rb[i][1] = bsrc_[256];                                                                        \
-    }                                                                                                         \
-  }
-#define H3_STORE_STAGE(k0_)                                                                                   \
-  {                                                                                                           \
-    const bool kok_ = (k0_) + 8 * p_kg < K;                                                                   \
-    _Pragma("unroll") for (int i = 0; i < 2; ++i) {                                                           \
-      const int row_ = p_row0 + 64 * i;                                                                       \
-      uint4 keep_ = make_uint4(~0u, ~0u, ~0u, ~0u);                                                           \
-      if (MASKED) keep_ = keep_from_bits(ma[i] >> (8 * p_kg)); /* k0 is a multiple of 32 */                  \
-      if (!kok_) keep_ = make_uint4(0u, 0u, 0u, 0u);                                                          \
-      const bool nok_ = kok_ && (n0 + row_ < N);                                                              \
-      _Pragma("unroll") for (int p = 0; p < (ONE ? 1 : 2); ++p) {                                             \
-        uint4 a_ = ra[i][p];                                                                                  \
-        a_.x &= keep_.x; a_.y &= keep_.y; a_.z &= keep_.z; a_.w &= keep_.w;                                   \
-        As[row_ * HROW + p * 4 + p_kg] = a_;                                                                  \
-        Bs[row_ * HROW + p * 4 + p_kg] = nok_ ? rb[i][p] : make_uint4(0u, 0u, 0u, 0u);                        \
-      }                                                                                                       \
-    }                                                                                                         \
-  }
-
-  f32x16 acc[2][2];
-#pragma unroll
-  for (int ti = 0; ti < 2; ++ti)
-#pragma unroll
-    for (int tj = 0; tj < 2; ++tj)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[ti][tj][r] = 0.f;
-
-  const int wm = wave >> 1, wn = wave & 1, li = lane & 31, half = lane >> 5;
-
-  H3_LOAD_STAGE(0)
-  H3_STORE_STAGE(0)
-  __syncthreads();
-  for (int kt = 0; kt < nk; ++kt) {
-    if (kt + 1 < nk) H3_LOAD_STAGE((kt + 1) * 32)
-#pragma unroll
-    for (int s = 0; s < 2; ++s) {  // two 16-k MFMA steps per stage; this lane's 8 k's = group 2s + half
-      const int kg = 2 * s + half;
-      f16x8 ah[2], al[2], bh[2], bl[2];
-#pragma unroll
-      for (int ti = 0; ti < 2; ++ti) {
-        const uint4* p = &As[(wm * 64 + ti * 32 + li) * HROW + kg];
-        ah[ti] = __builtin_bit_cast(f16x8, p[0]);
-        if (!ONE) al[ti] = __builtin_bit_cast(f16x8, p[4]);
-      }
-#pragma unroll
-      for (int tj = 0; tj < 2; ++tj) {
-        const uint4* p = &Bs[(wn * 64 + tj * 32 + li) * HROW + kg];
-        bh[tj] = __builtin_bit_cast(f16x8, p[0]);
-        if (!ONE) bl[tj] = __builtin_bit_cast(f16x8, p[4]);
-      }
-      // swapped operands (B fragment in the A slot): the accumulator holds the transposed tile; small terms first
-#pragma unroll
-      for (int ti = 0; ti < 2; ++ti)
-#pragma unroll
-        for (int tj = 0; tj < 2; ++tj) {
-          f32x16 a = acc[ti][tj];
-          if (!ONE) {
-            a = __builtin_amdgcn_mfma_f32_32x32x16_f16(bl[tj], ah[ti], a, 0, 0, 0);
-            a = __builtin_amdgcn_mfma_f32_32x32x16_f16(bh[tj], al[ti], a, 0, 0, 0);
-          }
-          a = __builtin_amdgcn_mfma_f32_32x32x16_f16(bh[tj], ah[ti], a, 0, 0, 0);
-          acc[ti][tj] = a;
-        }
-    }
-    __syncthreads();
-    if (kt + 1 < nk) {
-      H3_STORE_STAGE((kt + 1) * 32)
-      __syncthreads();
-    }
-  }
-
-  if (a_amax_dev) out_scale /= h3_scale_from_amax(*a_amax_dev);
-  // result tile through LDS (the operand images are dead), leaving as whole 256-byte row pieces (see bl_gemm_x6.hip)
-  float* stage = reinterpret_cast<float*>(ABs) + wave * (32 * 68);
-#pragma unroll
-  for (int ti = 0; ti < 2; ++ti) {
-#pragma unroll
-    for (int tj = 0; tj < 2; ++tj)
-#pragma unroll
-      for (int gq = 0; gq < 4; ++gq)
-        *reinterpret_cast<float4*>(stage + li * 68 + tj * 32 + 8 * gq + 4 * half) =
-            make_float4(acc[ti][tj][4 * gq + 0] * out_scale, acc[ti][tj][4 * gq + 1] * out_scale, acc[ti][tj][4 * gq + 2] * out_scale,
-                        acc[ti][tj][4 * gq + 3] * out_scale);
-    const int c4 = lane & 15, n = n0 + wn * 64 + 4 * c4;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const int r = (lane >> 4) + 4 * j;
-      const int mm = wm * 64 + ti * 32 + r;
-      const float4 v = *reinterpret_cast<const float4*>(stage + r * 68 + 4 * c4);
-      if (mm < nrows && n < N) bl_store_streaming(c + (size_t)(row0 + mm) * ldc + n, v);
-    }
-  }
+  gemm_rows_body<SplitF16x2, MASKED, -1, ONE>(xp0, xp1, xp2, idx0, idx1, idx2, w0, w1, w2, koff1, koff2, nsrc, win_bits, ld_bits, bp,
+                                              strideB, group_ptr, group_w, G, M, N, K, c, ldc, xcd_remap, X6Epi{}, out_scale, a_amax_dev);
 }
-
 
 // ---- weight-gradient GEMM (128 x 128 tile) ---------------------------------------------------------
-// gW_g[i, n] += out_scale * sum_{e in group g} A[e, i] * Gr[e, n]   (bl_gemm_x6.hip::gemm_wgrad_x6_kernel with two planes:
-// operands stored in LDS as they arrive, [plane][message][feature] rows of 320 B, fragments by ds_read_b64_tr_b16)
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-#define HWRS 160
-#define HWPLANE (32 * HWRS)
-#define HWOPER (2 * HWPLANE)
-
-__device__ __forceinline__ f16x8 h3_tr_frag(const short* p) {
-  typedef s16x4 __attribute__((address_space(3))) * lds_s16x4_ptr;
-  const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(p));
-  const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(p + 4 * HWRS));
-  return __builtin_bit_cast(f16x8, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
-}
-
+// gemm_wgrad_body (bl_gemm_split.h) on the two-plane fp16 split: gW_g[i, n] += out_scale * sum_{e in group g} A[e, i] * Gr[e, n]
 template <bool ROUTED, bool ONE>
 __global__ __launch_bounds__(256, 2) void gemm_wgrad_h3_kernel(
     const uint4* __restrict__ xp0, const uint4* __restrict__ xp1, const uint4* __restrict__ xp2,
@@ -263,141 +95,9 @@ __global__ __launch_bounds__(256, 2) void gemm_wgrad_h3_kernel(
     const uint32_t* __restrict__ win_bits, int ld_bits, const int* __restrict__ group_ptr, const int* __restrict__ group_w, int G,
     int M, int N, int K, int kchunk, float* __restrict__ gw_base, long long strideW, int ldw, int ntiles_n, int xcd_remap,
     unsigned* __restrict__ order_ctr, float out_scale, const float* __restrict__ g_amax_dev) {
-  __shared__ __attribute__((aligned(16))) short As[HWOPER];
-  __shared__ __attribute__((aligned(16))) short Bs[HWOPER];
-
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  int g, e0, ne, tile_y;
-  if (!x6_locate(group_ptr, G, M, kchunk, xcd_remap, tile_y, g, e0, ne)) return;
-  const int e1 = e0 + ne;
-  const int i0 = (tile_y / ntiles_n) * HBM;
-  const int n0 = (tile_y % ntiles_n) * HBN;
-  const int wsel = group_w ? group_w[g] : g;
-
-  const int fg = tid & 15, msg0 = tid >> 4;  // messages msg0 and msg0 + 16
-  const int fi = i0 + 8 * fg, nn = n0 + 8 * fg;
-  const bool a_ok = fi < K, b_ok = nn < N;
-  const int fic = a_ok ? fi : 0, nnc = b_ok ? nn : 0;
-  int aj = 0;
-  if (nsrc > 1 && fic >= koff1) aj = 1;
-  if (nsrc > 2 && fic >= koff2) aj = 2;
-  const uint4* __restrict__ abase = (aj == 0 ? xp0 : (aj == 1 ? xp1 : xp2)) + ((fic - (aj == 0 ? 0 : (aj == 1 ? koff1 : koff2))) >> 3);
-  const int* __restrict__ aidx = aj == 0 ? idx0 : (aj == 1 ? idx1 : idx2);
-  const int awg = (aj == 0 ? w0 : (aj == 1 ? w1 : w2)) >> 3;  // uint4 per plane of an A row
-  const int gwg = N >> 3;
-  const uint4* __restrict__ gbase = gp + (nnc >> 3);
-  const uint32_t* __restrict__ mbase = ROUTED ? win_bits + (nnc >> 5) : nullptr;
-  const int mshift = nnc & 31;
-
-  uint4 ra[2][2], rb[2][2];
-  uint32_t mk[2];
-  int arow[2], grow[2], mrow[2];
-
-#define HW_LOAD_IDX(k0_)                                           \
-  {                                                                \
-    _Pragma("unroll") for (int i = 0; i < 2; ++i) {                \
-      const int e_ = (k0_) + msg0 + 16 * i;                        \
-      const int ec_ = e_ < e1 ? e_ : e0;                           \
-      arow[i] = aidx ? aidx[ec_] : ec_;                            \
-      grow[i] = g_idx ? g_idx[ec_] : ec_;                          \
-      mrow[i] = ec_;                                               \
-    }                                                              \
-  }
-#define HW_LOAD_STAGE()                                                                          \
-  {                                                                                              \
-    _Pragma("unroll") for (int i = 0; i < 2; ++i) {                                              \
-      const uint4* a_ = abase + (size_t)arow[i] * 2 * awg;                                       \
-      ra[i][0] = a_[0];                                                                          \
-      if (!ONE) ra[i][1] = a_[awg];                                                              \
-      const uint4* g_ = gbase + (size_t)grow[i] * 2 * gwg;                                       \
-      rb[i][0] = g_[0];                                                                          \
-      if (!ONE) rb[i][1] = g_[gwg];                                                              \
-      mk[i] = ROUTED ? mbase[(size_t)mrow[i] * ld_bits] : 0u;                                    \
-    }                                                                                            \
-  }
-#define HW_STORE_STAGE(k0_)                                                                      \
-  {                                                                                              \
-    _Pragma("unroll") for (int i = 0; i < 2; ++i) {                                              \
-      const int eid_ = (k0_) + msg0 + 16 * i;                                                    \
-      const bool eok_ = eid_ < e1;                                                               \
-      uint4 keep_ = ROUTED ? keep_from_bits(mk[i] >> mshift) : make_uint4(~0u, ~0u, ~0u, ~0u);   \
-      if (!(eok_ && b_ok)) keep_ = make_uint4(0u, 0u, 0u, 0u);                                   \
-      const int slot_ = (msg0 + 16 * i) * HWRS + 8 * fg;                                         \
-      _Pragma("unroll") for (int p = 0; p < (ONE ? 1 : 2); ++p) {                                \
-        *reinterpret_cast<uint4*>(&As[p * HWPLANE + slot_]) = (eok_ && a_ok) ? ra[i][p] : make_uint4(0u, 0u, 0u, 0u); \
-        uint4 b_ = rb[i][p];                                                                     \
-        b_.x &= keep_.x; b_.y &= keep_.y; b_.z &= keep_.z; b_.w &= keep_.w;                      \
-        *reinterpret_cast<uint4*>(&Bs[p * HWPLANE + slot_]) = b_;                                \
-      }                                                                                          \
-    }                                                                                            \
-  }
-
-  f32x16 acc[2][2];
-#pragma unroll
-  for (int ti = 0; ti < 2; ++ti)
-#pragma unroll
-    for (int tj = 0; tj < 2; ++tj)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[ti][tj][r] = 0.f;
-
-  const int wm = wave >> 1, wn = wave & 1, li = lane & 31, half = lane >> 5;
-  const int l16 = lane & 15, grp = lane >> 4;
-  const int tr_off = ((grp >> 1) * 8 + (l16 >> 2)) * HWRS + (grp & 1) * 16 + 4 * (l16 & 3);
-  const short* a_tr = As + tr_off + wm * 64;
-  const short* b_tr = Bs + tr_off + wn * 64;
-  const int nk = (ne + 31) / 32;
-
-  HW_LOAD_IDX(e0)
-  HW_LOAD_STAGE()
-  HW_LOAD_IDX(e0 + 32)
-  HW_STORE_STAGE(e0)
-  __syncthreads();
-  for (int kt = 0; kt < nk; ++kt) {
-    if (kt + 1 < nk) {
-      HW_LOAD_STAGE()
-      HW_LOAD_IDX(e0 + (kt + 2) * 32)
-    }
-#pragma unroll
-    for (int s = 0; s < 2; ++s) {  // two 16-message MFMA steps per stage
-      f16x8 af[2][2], bf[2][2];
-#pragma unroll
-      for (int t = 0; t < 2; ++t)
-#pragma unroll
-        for (int p = 0; p < (ONE ? 1 : 2); ++p) {
-          af[t][p] = h3_tr_frag(a_tr + p * HWPLANE + s * 16 * HWRS + t * 32);
-          bf[t][p] = h3_tr_frag(b_tr + p * HWPLANE + s * 16 * HWRS + t * 32);
-        }
-#define HW_TERM(pa_, pb_)                                                                             \
-  _Pragma("unroll") for (int ti = 0; ti < 2; ++ti) _Pragma("unroll") for (int tj = 0; tj < 2; ++tj)   \
-      acc[ti][tj] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[ti][pa_], bf[tj][pb_], acc[ti][tj], 0, 0, 0);
-      if (!ONE) { HW_TERM(1, 0) HW_TERM(0, 1) }
-      HW_TERM(0, 0)
-    }
-    __syncthreads();
-    if (kt + 1 < nk) {
-      HW_STORE_STAGE(e0 + (kt + 1) * 32)
-      __syncthreads();
-    }
-  }
-
-  if (g_amax_dev) out_scale /= h3_scale_from_amax(*g_amax_dev);
-  float* __restrict__ gw = gw_base + (long long)wsel * strideW;
-  unsigned* ctr = order_ctr ? order_ctr + (size_t)g * gridDim.y + tile_y : nullptr;
-  const unsigned turn = (unsigned)((e0 - (group_ptr ? group_ptr[g] : 0)) / kchunk);
-  bl_ordered_enter(ctr, turn);
-#pragma unroll
-  for (int ti = 0; ti < 2; ++ti)
-#pragma unroll
-    for (int tj = 0; tj < 2; ++tj) {
-      const int n = n0 + wn * 64 + tj * 32 + li;
-      if (n >= N) continue;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int f = i0 + wm * 64 + ti * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
-        if (f < K) unsafeAtomicAdd(&gw[(size_t)f * ldw + n], acc[ti][tj][r] * out_scale);
-      }
-    }
-  bl_ordered_leave(ctr, turn);
+  gemm_wgrad_body<SplitF16x2, ROUTED, ONE>(xp0, xp1, xp2, idx0, idx1, idx2, w0, w1, w2, koff1, koff2, nsrc, gp, g_idx, win_bits, ld_bits,
+                                           group_ptr, group_w, G, M, N, K, kchunk, gw_base, strideW, ldw, ntiles_n, xcd_remap, order_ctr,
+                                           out_scale, g_amax_dev);
 }
 
 // ---- amax of a tensor into device memory (gradient operands) ----------------------------------------
@@ -492,15 +192,11 @@ extern "C" int bl_gemm_rows_h3(const bl_rows_packed_t* a, const uint32_t* win_bi
   const char* who = "bl_gemm_rows_h3";
   if (M == 0) return BL_OK;
   BlPackedRows r;
-  if (int rc = bl_packed_rows(who, a, K, r)) return rc;
-  BL_CHECK_ARG(M > 0 && N > 0 && N % 4 == 0 && ldc % 4 == 0 && bp && c && bl_aligned16(bp) && bl_aligned16(c),
-               "%s: N/ldc multiples of 4, aligned pointers required", who);
+  dim3 grid;
+  if (int rc = bl_rows_gemm_plan(who, a, win_bits, ld_bits, bp, group_ptr, G, M, N, K, c, ldc, XBM, r, grid)) return rc;
   BL_CHECK_ARG(b_group_stride % 8 == 0 && (G <= 1 || b_group_stride >= bl_packed_weight_elems_h3(1, K, N)),
                "%s: packed group stride must cover one group's tiled weights (bl_pack_weights_h3)", who);
-  BL_CHECK_ARG(win_bits == nullptr || (a->nsrc == 1 && a->idx[0] && ld_bits * 32 >= K),
-               "%s: the routed form needs exactly one gathered source and ld_bits >= K / 32", who);
   BL_CHECK_ARG(out_scale > 0.f, "%s: out_scale must be positive", who);
-  dim3 grid((M + HBM - 1) / HBM + (group_ptr ? G : 0), (N + HBN - 1) / HBN);
 #define H3_ARGS                                                                                                               \
   BL_PACKED_ROWS_ARGS(r), win_bits, ld_bits, reinterpret_cast<const uint4*>(bp), (long long)(b_group_stride / 8), group_ptr, \
       group_w, G, M, N, K, c, ldc, 1, out_scale, a_amax_dev
@@ -517,7 +213,6 @@ extern "C" int bl_gemm_rows_h3(const bl_rows_packed_t* a, const uint32_t* win_bi
   return BL_OK;
 }
 
-int g_h3_kchunk_cap = 4096;  // rows per workgroup flush; follows bl_set_wgrad_kchunk_cap (csrc/bl_gemm_x6.hip)
 // (a template, so that naming the kernel here does not instantiate it ahead of the dispatch chain: the chain orders the code object)
 template <bool ROUTED>
 static int wgrad_h3_resident() {
@@ -536,16 +231,12 @@ extern "C" int bl_gemm_wgrad_h3(const bl_rows_packed_t* a, const uint16_t* g_pac
                "%s: N a multiple of 32, aligned pointers and a positive out_scale required", who);
   const bool routed = win_bits != nullptr;
   BL_CHECK_ARG(!routed || (g_idx && ld_bits * 32 >= N), "%s: the routed form needs g_idx and ld_bits >= N / 32", who);
-  const int resident = routed ? wgrad_h3_resident<true>() : wgrad_h3_resident<false>();
-  const int ntiles_n = (N + HBN - 1) / HBN;
-  const int ntiles_all = ((K + HBM - 1) / HBM) * ntiles_n;
-  const int kchunk = bl_wgrad_kchunk(M, ntiles_all, (group_ptr ? G : 0) * ntiles_all, resident, g_h3_kchunk_cap);
-  dim3 grid((M + kchunk - 1) / kchunk + (group_ptr ? G : 0), ntiles_all);
-  unsigned* order_ctr = group_w ? nullptr : bl_order_counters((group_ptr ? G : 1) * ntiles_all, stream);
-  const int xcd = order_ctr ? 0 : 1;
+  const BlWgradPlan p = bl_wgrad_plan(group_ptr, group_w, G, M, N, K, XBM, XBN, routed ? wgrad_h3_resident<true>() : wgrad_h3_resident<false>(),
+                                      stream);
+  const dim3 grid = p.grid;
 #define HW_ARGS                                                                                                                  \
-  BL_PACKED_ROWS_ARGS(r), reinterpret_cast<const uint4*>(g_packed), g_idx, win_bits, ld_bits, group_ptr, group_w, G, M, N, K, kchunk, \
-      gw, (long long)gw_group_stride, ld_gw, ntiles_n, xcd, order_ctr, out_scale, g_amax_dev
+  BL_PACKED_ROWS_ARGS(r), reinterpret_cast<const uint4*>(g_packed), g_idx, win_bits, ld_bits, group_ptr, group_w, G, M, N, K, p.kchunk, \
+      gw, (long long)gw_group_stride, ld_gw, p.ntiles_n, p.xcd, p.order_ctr, out_scale, g_amax_dev
   if (g_h3_one_term) {
     if (routed)
       hipLaunchKernelGGL((gemm_wgrad_h3_kernel<true, true>), grid, dim3(256), 0, (hipStream_t)stream, HW_ARGS);

@@ -1,5 +1,6 @@
 // Host side shared by the GEMM entry points (bl_gemm*.hip): the rules of the packed rows descriptor, the order in which
-// its twelve kernel arguments are passed, the weight gradients' chunk solver and the cached resident-workgroup count.
+// its twelve kernel arguments are passed, the argument rules and grid of the 128 x 128 row GEMMs, the weight gradients'
+// launch plan (chunk solver, grid, flush order) and the cached resident-workgroup count.
 // Host-only: no device code and nothing exported.
 #pragma once
 #include "bl_common.h"
@@ -37,6 +38,20 @@ static inline int bl_packed_rows(const char* who, const bl_rows_packed_t* a, int
   (r).x[0], (r).x[1], (r).x[2], (r).idx[0], (r).idx[1], (r).idx[2], (r).width[0], (r).width[1], (r).width[2], (r).koff[1], \
       (r).koff[2], (r).nsrc
 
+// What the row GEMMs of both operand splits (bl_gemm_rows_x6*, bl_gemm_rows_h3) ask of their arguments besides the weight
+// image's size, which each checks itself, and their grid: row pieces of `tile` rows (one partial piece more per group) x column tiles.
+static inline int bl_rows_gemm_plan(const char* who, const bl_rows_packed_t* a, const uint32_t* win_bits, int ld_bits, const void* bp,
+                                    const int32_t* group_ptr, int G, int M, int N, int K, const float* c, int ldc, int tile,
+                                    BlPackedRows& r, dim3& grid) {
+  if (int rc = bl_packed_rows(who, a, K, r)) return rc;
+  BL_CHECK_ARG(M > 0 && N > 0 && N % 4 == 0 && ldc % 4 == 0 && bp && c && bl_aligned16(bp) && bl_aligned16(c),
+               "%s: N/ldc multiples of 4, aligned pointers required", who);
+  BL_CHECK_ARG(win_bits == nullptr || (a->nsrc == 1 && a->idx[0] && ld_bits * 32 >= K),
+               "%s: the routed form needs exactly one gathered source and ld_bits >= K / 32", who);
+  grid = dim3((M + tile - 1) / tile + (group_ptr ? G : 0), (N + tile - 1) / tile);
+  return BL_OK;
+}
+
 // Rows one workgroup of a weight-gradient GEMM reduces before it flushes its output tile: the chunk of the smallest integer
 // number of rounds of `resident` workgroups that is <= cap rows (a partial last round is tail: 1.24 rounds at a fixed chunk
 // cost 38 % of the kernel), a multiple of 32 and >= 256 so that the tile-sized atomic flush is amortised.
@@ -53,6 +68,35 @@ static inline int bl_wgrad_kchunk(long long M, int ntiles_all, int extra, int re
     }
   }
   return kchunk < 256 ? 256 : kchunk;
+}
+
+// Largest number of rows one workgroup of a weight-gradient GEMM (either operand split) reduces before it flushes its output
+// tile (bl_set_wgrad_kchunk_cap).  Every flush is tile-size fp32 atomics, and the chip retires ~312 G of those per second whatever
+// the addresses (tools/atomic_bench.py): at c2's layer shape (E = 640 000, K = 256, N = 128) the 864-row chunks of the old cap
+// (1024) were 97 MB = 24 M atomics per launch, ~0.08 ms of a 0.25-ms kernel; the cap trades that against the balance of the last
+// round of workgroups.  Measured on bf16x6 (profiles/r04e_kcap_*.log, same box): H = 128 layer 0.254 / 0.232 / 0.210 / 0.220 /
+// 0.217 ms at 1024 / 2048 / 3072 / 4096 / 8192, concat layer 0.921 / 0.863 / 0.824 / 0.829 / 0.908 ms at 1024 / 2048 / 4096 /
+// 8192 / 16384.
+inline int g_wgrad_kchunk_cap = 4096;
+
+// Launch plan of a weight-gradient GEMM with tile_rows x tile_cols output tiles: rows per workgroup (bl_wgrad_kchunk: an integer
+// number of rounds of `resident` workgroups), the grid, and the flush order -- without group_w every (group, tile) owns its output
+// and its chunks can add in order (the counters are null unless the deterministic mode is on).
+struct BlWgradPlan {
+  int ntiles_n, kchunk, xcd;
+  dim3 grid;
+  unsigned* order_ctr;
+};
+static inline BlWgradPlan bl_wgrad_plan(const int32_t* group_ptr, const int32_t* group_w, int G, int M, int N, int K, int tile_rows,
+                                        int tile_cols, int resident, void* stream) {
+  BlWgradPlan p;
+  p.ntiles_n = (N + tile_cols - 1) / tile_cols;
+  const int ntiles_all = ((K + tile_rows - 1) / tile_rows) * p.ntiles_n;
+  p.kchunk = bl_wgrad_kchunk(M, ntiles_all, (group_ptr ? G : 0) * ntiles_all, resident, g_wgrad_kchunk_cap);
+  p.grid = dim3((M + p.kchunk - 1) / p.kchunk + (group_ptr ? G : 0), ntiles_all);
+  p.order_ctr = group_w ? nullptr : bl_order_counters((group_ptr ? G : 1) * ntiles_all, stream);
+  p.xcd = p.order_ctr ? 0 : 1;  // ordered flushes want "lower chunk = lower workgroup id"
+  return p;
 }
 
 // workgroups of `threads` threads (no dynamic LDS) of Kernel that the device holds at once; asked once per process and kernel

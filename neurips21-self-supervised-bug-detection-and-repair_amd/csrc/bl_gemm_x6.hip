@@ -27,27 +27,10 @@
 
 #include "bl_common.h"
 #include "bl_gemm_host.h"
+#include "bl_gemm_split.h"
 #include "bl_x6_locate.h"
 #include "bl_x6w_image.h"
 #include "bl_h3_image.h"
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
-#define XBM 128
-#define XBN 128
-// LDS row of a stage image: [plane (3)][k-group slot (4)] x 16 B, in one of two layouts:
-//   padded    208-byte rows (13 uint4): fragment reads conflict-free, the staging stores' 16-lane groups overlap in 4 of 64 banks
-//             (SQ_LDS_BANK_CONFLICT a third of SQ_LDS_IDX_ACTIVE, profiles/r04z_fwd_gemm_pmc.json);
-//   swizzled  192-byte rows, k-group kg of a row in slot kg ^ ((row >> 2) & 3): four consecutive rows' 64-byte plane segments tile
-//             the 64 banks and the reads of 16 consecutive rows hit 16 different (segment, slot) pairs -- conflict-free both ways.
-// Measured (profiles/r04y_swizzle.log): the routed form gains 2 % (H = 128 layer) / 4.3 % (concat layer), the plain form loses 2 %
-// at the H = 128 layer (equal at the concat layer).  So: swizzled for the routed form, padded for the plain one (X6_SWZ: 0 = padded
-// everywhere, 1 = swizzled everywhere, 2 = as measured).
-#define X6_SWZ 2
-#define X6_SWIZZLED(masked_) (X6_SWZ == 1 || (X6_SWZ == 2 && (masked_)))
-#define XROW_MAX 13
-
 
 // ---- packing ------------------------------------------------------------------------------------
 // rows: out[r][kg][plane][j] = plane(x[r, 8 kg + j])
@@ -69,7 +52,6 @@ __global__ __launch_bounds__(256) void pack_rows_kernel(const float* __restrict_
 #pragma unroll
   for (int j = 0; j < 8; ++j) split3(v[j], h[j], m[j], l[j]);
   uint4* o = out + r * 3 * kgn + kg;
-#define PK(a_, b_) ((uint32_t)(a_) | ((uint32_t)(b_) << 16))
   o[0] = make_uint4(PK(h[0], h[1]), PK(h[2], h[3]), PK(h[4], h[5]), PK(h[6], h[7]));
   o[kgn] = make_uint4(PK(m[0], m[1]), PK(m[2], m[3]), PK(m[4], m[5]), PK(m[6], m[7]));
   o[2 * kgn] = make_uint4(PK(l[0], l[1]), PK(l[2], l[3]), PK(l[4], l[5]), PK(l[6], l[7]));
@@ -142,34 +124,11 @@ __global__ __launch_bounds__(256) void pack_weights_multi_kernel(const bl_pack_j
 
 // ---- GEMM -----------------------------------------------------------------------------------------
 // (work-item lookup x6_find_piece / x6_locate, XCD-contiguous tile order, routing masks: bl_x6_locate.h)
-// optional epilogue of the row GEMM: C = drop(act(A . B + bias)) -- the dense node update of the message-passing layer
-// (ptgnn MlpMessagePassingLayer's Linear -> tanh -> Dropout tail; call site buglab/models/gnnlayerdefs.py:6-23)
-struct X6Epi {
-  const float* bias;  // [N] or nullptr
-  int act;            // BL_ACT_*
-  uint32_t drop_key, drop_thresh;
-  float drop_scale;
-  // the extended forms (bl_gemm_rows_x6_epi2: the Linear layers of the relational transformer block, csrc/bl_great_layer.hip)
-  int form;                // BL_X6_EPI_*
-  const float* res;        // RES: c = A . B + res[row, n]
-  int ld_res;
-  const uint2* himask;     // MASK: the packed forward output y [M][3 N] -- c = (y's hi plane != 0) ? A . B x mask_scale : 0
-  float mask_scale;
-  float* colsum;           // MASK: [N] += column sums of c (the bias gradient)
-  uint2* c_packed;         // PACK / MASK: the result in bl_pack_bf16x3's form [M][3 N] instead of fp32
-};
-
+// gemm_rows_body (bl_gemm_split.h) on the three-plane bf16 split, with its epilogue family (X6Epi).
 // The plain form fits three workgroups per CU (3 x 52 KB of LDS, <= 168 registers); the routed form
 // keeps its routing bytes and masks in registers and runs two.
-// EPI: -1 = no epilogue, else the activation code (a template parameter: with a run-time switch the compiler evaluates
-// every activation's libm call for every element -- measured 0.12 vs 0.05 ms on the c2 dense shape)
 #define X6_MASKED_WGS 2  // workgroups per CU the routed form is compiled for (3: 168 registers with 11 of them in scratch)
 #define X6_PLAIN_WGS 3
-// (ablation builds of this kernel -- rows not gathered, no MFMAs, no result stores, term-major MFMA order, direct stores -- are made
-// from tools/experiments/bl_gemm_x6_switches.hip; their numbers are in tools/experiments/README.md)
-// ONE: the reduced-precision form behind bl_set_seq_gemm_mode(1) ("bf16x1", `train.py --amp` on the sequence models): the same
-// packed images, high planes only -- the mid / lo planes are neither loaded nor staged (LDS rows of 64 B, padded to 80 B in the
-// plain form), one MFMA term per 16 k's, fp32 accumulation; every epilogue as in the six-term form.
 template <bool MASKED, int EPI, bool ONE>
 __global__ __launch_bounds__(256, MASKED ? X6_MASKED_WGS : X6_PLAIN_WGS) void gemm_rows_x6_kernel(
     const uint4* __restrict__ xp0, const uint4* __restrict__ xp1, const uint4* __restrict__ xp2,
@@ -177,268 +136,12 @@ __global__ __launch_bounds__(256, MASKED ? X6_MASKED_WGS : X6_PLAIN_WGS) void ge
     int koff1, int koff2, int nsrc, const uint32_t* __restrict__ win_bits, int ld_bits, const uint4* __restrict__ bp,
     long long strideB, const int* __restrict__ group_ptr, const int* __restrict__ group_w, int G, int M, int N, int K,
     float* __restrict__ c, int ldc, int xcd_remap, X6Epi epi) {
-  // one array: after the last stage the four waves' result tiles are staged in it on their way out (see the epilogue)
-  // EPI: -1 none; 0..15 = activation code (bias / activation / dropout, fp32 result); 16 + code = the same, result PACKED only;
-  // 32 = + residual (fp32 result); 64 = masked by the packed forward output, column sums, result packed only
-  constexpr bool E_ACT = EPI >= 0 && EPI < 32, E_PACK = EPI >= 16 && (EPI < 32 || EPI == 64), E_RES = EPI == 32, E_MASK = EPI == 64;
-  constexpr int ACT = EPI >= 0 ? (EPI & 15) : 0;
-  constexpr bool SWZ = X6_SWIZZLED(MASKED);
-  constexpr int NP = ONE ? 1 : 3;                                   // planes loaded, staged and multiplied
-  constexpr int XROW = ONE ? (SWZ ? 4 : 5) : (SWZ ? 12 : 13);        // (ONE, padded: 80-byte rows -- 16 rows' b128 reads on 64 different banks)
-  constexpr int XEPI = 4 * 32 * 68 / 4;                              // uint4 the four waves' result tiles take on their way out
-  constexpr int XLDS = (XBM + XBN) * XROW > XEPI ? (XBM + XBN) * XROW : XEPI;
-#define XSLOT(row_, kg_) (SWZ ? ((kg_) ^ (((row_) >> 2) & 3)) : (kg_))
-  __shared__ uint4 ABs[XLDS];
-  uint4* As = ABs;
-  uint4* Bs = ABs + XBM * XROW;
-
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  int g, row0, nrows, tile_y;
-  if (!x6_locate(group_ptr, G, M, XBM, xcd_remap, tile_y, g, row0, nrows)) return;
-  const int n0 = tile_y * XBN;
-  const int wsel = group_w ? group_w[g] : g;
-  // tiled packed weights: this workgroup's 24 KB stage blocks, thread t reads uint4s t + 256 q
-  const uint4* __restrict__ Bt = bp + (long long)wsel * strideB + (size_t)tile_y * (K >> 5) * 1536 + tid;
-
-  // loader mapping: (row, k-group) pairs, 2 per thread; 4 consecutive lanes cover one row's 64-byte
-  // plane segment.  Gathered row ids live in registers (one per piece and source).
-  const int p_kg = tid & 3, p_row0 = tid >> 2;  // rows p_row0 and p_row0 + 64
-  int gr0[2], gr1[2], gr2[2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    const int r = row0 + min(p_row0 + 64 * i, nrows - 1);
-    gr0[i] = idx0 ? idx0[r] : r;
-    gr1[i] = nsrc > 1 ? (idx1 ? idx1[r] : r) : 0;
-    gr2[i] = nsrc > 2 ? (idx2 ? idx2[r] : r) : 0;
-  }
-  uint4 ra[2][NP], rb[2][NP];
-  uint32_t ma[2];
-  const int nk = (K + 31) / 32;
-
-#define X6_LOAD_STAGE(k0_)                                                                                    \
-  {                                                                                                           \
-    const int k_ = (k0_) + 8 * p_kg;                                                                          \
-    const int kc_ = k_ < K ? k_ : 0;                                                                          \
-    int j_ = 0;                                                                                               \
-    if (nsrc > 1 && kc_ >= koff1) j_ = 1;                                                                     \
-    if (nsrc > 2 && kc_ >= koff2) j_ = 2;                                                                     \
-    const int kl_ = kc_ - (j_ == 0 ? 0 : (j_ == 1 ? koff1 : koff2));                                          \
-    const uint4* base_ = j_ == 0 ? xp0 : (j_ == 1 ? xp1 : xp2);                                               \
-    const int wj_ = j_ == 0 ? w0 : (j_ == 1 ? w1 : w2);                                                       \
-    _Pragma("unroll") for (int i = 0; i < 2; ++i) {                                                           \
-      const int row_ = p_row0 + 64 * i;                                                                       \
-      const int gr_ = j_ == 0 ? gr0[i] : (j_ == 1 ? gr1[i] : gr2[i]);                                         \
-      const uint4* src_ = base_ + (size_t)gr_ * 3 * (wj_ >> 3) + (kl_ >> 3);                                  \
-      ra[i][0] = src_[0];                                                                                     \
-      if constexpr (!ONE) {                                                                                   \
-        ra[i][1] = src_[wj_ >> 3];                                                                            \
-        ra[i][2] = src_[2 * (wj_ >> 3)];                                                                      \
-      }                                                                                                       \
-      if (MASKED) ma[i] = win_bits[(size_t)(row0 + min(row_, nrows - 1)) * ld_bits + (kc_ >> 5)];              \
-      const uint4* bsrc_ = Bt + (size_t)((k0_) >> 5) * 1536 + i * 768;                                        \
-      rb[i][0] = bsrc_[0];                                                                                    \
-      if constexpr (!ONE) {                                                                                   \
-        rb[i][1] = bsrc_[256];                                                                                \
-        rb[i][2] = bsrc_[512];                                                                                \
-      }                                                                                                       \
-    }                                                                                                         \
-  }
-#define X6_STORE_STAGE(k0_)                                                                                   \
-  {                                                                                                           \
-    const bool kok_ = (k0_) + 8 * p_kg < K;                                                                   \
-    _Pragma("unroll") for (int i = 0; i < 2; ++i) {                                                           \
-      const int row_ = p_row0 + 64 * i;                                                                       \
-      uint4 keep_ = make_uint4(~0u, ~0u, ~0u, ~0u);                                                           \
-      if (MASKED) keep_ = keep_from_bits(ma[i] >> (8 * p_kg)); /* k0 is a multiple of 32 */                  \
-      if (!kok_) keep_ = make_uint4(0u, 0u, 0u, 0u);                                                          \
-      const bool nok_ = kok_ && (n0 + row_ < N);                                                              \
-      _Pragma("unroll") for (int p = 0; p < NP; ++p) {                                                        \
-        uint4 a_ = ra[i][p];                                                                                  \
-        a_.x &= keep_.x; a_.y &= keep_.y; a_.z &= keep_.z; a_.w &= keep_.w;                                   \
-        As[row_ * XROW + p * 4 + XSLOT(row_, p_kg)] = a_;                                                     \
-        Bs[row_ * XROW + p * 4 + XSLOT(row_, p_kg)] = nok_ ? rb[i][p] : make_uint4(0u, 0u, 0u, 0u);           \
-      }                                                                                                       \
-    }                                                                                                         \
-  }
-
-  f32x16 acc[2][2];
-#pragma unroll
-  for (int ti = 0; ti < 2; ++ti)
-#pragma unroll
-    for (int tj = 0; tj < 2; ++tj)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[ti][tj][r] = 0.f;
-
-  const int wm = wave >> 1, wn = wave & 1, li = lane & 31, half = lane >> 5;
-
-  X6_LOAD_STAGE(0)
-  X6_STORE_STAGE(0)
-  __syncthreads();
-  for (int kt = 0; kt < nk; ++kt) {
-    if (kt + 1 < nk) X6_LOAD_STAGE((kt + 1) * 32)
-#pragma unroll
-    for (int s = 0; s < 2; ++s) {  // two 16-k MFMA steps per stage; this lane's 8 k's = group 2s + half
-      const int kg = 2 * s + half;
-      if constexpr (ONE) {
-        bf16x8 ah[2], bh[2];
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-          ah[t] = __builtin_bit_cast(bf16x8, As[(wm * 64 + t * 32 + li) * XROW + XSLOT(li, kg)]);
-          bh[t] = __builtin_bit_cast(bf16x8, Bs[(wn * 64 + t * 32 + li) * XROW + XSLOT(li, kg)]);
-        }
-#pragma unroll
-        for (int ti = 0; ti < 2; ++ti)
-#pragma unroll
-          for (int tj = 0; tj < 2; ++tj) acc[ti][tj] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bh[tj], ah[ti], acc[ti][tj], 0, 0, 0);
-      } else {
-        bf16x8 ah[2], am[2], al[2], bh[2], bm[2], bl[2];
-#pragma unroll
-        for (int ti = 0; ti < 2; ++ti) {
-          const uint4* p = &As[(wm * 64 + ti * 32 + li) * XROW + XSLOT(li, kg)];
-          ah[ti] = __builtin_bit_cast(bf16x8, p[0]);
-          am[ti] = __builtin_bit_cast(bf16x8, p[4]);
-          al[ti] = __builtin_bit_cast(bf16x8, p[8]);
-        }
-#pragma unroll
-        for (int tj = 0; tj < 2; ++tj) {
-          const uint4* p = &Bs[(wn * 64 + tj * 32 + li) * XROW + XSLOT(li, kg)];
-          bh[tj] = __builtin_bit_cast(bf16x8, p[0]);
-          bm[tj] = __builtin_bit_cast(bf16x8, p[4]);
-          bl[tj] = __builtin_bit_cast(bf16x8, p[8]);
-        }
-        // swapped operands (B fragment in the A slot): the accumulator holds the transposed tile, so
-        // a lane owns 4 consecutive columns of one row.  Small terms first.  The six terms of one accumulator are written back to
-        // back (hipcc alternates between two accumulators); letting the four accumulators take turns instead measured equal
-        // (profiles/r04y_term_major.log): a dependent MFMA two issue slots later does not stall
-#pragma unroll
-        for (int ti = 0; ti < 2; ++ti)
-#pragma unroll
-          for (int tj = 0; tj < 2; ++tj) {
-            f32x16 a = acc[ti][tj];
-            a = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bm[tj], am[ti], a, 0, 0, 0);
-            a = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bl[tj], ah[ti], a, 0, 0, 0);
-            a = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bh[tj], al[ti], a, 0, 0, 0);
-            a = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bm[tj], ah[ti], a, 0, 0, 0);
-            a = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bh[tj], am[ti], a, 0, 0, 0);
-            a = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bh[tj], ah[ti], a, 0, 0, 0);
-            acc[ti][tj] = a;
-          }
-      }
-    }
-    __syncthreads();
-    if (kt + 1 < nk) {
-      X6_STORE_STAGE((kt + 1) * 32)
-      __syncthreads();
-    }
-  }
-
-  // The accumulator layout gives a lane 4 consecutive columns of one row, a wave-wide store 64 pieces of 16 B on 32 different
-  // rows: 32-byte segments.  The tile goes through LDS instead (per wave [32 rows][64 + 4] fp32, the operand images are dead
-  // after the last stage's barrier) and leaves as whole 256-byte row pieces, 16 lanes per piece: measured on the node
-  // update's backward kernel (same layout, csrc/bl_node_bwd.hip), the direct form cost 2-3x the time of its bytes.
-  float* stage = reinterpret_cast<float*>(ABs) + wave * (32 * 68);
-  float4 csum = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-  for (int ti = 0; ti < 2; ++ti) {
-    const int m = wm * 64 + ti * 32 + li;
-#pragma unroll
-    for (int tj = 0; tj < 2; ++tj)
-#pragma unroll
-      for (int gq = 0; gq < 4; ++gq) {
-        const int n = n0 + wn * 64 + tj * 32 + 8 * gq + 4 * half;
-        float v[4] = {acc[ti][tj][4 * gq + 0], acc[ti][tj][4 * gq + 1], acc[ti][tj][4 * gq + 2], acc[ti][tj][4 * gq + 3]};
-        if (E_ACT) {
-          float4 bv = make_float4(0.f, 0.f, 0.f, 0.f);
-          if (epi.bias && n < N) bv = *reinterpret_cast<const float4*>(epi.bias + n);
-          v[0] += bv.x; v[1] += bv.y; v[2] += bv.z; v[3] += bv.w;
-#pragma unroll
-          for (int u = 0; u < 4; ++u) {
-            v[u] = bl_act(ACT, v[u]);
-            if (epi.drop_thresh) {  // same counter as the fp32 row GEMM: element index row * N + column
-              const uint32_t idx = (uint32_t)(row0 + m) * (uint32_t)N + (uint32_t)(n + u);
-              v[u] = ((bl_lowbias32(idx + epi.drop_key) >> 8) >= epi.drop_thresh) ? v[u] * epi.drop_scale : 0.f;
-            }
-          }
-        }
-        *reinterpret_cast<float4*>(stage + li * 68 + tj * 32 + 8 * gq + 4 * half) = make_float4(v[0], v[1], v[2], v[3]);
-      }
-    // (a wave reads back only what it wrote itself; its LDS operations execute in order)
-    const int c4 = lane & 15, n = n0 + wn * 64 + 4 * c4;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const int r = (lane >> 4) + 4 * j;
-      const int mm = wm * 64 + ti * 32 + r;
-      float4 v = *reinterpret_cast<const float4*>(stage + r * 68 + 4 * c4);
-      if (mm < nrows && n < N) {
-        const size_t grow = (size_t)(row0 + mm);
-        if (E_RES) {
-          const float4 rv = *reinterpret_cast<const float4*>(epi.res + grow * epi.ld_res + n);
-          v.x += rv.x; v.y += rv.y; v.z += rv.z; v.w += rv.w;
-        }
-        if (E_MASK) {  // y = drop(relu(z)) != 0  <=>  kept and z > 0: the hi plane of a non-zero fp32 is non-zero
-          const uint2 hm = epi.himask[(grow * 3 * N + n) >> 2];
-          v.x = (hm.x & 0x7fffu) ? v.x * epi.mask_scale : 0.f;
-          v.y = (hm.x & 0x7fff0000u) ? v.y * epi.mask_scale : 0.f;
-          v.z = (hm.y & 0x7fffu) ? v.z * epi.mask_scale : 0.f;
-          v.w = (hm.y & 0x7fff0000u) ? v.w * epi.mask_scale : 0.f;
-          csum.x += v.x; csum.y += v.y; csum.z += v.z; csum.w += v.w;
-        }
-        if (E_PACK) {
-          uint16_t h[4], m[4], l[4];
-          split3(v.x, h[0], m[0], l[0]);
-          split3(v.y, h[1], m[1], l[1]);
-          split3(v.z, h[2], m[2], l[2]);
-          split3(v.w, h[3], m[3], l[3]);
-          uint2* o = epi.c_packed + ((grow * 3 * N + n) >> 2);
-          o[0] = make_uint2(PK(h[0], h[1]), PK(h[2], h[3]));
-          o[N >> 2] = make_uint2(PK(m[0], m[1]), PK(m[2], m[3]));
-          o[N >> 1] = make_uint2(PK(l[0], l[1]), PK(l[2], l[3]));
-        } else {
-          *reinterpret_cast<float4*>(c + grow * ldc + n) = v;
-        }
-      }
-    }
-  }
-  if (E_MASK) {  // column sums of this wave's 64 x 64 block: over the four row groups of the lanes, then one atomic per column
-    csum.x += __shfl_xor(csum.x, 16, 64); csum.y += __shfl_xor(csum.y, 16, 64); csum.z += __shfl_xor(csum.z, 16, 64); csum.w += __shfl_xor(csum.w, 16, 64);
-    csum.x += __shfl_xor(csum.x, 32, 64); csum.y += __shfl_xor(csum.y, 32, 64); csum.z += __shfl_xor(csum.z, 32, 64); csum.w += __shfl_xor(csum.w, 32, 64);
-    const int n = n0 + wn * 64 + 4 * (lane & 15);
-    if (lane < 16 && n < N && epi.colsum) {
-      unsafeAtomicAdd(epi.colsum + n, csum.x);
-      unsafeAtomicAdd(epi.colsum + n + 1, csum.y);
-      unsafeAtomicAdd(epi.colsum + n + 2, csum.z);
-      unsafeAtomicAdd(epi.colsum + n + 3, csum.w);
-    }
-  }
+  gemm_rows_body<SplitBf16x3, MASKED, EPI, ONE>(xp0, xp1, xp2, idx0, idx1, idx2, w0, w1, w2, koff1, koff2, nsrc, win_bits, ld_bits, bp,
+                                                strideB, group_ptr, group_w, G, M, N, K, c, ldc, xcd_remap, epi, 1.f, nullptr);
 }
-
-#undef XSLOT
 
 // ---- weight-gradient GEMM -------------------------------------------------------------------------
-// gW_g[i, n] += sum_{e in group g} A[e, i] * Gr[e, n]     A = gathered packed rows (h[src] | h[tgt]),
-//                                                          Gr[e, :] = g_node[g_idx[e], :] where winner == e
-// The contraction runs over MESSAGES, but the bf16 MFMA wants 8 consecutive k's of one row in a
-// lane: the operands have to be transposed on the way.  Both tiles are stored in LDS exactly as
-// they arrive -- [plane][message][feature], feature-contiguous rows of 320 B -- and the fragments are
-// read with ds_read_b64_tr_b16, gfx950's transposing LDS read: a 16-lane group reads a
-// [4 messages][16 features] block (lane 4j+q supplies the address of message j, features 4q..4q+3)
-// and lane i receives the 4 messages of feature i.  Two reads = the 8 k's of one MFMA operand.
-// Row stride 320 B puts the 4 message rows of a block 16 banks apart: conflict-free.
-// Global loads are full 256-byte plane rows (16 lanes x 16 B per message and plane).
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef short s16x8 __attribute__((ext_vector_type(8)));
-#define WRS 160                 // shorts per LDS message row (128 features + 32 pad)
-#define WPLANE (32 * WRS)       // shorts per plane (32 messages)
-#define WOPER (3 * WPLANE)      // shorts per operand image
-
-__device__ __forceinline__ bf16x8 tr_frag(const short* p) {
-  typedef s16x4 __attribute__((address_space(3))) * lds_s16x4_ptr;
-  const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(p));
-  const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(p + 4 * WRS));
-  return __builtin_bit_cast(bf16x8, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
-}
-
-// ONE: the high planes only (bl_set_seq_gemm_mode(1)), as in gemm_rows_x6_kernel
+// gemm_wgrad_body (bl_gemm_split.h) on the three-plane bf16 split
 template <bool ROUTED, bool ONE>
 __global__ __launch_bounds__(256, 2) void gemm_wgrad_x6_kernel(
     const uint4* __restrict__ xp0, const uint4* __restrict__ xp1, const uint4* __restrict__ xp2,
@@ -447,153 +150,9 @@ __global__ __launch_bounds__(256, 2) void gemm_wgrad_x6_kernel(
     const uint32_t* __restrict__ win_bits, int ld_bits, const int* __restrict__ group_ptr, const int* __restrict__ group_w, int G,
     int M, int N, int K, int kchunk, float* __restrict__ gw_base, long long strideW, int ldw, int ntiles_n, int xcd_remap,
     unsigned* __restrict__ order_ctr) {
-  constexpr int NP = ONE ? 1 : 3;
-  __shared__ __attribute__((aligned(16))) short As[NP * WPLANE];
-  __shared__ __attribute__((aligned(16))) short Bs[NP * WPLANE];
-
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  int g, e0, ne, tile_y;
-  if (!x6_locate(group_ptr, G, M, kchunk, xcd_remap, tile_y, g, e0, ne)) return;
-  const int e1 = e0 + ne;
-  const int i0 = (tile_y / ntiles_n) * XBM;
-  const int n0 = (tile_y % ntiles_n) * XBN;
-  const int wsel = group_w ? group_w[g] : g;
-
-  // loader: units (message, 8-feature group); unit u = tid + 256 i -> message u >> 4, group u & 15
-  const int fg = tid & 15, msg0 = tid >> 4;  // messages msg0 and msg0 + 16
-  const int fi = i0 + 8 * fg, nn = n0 + 8 * fg;
-  const bool a_ok = fi < K, b_ok = nn < N;
-  const int fic = a_ok ? fi : 0, nnc = b_ok ? nn : 0;
-  int aj = 0;
-  if (nsrc > 1 && fic >= koff1) aj = 1;
-  if (nsrc > 2 && fic >= koff2) aj = 2;
-  const uint4* __restrict__ abase = (aj == 0 ? xp0 : (aj == 1 ? xp1 : xp2)) + ((fic - (aj == 0 ? 0 : (aj == 1 ? koff1 : koff2))) >> 3);
-  const int* __restrict__ aidx = aj == 0 ? idx0 : (aj == 1 ? idx1 : idx2);
-  const int awg = (aj == 0 ? w0 : (aj == 1 ? w1 : w2)) >> 3;  // uint4 per plane of an A row
-  const int gwg = N >> 3;                                      // uint4 per plane of a G row
-  const uint4* __restrict__ gbase = gp + (nnc >> 3);
-  const uint32_t* __restrict__ mbase = ROUTED ? win_bits + (nnc >> 5) : nullptr;
-  const int mshift = nnc & 31;
-
-  uint4 ra[2][NP], rb[2][NP];
-  uint32_t mk[2];
-  int arow[2], grow[2], mrow[2];  // gathered rows / message ids of the NEXT stage to load
-
-#define WX6_LOAD_IDX(k0_)                                          \
-  {                                                                \
-    _Pragma("unroll") for (int i = 0; i < 2; ++i) {                \
-      const int e_ = (k0_) + msg0 + 16 * i;                        \
-      const int ec_ = e_ < e1 ? e_ : e0;                           \
-      arow[i] = aidx ? aidx[ec_] : ec_;                            \
-      grow[i] = g_idx ? g_idx[ec_] : ec_;                          \
-      mrow[i] = ec_;                                               \
-    }                                                              \
-  }
-#define WX6_LOAD_STAGE()                                                                         \
-  {                                                                                              \
-    _Pragma("unroll") for (int i = 0; i < 2; ++i) {                                              \
-      const uint4* a_ = abase + (size_t)arow[i] * 3 * awg;                                       \
-      ra[i][0] = a_[0];                                                                          \
-      if constexpr (!ONE) {                                                                      \
-        ra[i][1] = a_[awg];                                                                      \
-        ra[i][2] = a_[2 * awg];                                                                  \
-      }                                                                                          \
-      const uint4* g_ = gbase + (size_t)grow[i] * 3 * gwg;                                       \
-      rb[i][0] = g_[0];                                                                          \
-      if constexpr (!ONE) {                                                                      \
-        rb[i][1] = g_[gwg];                                                                      \
-        rb[i][2] = g_[2 * gwg];                                                                  \
-      }                                                                                          \
-      mk[i] = ROUTED ? mbase[(size_t)mrow[i] * ld_bits] : 0u;                                    \
-    }                                                                                            \
-  }
-#define WX6_STORE_STAGE(k0_)                                                                     \
-  {                                                                                              \
-    _Pragma("unroll") for (int i = 0; i < 2; ++i) {                                              \
-      const int eid_ = (k0_) + msg0 + 16 * i;                                                    \
-      const bool eok_ = eid_ < e1;                                                               \
-      uint4 keep_ = ROUTED ? keep_from_bits(mk[i] >> mshift) : make_uint4(~0u, ~0u, ~0u, ~0u);   \
-      if (!(eok_ && b_ok)) keep_ = make_uint4(0u, 0u, 0u, 0u);                                   \
-      const int slot_ = (msg0 + 16 * i) * WRS + 8 * fg;                                          \
-      _Pragma("unroll") for (int p = 0; p < NP; ++p) {                                           \
-        *reinterpret_cast<uint4*>(&As[p * WPLANE + slot_]) = (eok_ && a_ok) ? ra[i][p] : make_uint4(0u, 0u, 0u, 0u); \
-        uint4 b_ = rb[i][p];                                                                     \
-        b_.x &= keep_.x; b_.y &= keep_.y; b_.z &= keep_.z; b_.w &= keep_.w;                      \
-        *reinterpret_cast<uint4*>(&Bs[p * WPLANE + slot_]) = b_;                                 \
-      }                                                                                          \
-    }                                                                                            \
-  }
-
-  f32x16 acc[2][2];
-#pragma unroll
-  for (int ti = 0; ti < 2; ++ti)
-#pragma unroll
-    for (int tj = 0; tj < 2; ++tj)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[ti][tj][r] = 0.f;
-
-  const int wm = wave >> 1, wn = wave & 1, li = lane & 31, half = lane >> 5;
-  // transposing-read address of this lane inside a [32 messages][WRS] plane, tile feature base 0
-  const int l16 = lane & 15, grp = lane >> 4;
-  const int tr_off = ((grp >> 1) * 8 + (l16 >> 2)) * WRS + (grp & 1) * 16 + 4 * (l16 & 3);
-  const short* a_tr = As + tr_off + wm * 64;
-  const short* b_tr = Bs + tr_off + wn * 64;
-  const int nk = (ne + 31) / 32;
-
-  WX6_LOAD_IDX(e0)
-  WX6_LOAD_STAGE()
-  WX6_LOAD_IDX(e0 + 32)
-  WX6_STORE_STAGE(e0)
-  __syncthreads();
-  for (int kt = 0; kt < nk; ++kt) {
-    if (kt + 1 < nk) {
-      WX6_LOAD_STAGE()
-      WX6_LOAD_IDX(e0 + (kt + 2) * 32)
-    }
-#pragma unroll
-    for (int s = 0; s < 2; ++s) {  // two 16-message MFMA steps per stage
-      bf16x8 af[2][NP], bf[2][NP];
-#pragma unroll
-      for (int t = 0; t < 2; ++t)
-#pragma unroll
-        for (int p = 0; p < NP; ++p) {
-          af[t][p] = tr_frag(a_tr + p * WPLANE + s * 16 * WRS + t * 32);
-          bf[t][p] = tr_frag(b_tr + p * WPLANE + s * 16 * WRS + t * 32);
-        }
-#define WX6_TERM(pa_, pb_)                                                                            \
-  _Pragma("unroll") for (int ti = 0; ti < 2; ++ti) _Pragma("unroll") for (int tj = 0; tj < 2; ++tj)   \
-      acc[ti][tj] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[ti][pa_], bf[tj][pb_], acc[ti][tj], 0, 0, 0);
-      if constexpr (ONE) {
-        WX6_TERM(0, 0)
-      } else {
-        WX6_TERM(1, 1) WX6_TERM(2, 0) WX6_TERM(0, 2) WX6_TERM(1, 0) WX6_TERM(0, 1) WX6_TERM(0, 0)
-      }
-    }
-    __syncthreads();
-    if (kt + 1 < nk) {
-      WX6_STORE_STAGE(e0 + (kt + 1) * 32)
-      __syncthreads();
-    }
-  }
-
-  float* __restrict__ gw = gw_base + (long long)wsel * strideW;
-  // deterministic mode (launched without the XCD remap): the message chunks of one (group, tile) add in chunk order
-  unsigned* ctr = order_ctr ? order_ctr + (size_t)g * gridDim.y + tile_y : nullptr;
-  const unsigned turn = (unsigned)((e0 - (group_ptr ? group_ptr[g] : 0)) / kchunk);
-  bl_ordered_enter(ctr, turn);
-#pragma unroll
-  for (int ti = 0; ti < 2; ++ti)
-#pragma unroll
-    for (int tj = 0; tj < 2; ++tj) {
-      const int n = n0 + wn * 64 + tj * 32 + li;
-      if (n >= N) continue;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int f = i0 + wm * 64 + ti * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
-        if (f < K) unsafeAtomicAdd(&gw[(size_t)f * ldw + n], acc[ti][tj][r]);
-      }
-    }
-  bl_ordered_leave(ctr, turn);
+  gemm_wgrad_body<SplitBf16x3, ROUTED, ONE>(xp0, xp1, xp2, idx0, idx1, idx2, w0, w1, w2, koff1, koff2, nsrc, gp, g_idx, win_bits, ld_bits,
+                                            group_ptr, group_w, G, M, N, K, kchunk, gw_base, strideW, ldw, ntiles_n, xcd_remap, order_ctr,
+                                            1.f, nullptr);
 }
 
 // ---- weight-gradient GEMM, wide tile ---------------------------------------------------------------
@@ -783,7 +342,9 @@ __global__ __launch_bounds__(512) void gemm_wgrad_x6_wide_kernel(
 // (WW_S staging piece, WW_T six-term MFMA group, WW_F fragment reads: the ablation / trace builds that blank them out one at a
 // time are made from tools/experiments/bl_gemm_x6_switches.hip, profiles/r04d_wgrad_ablation.log)
 #define WW_S(x_) x_
-#define WW_T(pa_, pb_) WX6_TERM(pa_, pb_)
+#define WW_T(pa_, pb_)                                                                                \
+  _Pragma("unroll") for (int ti = 0; ti < 2; ++ti) _Pragma("unroll") for (int tj = 0; tj < 2; ++tj)   \
+      acc[ti][tj] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[ti][pa_], bf[tj][pb_], acc[ti][tj], 0, 0, 0);
 #define WW_F(rd_, s_) WW_FRAGS(rd_, s_)
 #define WW_ITER(X, Y, KT)                                                                              \
   {                                                                                                    \
@@ -940,15 +501,11 @@ int gemm_rows_x6_impl(const char* who, const bl_rows_packed_t* a, const uint32_t
   const bool one = bl_seq_gemm_mode() == 1;
   if (M == 0) return BL_OK;
   BlPackedRows r;
-  if (int rc = bl_packed_rows(who, a, K, r)) return rc;
-  BL_CHECK_ARG(M > 0 && N > 0 && N % 4 == 0 && ldc % 4 == 0 && bp && c && bl_aligned16(bp) && bl_aligned16(c),
-               "%s: N/ldc multiples of 4, aligned pointers required", who);
+  dim3 grid;
+  if (int rc = bl_rows_gemm_plan(who, a, win_bits, ld_bits, bp, group_ptr, G, M, N, K, c, ldc, XBM, r, grid)) return rc;
   BL_CHECK_ARG(b_group_stride % 8 == 0 && (G <= 1 || b_group_stride >= (int64_t)((N + 127) / 128) * (K / 32) * 12288),
                "%s: packed group stride must cover one group's tiled weights (bl_pack_weights_x6)", who);
-  BL_CHECK_ARG(win_bits == nullptr || (a->nsrc == 1 && a->idx[0] && ld_bits * 32 >= K),
-               "%s: the routed form needs exactly one gathered source and ld_bits >= K / 32", who);
   BL_CHECK_ARG(!(win_bits && epi), "%s: the routed form has no epilogue", who);
-  dim3 grid((M + XBM - 1) / XBM + (group_ptr ? G : 0), (N + XBN - 1) / XBN);
   const int xcd = 1;  // XCD-contiguous tile order (x6_locate)
   X6Epi e = {nullptr, BL_ACT_NONE, 0u, 0u, 1.f, 0, nullptr, 0, nullptr, 1.f, nullptr, nullptr};
   if (epi) e = *epi;
@@ -991,17 +548,7 @@ int gemm_rows_x6_impl(const char* who, const bl_rows_packed_t* a, const uint32_t
   return BL_OK;
 }
 
-}  // namespace
-extern int g_h3_kchunk_cap;  // csrc/bl_gemm_h3.hip
-namespace {
 bool g_wgrad_wide = true;  // bl_set_wgrad_tile: A/B switch between the 256 x 128 and the 128 x 128 weight-gradient tile
-// Largest number of rows one workgroup reduces before it flushes its output tile (bl_set_wgrad_kchunk_cap).  Every flush is
-// tile-size fp32 atomics, and the chip retires ~312 G of those per second whatever the addresses (tools/atomic_bench.py):
-// at c2's layer shape (E = 640 000, K = 256, N = 128) the 864-row chunks of the old cap (1024) were 97 MB = 24 M atomics per
-// launch, ~0.08 ms of a 0.25-ms kernel; the cap trades that against the balance of the last round of workgroups.  Measured
-// (profiles/r04e_kcap_*.log, same box): H = 128 layer 0.254 / 0.232 / 0.210 / 0.220 / 0.217 ms at 1024 / 2048 / 3072 / 4096 /
-// 8192, concat layer 0.921 / 0.863 / 0.824 / 0.829 / 0.908 ms at 1024 / 2048 / 4096 / 8192 / 16384.
-int g_wgrad_kchunk_cap = 4096;
 
 // (a template, so that naming the kernel here does not instantiate it ahead of the dispatch chain: the chain orders the code object)
 template <bool ROUTED, bool ONE>
@@ -1035,15 +582,11 @@ int gemm_wgrad_x6_impl(const char* who, const bl_rows_packed_t* a, const uint16_
   // rows reduced by one workgroup: an integer number of rounds of resident workgroups (bl_wgrad_kchunk)
   const int resident = wide ? bl_num_cus() : (one ? (routed ? wgrad_x6_resident<true, true>() : wgrad_x6_resident<false, true>())
                                                         : (routed ? wgrad_x6_resident<true, false>() : wgrad_x6_resident<false, false>()));
-  const int ntiles_n = (N + XBN - 1) / XBN;
-  const int ntiles_all = ((K + (wide ? 255 : XBM - 1)) / (wide ? 256 : XBM)) * ntiles_n;
-  const int kchunk = bl_wgrad_kchunk(M, ntiles_all, (group_ptr ? G : 0) * ntiles_all, resident, g_wgrad_kchunk_cap);
-  dim3 grid((M + kchunk - 1) / kchunk + (group_ptr ? G : 0), ntiles_all);
-  unsigned* order_ctr = group_w ? nullptr : bl_order_counters((group_ptr ? G : 1) * ntiles_all, stream);
-  const int xcd = order_ctr ? 0 : 1;  // ordered flushes want "lower chunk = lower workgroup id"
+  const BlWgradPlan p = bl_wgrad_plan(group_ptr, group_w, G, M, N, K, wide ? 256 : XBM, XBN, resident, stream);
+  const dim3 grid = p.grid;
 #define WX6_ARGS                                                                                                              \
   BL_PACKED_ROWS_ARGS(r), reinterpret_cast<const uint4*>(g_packed), g_idx, win_bits, ld_bits, group_ptr, group_w, G, M, N, K, \
-      kchunk, gw, (long long)gw_group_stride, ld_gw, ntiles_n, xcd, order_ctr
+      p.kchunk, gw, (long long)gw_group_stride, ld_gw, p.ntiles_n, p.xcd, p.order_ctr
   if (wide && routed)
     hipLaunchKernelGGL((gemm_wgrad_x6_wide_kernel<true, true>), grid, dim3(512), 0, (hipStream_t)stream, WX6_ARGS);
   else if (wide && gather)
@@ -1071,11 +614,11 @@ extern "C" int32_t bl_set_wgrad_tile(int32_t rows) {
   return prev;
 }
 
-// Rows per workgroup of the bf16x6 weight-gradient GEMMs: the chunk is the smallest one that fills an integer number of rounds
+// Rows per workgroup of the weight-gradient GEMMs (both operand splits): the chunk is the smallest one that fills an integer number of rounds
 // of resident workgroups and is <= cap rows.  Returns the previous cap.
 extern "C" int32_t bl_set_wgrad_kchunk_cap(int32_t rows) {
   const int32_t prev = g_wgrad_kchunk_cap;
-  if (rows >= 256) g_wgrad_kchunk_cap = g_h3_kchunk_cap = rows;  // (the f16x3 weight gradient follows the same cap)
+  if (rows >= 256) g_wgrad_kchunk_cap = rows;
   return prev;
 }
 

@@ -596,3 +596,110 @@ def test_train_cli_with_amp_on_seq_great(ops, tmp_path):
     assert model_path.exists()
     _, nn_ = GnnBugLabModel.restore_model(model_path, torch.device("cuda"))
     assert all(bool(torch.isfinite(q).all()) for q in nn_.parameters())
+
+
+# ---- 6. the fp16 counterpart: the one-term forms of the f16x3 entry points ------------------------------------------------
+def _f16(bits: torch.Tensor) -> torch.Tensor:
+    """int16 fp16 bit patterns -> fp64"""
+    return bits.cpu().contiguous().view(torch.float16).double()
+
+
+def _weights_h3_plane0(image: torch.Tensor, G: int, K: int, N: int) -> torch.Tensor:
+    """high plane of bl_pack_weights_h3's image as fp64 [G, K, N], scale included (layout: csrc/bl_h3_image.h) -- per (group,
+    128-column tile, 32-k stage): [i 2][plane 2][row_lo 64][k-group 4] x 8, column 64 i + row_lo"""
+    nst, ntn = K // 32, (N + 127) // 128
+    t = _f16(image).view(G, ntn, nst, 2, 2, 64, 4, 8)[:, :, :, :, 0]  # [G, tile, stage, i, row_lo, k-group, 8]
+    return t.permute(0, 2, 5, 6, 1, 3, 4).reshape(G, K, ntn * 128)[:, :, :N]
+
+
+@pytest.fixture()
+def h1(ops):
+    prev = ops.set_msg_gemm_mode("f16x1")
+    try:
+        yield ops
+    finally:
+        ops.set_msg_gemm_mode(prev)
+    assert ops.msg_gemm_mode() == prev
+
+
+def _keep_of(bits: np.ndarray) -> torch.Tensor:
+    return torch.from_numpy(np.unpackbits(bits.view(np.uint8).reshape(bits.shape[0], -1), axis=1, bitorder="little").astype(np.float64))
+
+
+H3_SHAPES = [(M, K, N) for M in (1, 65, 129) for K in (32, 96) for N in (32, 96)]
+
+
+def test_h3_rows_one_term_matches_fp64_of_the_high_planes(h1):
+    """bl_gemm_rows_h3 in f16x1 against out_scale x the fp64 product of the decoded fp16 high planes (their scales are powers of
+    two, so they are in the planes and leave through out_scale exactly): every (rows, K, N) of the grid; two groups with one of
+    them empty on a gathered source; the routed form.  Products of two 11-bit significands are exact in fp32 and the accumulation
+    is fp32: the bound is _assert_within's."""
+    ops, rng = h1, np.random.default_rng(6)
+    out_scale = 1.0 / (ops.H3_ROW_SCALE * ops.H3_W_SCALE)
+
+    def case(M, K, N, *, sizes=None, gather=False, routed=False):
+        G = len(sizes) if sizes else 1
+        R = 37 if gather else max(M, 8)
+        x = torch.from_numpy(rng.standard_normal((R, K)).astype(np.float32))
+        W = torch.from_numpy((rng.standard_normal((G, K, N)) / math.sqrt(K)).astype(np.float32))
+        xp, image = ops.pack_f16x2(x.cuda()), ops.pack_weights_h3(W.cuda(), True)
+        idx = rng.integers(0, R, M).astype(np.int32) if gather else None
+        A = _f16(xp[:, :K])
+        A = A[torch.from_numpy(idx.astype(np.int64))] if gather else A[:M]
+        bits = None
+        if routed:
+            bits = rng.integers(-2 ** 31, 2 ** 31, (M, K // 32)).astype(np.int32)
+            bits[::7] = 0
+            A = A * _keep_of(bits)
+        B = _weights_h3_plane0(image, G, K, N)
+        ptr = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int32) if sizes else np.array([0, M], dtype=np.int32)
+        ref, mag = torch.zeros(M, N, dtype=torch.float64), torch.zeros(M, N, dtype=torch.float64)
+        for g in range(G):
+            lo, hi = int(ptr[g]), int(ptr[g + 1])
+            ref[lo:hi] = (A[lo:hi] @ B[g]) * out_scale
+            mag[lo:hi] = (A[lo:hi].abs() @ B[g].abs()) * out_scale
+        got = ops.gemm_rows_h3([(xp, _dev(idx) if gather else None, K)], image, M, N, out_scale=out_scale,
+                               group_ptr=_dev(ptr) if sizes else None, G=G, win_bits=_dev(bits) if routed else None)
+        _assert_within(got, ref, mag, K, ("h3 rows", M, K, N, sizes, gather, routed))
+
+    for M, K, N in H3_SHAPES:
+        case(M, K, N)
+    for sizes in ((0, 65), (129, 0)):
+        case(sum(sizes), 96, 96, sizes=sizes, gather=True)
+    for M, K, N in H3_SHAPES:
+        case(M, K, N, gather=True, routed=True)
+
+
+def test_h3_weight_gradient_one_term_matches_fp64_of_the_high_planes(h1):
+    """bl_gemm_wgrad_h3 in f16x1: gw[g] = out_scale x rows^T . G rows over groups of 1, 65 and 129 rows (the contraction length of
+    the bound), plain (direct rows) and routed (both sides gathered, the gradient rows masked by the winner bits), K and N in
+    {32, 96} -- the smallest the argument checks admit.  gw starts at zero and every group is one chunk, so the flush adds no
+    rounding of its own."""
+    ops, rng = h1, np.random.default_rng(7)
+    sizes = (1, 65, 129)
+    M, G = sum(sizes), len(sizes)
+    ptr = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int32)
+    g_scale = 1024.0
+    out_scale = 1.0 / (ops.H3_ROW_SCALE * g_scale)
+    for K in (32, 96):
+        for N in (32, 96):
+            for routed in (False, True):
+                R = 50 if routed else M
+                x = torch.from_numpy(rng.standard_normal((R, K)).astype(np.float32))
+                gz = torch.from_numpy(rng.standard_normal((R, N)).astype(np.float32))
+                xp, gp = ops.pack_f16x2(x.cuda()), ops.pack_f16x2(gz.cuda(), g_scale)
+                A, Gr = _f16(xp[:, :K]), _f16(gp[:, :N])
+                ia = ig = bits = None
+                if routed:
+                    ia, ig = rng.integers(0, R, M).astype(np.int32), rng.integers(0, R, M).astype(np.int32)
+                    bits = rng.integers(-2 ** 31, 2 ** 31, (M, N // 32)).astype(np.int32)
+                    bits[::7] = 0
+                    A, Gr = A[torch.from_numpy(ia.astype(np.int64))], Gr[torch.from_numpy(ig.astype(np.int64))] * _keep_of(bits)
+                gw = torch.zeros((G, K, N), device="cuda")
+                ops.gemm_wgrad_h3([(xp, _dev(ia) if routed else None, K)], gp, M, N, gw, out_scale=out_scale, g_idx=_dev(ig) if routed else None,
+                                  win_bits=_dev(bits) if routed else None, gw_group_stride=K * N, group_ptr=_dev(ptr), G=G)
+                for g, rows in enumerate(sizes):
+                    lo, hi = int(ptr[g]), int(ptr[g + 1])
+                    ref = (A[lo:hi].T @ Gr[lo:hi]) * out_scale
+                    mag = (A[lo:hi].abs().T @ Gr[lo:hi].abs()) * out_scale
+                    _assert_within(gw[g], ref, mag, rows, ("h3 wgrad", K, N, routed, rows))
