@@ -827,6 +827,40 @@ int bl_eval_judge(const float* src, int64_t n_src, const int32_t* loc_idx, const
                   int64_t capacity, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Confidence calibration (buglab/models/calibrate.py), in csrc/bl_confidence.hip.  BEYOND THE REFERENCE: it has no
+ * counterpart; what is calibrated is the confidence its evaluate.py:60-140 thresholds and its visualize.py ranks by.  One
+ * inverse temperature beta and a NO_BUG bias rescale the localization distribution, one repair_beta the repair groups:
+ *   z_i = beta * l_i (+ bias on NO_BUG);  l'_i = log_softmax(z)_i = (z_i - m) - log1p(sum over i != i_m of exp(z_i - m)),
+ * m = z's first maximum, at i_m.  fp64 throughout, compiled without fused multiply-adds; buglab/models/_calibrate.py is the
+ * same arithmetic in NumPy.  Entries that are not above -inf have probability 0: they enter no maximum and no sum.
+ *
+ * bl_conf_loc_stats: a POOL of nseg location segments, segment s = vals[seg_off[s] : seg_off[s + 1]] (fp32 log-probabilities,
+ *   offsets clamped to [0, n_vals]), NO_BUG at its last place, the target at place tgt[s] of the segment.  With
+ *   F(beta, bias) = - sum_s l'_s[tgt[s]]:  out[0..5] = F, dF/dbeta, dF/dbias, d2F/dbeta2, d2F/dbeta dbias, d2F/dbias2.
+ *   Per segment (E = sum_i p_i l_i, p = exp(l'), p_nb = NO_BUG's):  log1p(Z') + (m - z_tgt) | E - l_tgt | p_nb - [tgt is NO_BUG] |
+ *   sum_i p_i (l_i - E)^2 | p_nb (l_nb - E) | p_nb (1 - p_nb).  An empty segment contributes 0; a segment with nothing above
+ *   -inf or a target outside it contributes NaN.
+ * bl_conf_group_stats: the same over nseg repair groups with one scale and no bias: out[0..2] = F_r, F_r', F_r''.
+ *   Both: one wave per segment, lanes stride over it (any length); the segments' terms are written to partials
+ *   ([6, nseg] / [3, nseg] doubles, the caller's) and a second kernel sums each column in an order fixed by nseg alone: no
+ *   atomics, bit-identical from launch to launch.  nseg == 0 writes zeros.  No synchronisation.
+ *
+ * bl_conf_apply: a predict minibatch's flat output [loc | text | var | swap] (n_flat floats) IN PLACE.  Sample b < B owns
+ *   flat[candidate_ptr[b] : candidate_ptr[b + 1]] (clamped to [0, C]) and its NO_BUG entry flat[C + b]: they become l'.
+ *   Repair group g < G owns flat[item_base + group_items[k]] for k in group_ptr[g] : group_ptr[g + 1] (the CSR the model's own
+ *   log-softmax runs over; items outside [0, n_items) are left out): they become log_softmax(repair_beta * r).  Every entry
+ *   belongs to at most one segment.  Rounded once to fp32; -inf stays -inf.  B == 0 / G == 0 leave that part untouched.
+ * BL_EINVAL: null pointers, negative sizes, a scale that is not finite and > 0, a bias that is not finite, C + B > n_flat,
+ * item_base + n_items > n_flat.  BL_ERANGE: n_vals / n_flat beyond int32. */
+int bl_conf_loc_stats(const float* vals, int64_t n_vals, const int32_t* seg_off, const int32_t* tgt, int32_t nseg, double beta,
+                      double bias, double* partials, double* out, void* stream);
+int bl_conf_group_stats(const float* vals, int64_t n_vals, const int32_t* seg_off, const int32_t* tgt, int32_t nseg, double beta,
+                        double* partials, double* out, void* stream);
+int bl_conf_apply(float* flat, int64_t n_flat, const int32_t* candidate_ptr, int32_t B, int64_t C, const int32_t* group_ptr,
+                  const int32_t* group_items, int32_t G, int64_t n_items, int64_t item_base, double beta, double bias,
+                  double repair_beta, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Near-duplicate detection (buglab/data/deduplication/index.py:15-70: `DuplicationIndex.check_if_duplicate_and_add`, which
  * updates a 256-permutation MinHash one token at a time and keeps one Python dict per LSH band), in csrc/bl_dedup.hip.  The
  * arithmetic is the written specification of DESIGN.md "Near-duplicate detection"; all of it is integer work and every result is

@@ -110,13 +110,17 @@ def prediction_minibatches(model, tagged: Iterable[Tuple[Any, Any]], device, par
 
 def flat_prediction_output(trained_nn, mb_data) -> torch.Tensor:
     """The forward of the model's own `predict` (gnn.py / seqmodel.py) -> its flat fp32 output [loc | text | var | swap],
-    left on the device."""
+    left on the device; calibrated there (hip_ops.conf_apply) when the model carries a `confidence_calibration`."""
     _, loc_lp, enc_out, _ = trained_nn.compute_localization_logprobs(mb_data["graph_data"])
     swap_lp, text_lp, var_lp, _ = trained_nn._compute_repair_logprobs(
         enc_out, mb_data["target_rewrites"], mb_data["rewrite_to_location_group"], mb_data["candidate_symbol_to_location_group"],
         mb_data["swapped_pair_to_call_location_group"], mb_data["repair_group_ptr"], mb_data["repair_group_items"])
     flat = torch.cat([t.detach().reshape(-1).float() for t in (loc_lp, text_lp, var_lp, swap_lp)])
     assert flat.shape[0] == mb_data["prediction_layout"].flat_size
+    if mb_data.get("confidence_calibration") is not None:  # the model's own, put there by `_finalize_prediction_minibatch`
+        from buglab.models._calibrate import apply_to_flat
+
+        apply_to_flat(mb_data["confidence_calibration"], flat, mb_data)
     return flat
 
 

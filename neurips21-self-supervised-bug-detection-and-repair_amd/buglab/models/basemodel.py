@@ -50,6 +50,17 @@ class AbstractBugLabModel:
             self._tensorize_only_at_target_location_rewrites = True
 
     # -------------------------------------------------------------------------------------------
+    @property
+    def confidence_calibration(self):
+        """The `ConfidenceCalibration` fitted by buglab/models/calibrate.py (beyond the reference), or None: `predict` and the
+        services' `flat_prediction_output` then report calibrated log-probabilities.  Pickled with the model; a checkpoint
+        written before the field existed has none."""
+        return getattr(self, "_confidence_calibration", None)
+
+    @confidence_calibration.setter
+    def confidence_calibration(self, value) -> None:
+        self._confidence_calibration = value
+
     def _compute_rewrite_data(self, datapoint, candidate_node_idxs: Sequence[int]):
         """Same 16-tuple as reference basemodel.py:80-238.
 
@@ -126,6 +137,8 @@ class AbstractBugLabModel:
         layout = prediction_layout(mb)
         out = to_device(mb, device)
         out["prediction_layout"] = layout
+        if self.confidence_calibration is not None:
+            out["confidence_calibration"] = self.confidence_calibration
         return out
 
     def _iter_per_sample_results(self, mb_data, candidate_location_sample_idx, candidate_location_log_probs,
@@ -146,9 +159,15 @@ class AbstractBugLabModel:
         if all(hasattr(t, "detach") for t in parts):
             import torch
 
-            flat = torch.cat([t.detach().reshape(-1).float() for t in parts]).cpu().numpy()
+            flat = torch.cat([t.detach().reshape(-1).float() for t in parts])
+            if mb_data.get("confidence_calibration") is not None:
+                from buglab.models._calibrate import apply_to_flat
+
+                apply_to_flat(mb_data["confidence_calibration"], flat, mb_data)
+            flat = flat.cpu().numpy()
         else:
             flat = np.concatenate([to_np(t).reshape(-1).astype(np.float32) for t in parts])
+            assert mb_data.get("confidence_calibration") is None, "calibrated models predict from tensors"
         assert flat.shape[0] == layout.flat_size
         loc_all, rw_all = flat[layout.loc_idx].tolist(), flat[layout.rw_idx].tolist()
         assert layout.num_samples == num_samples

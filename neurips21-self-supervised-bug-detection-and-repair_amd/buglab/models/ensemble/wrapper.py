@@ -236,6 +236,10 @@ class EnsembleWrapper:
             raise ValueError(f"{len(self._models)} ensemble members but {len(nns)} modules")
         for n in nns:
             n.eval()
+        if not getattr(self, "_calibration_notice_given", False) and any(
+                getattr(m, "confidence_calibration", None) is not None for m in self._models):
+            self._calibration_notice_given = True  # once per wrapper
+            LOGGER.info("Ensemble members carry a confidence calibration; the ensemble combines their uncalibrated values.")
         with torch.no_grad(), ExitStack() as stack:
             for m in self._models:
                 stack.enter_context(m._tensorize_all_location_rewrites())

@@ -196,6 +196,10 @@ _SIGNATURES = {
     "bl_report_order": ([c_void_p, c_void_p, c_int64, c_int64, c_int32, c_void_p, c_void_p, c_void_p], ctypes.c_int),
     "bl_eval_judge": ([c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int32,
                        c_int32, c_void_p, c_void_p, c_int64, c_int64, c_void_p], ctypes.c_int),
+    "bl_conf_loc_stats": ([c_void_p, c_int64, c_void_p, c_void_p, c_int32, c_double, c_double, c_void_p, c_void_p, c_void_p], ctypes.c_int),
+    "bl_conf_group_stats": ([c_void_p, c_int64, c_void_p, c_void_p, c_int32, c_double, c_void_p, c_void_p, c_void_p], ctypes.c_int),
+    "bl_conf_apply": ([c_void_p, c_int64, c_void_p, c_int32, c_int64, c_void_p, c_void_p, c_int32, c_int64, c_int64, c_double, c_double,
+                       c_double, c_void_p], ctypes.c_int),
     "bl_dedup_sha1_u32": ([c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p], ctypes.c_int),
     "bl_dedup_minhash": ([c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int32, c_void_p, c_void_p], ctypes.c_int),
     "bl_dedup_lsh_insert_query": ([c_void_p, c_int32, c_int32, c_int32, c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p,

@@ -1,5 +1,5 @@
-"""Forward-only device services: ensemble combine, self-supervision scoring / sampling, bug reports, evaluation, near-duplicate
-detection."""
+"""Forward-only device services: ensemble combine, self-supervision scoring / sampling, bug reports, evaluation, confidence
+calibration, near-duplicate detection."""
 from __future__ import annotations
 
 from typing import Optional, Tuple
@@ -10,7 +10,7 @@ from ._cabi import _check, _f32, _i32, load_library, _p, _req, _stream
 
 __all__ = ["ENSEMBLE_KINDS", "ENSEMBLE_MAX_MEMBERS", "ensemble_combine", "SELECTOR_MAX_K", "_f64", "score_targets",
            "selector_sample", "REPORT_MAX_SAMPLES", "REPORT_INDEX_FIELDS", "report_summarize", "report_order", "EVAL_INDEX_FIELDS", "eval_judge",
-           "DEDUP_MAX_PERM",
+           "conf_loc_stats", "conf_group_stats", "conf_apply", "DEDUP_MAX_PERM",
            "DEDUP_EMPTY_SLOT", "_i64", "dedup_sha1_u32", "dedup_minhash", "dedup_lsh_insert_query"]
 
 
@@ -161,6 +161,54 @@ def eval_judge(src, ix, out_conf, out_verdict, offset: int, *, assume_buggy: boo
     _check(load_library().bl_eval_judge(src.data_ptr(), src.numel(), p("loc_idx"), p("loc_off"), p("key_node"), total_loc, p("rw_idx"),
                                         p("rw_off"), p("rw_node"), total_rw, p("tgt_rw"), B, int(bool(assume_buggy)),
                                         out_conf.data_ptr(), out_verdict.data_ptr(), offset, N, _stream()), "bl_eval_judge")
+
+
+# ------------------------------------------------------------------------------------------------
+# confidence calibration (csrc/bl_confidence.hip; include/buglab_hip.h::bl_conf_loc_stats, bl_conf_group_stats, bl_conf_apply)
+def _conf_stats(what: str, cols: int, vals, seg_off, tgt, scalars) -> torch.Tensor:
+    _f32(vals, "vals"), _i32(seg_off, "seg_off"), _i32(tgt, "tgt")
+    nseg = tgt.shape[0]
+    if vals.dim() != 1 or tgt.dim() != 1 or seg_off.dim() != 1 or seg_off.shape[0] != nseg + 1:
+        raise ValueError(f"{what}: vals {tuple(vals.shape)} must be [n], tgt {tuple(tgt.shape)} [nseg] and seg_off "
+                         f"{tuple(seg_off.shape)} [nseg + 1]")
+    work = torch.empty(cols * (nseg + 1), dtype=torch.float64, device=vals.device)  # [the result | cols x nseg partials]
+    _check(getattr(load_library(), "bl_" + what)(vals.data_ptr(), vals.numel(), seg_off.data_ptr(), tgt.data_ptr(), nseg, *scalars,
+                                                 work.data_ptr() + 8 * cols, work.data_ptr(), _stream()), "bl_" + what)
+    return work[:cols]
+
+
+def conf_loc_stats(vals, seg_off, tgt, beta: float, bias: float) -> torch.Tensor:
+    """The calibration loss of a pool of location segments at (beta, bias) and its derivatives, float64 [6] = F | dF/dbeta |
+    dF/dbias | d2F/dbeta2 | d2F/dbeta dbias | d2F/dbias2.  vals float32 [n]: the segments' log-probabilities back to back,
+    NO_BUG last in each; seg_off int32 [nseg + 1]; tgt int32 [nseg]: the target's place within its segment.  No sync."""
+    return _conf_stats("conf_loc_stats", 6, vals, seg_off, tgt, (float(beta), float(bias)))
+
+
+def conf_group_stats(vals, seg_off, tgt, beta: float) -> torch.Tensor:
+    """The same for repair groups under one scale: float64 [3] = F_r | F_r' | F_r''.  No sync."""
+    return _conf_stats("conf_group_stats", 3, vals, seg_off, tgt, (float(beta),))
+
+
+def conf_apply(flat, candidate_ptr, num_samples: int, repair_group_ptr, repair_group_items, *, beta: float, no_bug_bias: float,
+               repair_beta: float) -> None:
+    """Calibrates a predict minibatch's flat fp32 output [loc | text | var | swap] IN PLACE: each sample's location entries
+    (candidates candidate_ptr[b] : candidate_ptr[b + 1], NO_BUG at C + b) become log_softmax(beta * l + no_bug_bias * [NO_BUG]),
+    each repair group (the CSR repair_group_ptr / repair_group_items over the entries behind the C + B location entries)
+    log_softmax(repair_beta * r).  The location part is left alone when (beta, no_bug_bias) == (1, 0), the repair part when
+    repair_beta == 1.  candidate_ptr int32 [B + 1] (C is read from the flat layout: the repair items fill the rest).  No sync."""
+    _f32(flat, "flat"), _i32(candidate_ptr, "candidate_ptr"), _i32(repair_group_ptr, "repair_group_ptr")
+    _i32(repair_group_items, "repair_group_items")
+    B, n_items = int(num_samples), repair_group_items.shape[0]
+    if flat.dim() != 1 or candidate_ptr.dim() != 1 or candidate_ptr.shape[0] != B + 1 or repair_group_ptr.dim() != 1 \
+            or repair_group_ptr.shape[0] < 1 or repair_group_items.dim() != 1 or flat.shape[0] < B + n_items:
+        raise ValueError(f"conf_apply: inconsistent shapes (B {B}, flat {tuple(flat.shape)}, candidate_ptr {tuple(candidate_ptr.shape)}, "
+                         f"repair_group_ptr {tuple(repair_group_ptr.shape)}, repair_group_items {tuple(repair_group_items.shape)})")
+    C = flat.shape[0] - n_items - B
+    do_loc = not (float(beta) == 1.0 and float(no_bug_bias) == 0.0)
+    G = repair_group_ptr.shape[0] - 1 if float(repair_beta) != 1.0 else 0
+    _check(load_library().bl_conf_apply(flat.data_ptr(), flat.numel(), candidate_ptr.data_ptr(), B if do_loc else 0, C,
+                                        repair_group_ptr.data_ptr(), _p(repair_group_items), G, n_items, C + B, float(beta),
+                                        float(no_bug_bias), float(repair_beta), _stream()), "bl_conf_apply")
 
 
 # ------------------------------------------------------------------------------------------------
