@@ -861,6 +861,38 @@ int bl_conf_apply(float* flat, int64_t n_flat, const int32_t* candidate_ptr, int
                   double repair_beta, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Knowledge distillation (buglab/models/distill.py annotates records with a teacher's distributions; GnnBugLabModule
+ * .set_distillation switches the term on), in csrc/bl_distill.hip.  BEYOND THE REFERENCE: it has no soft-target loss; the term
+ * sits beside the hard-label loss assembly of buglab/models/gnn.py:221-251 and
+ * buglab/models/layers/localizationmodule.py:63-124 (bl_bug_loss_fwd above) and reads the same logits.  Per segment, in fp64,
+ * compiled without fused multiply-adds (buglab/models/_distill.py is the same arithmetic in NumPy):
+ *   a_i = z_i / tau, ms = max a, Ss = sum exp(a_i - ms):  log q_i = (a_i - ms) - log Ss,  q_i = exp(a_i - ms) / Ss;
+ *   u_i = t_i / tau over the teacher entries t_i > -inf, mt, St likewise:  log p_i = (u_i - mt) - log St,  p_i = exp(u_i - mt) / St;
+ *   KL = sum over p_i > 0 of p_i (log p_i - log q_i);  delta_i = q_i - p_i, p_i = 0 where t_i is -inf or NaN.
+ * Location segment b < B: the candidate rows candidate_ptr[b] .. candidate_ptr[b + 1] (clamped to [0, C]) and then NO_BUG,
+ * whose student logit is the constant 1.0 and whose teacher value is teacher_loc[C + b] (teacher_loc has C + B entries, in the
+ * item order of the localization log-softmax).  Repair segment g < G: the logits repair_group_items[k], k in
+ * repair_group_ptr[g] : repair_group_ptr[g + 1] (the CSR of the model's own repair log-softmax: every logit belongs to exactly one
+ * group; items outside [0, R) are left out), teacher_repair in the order of repair_logits = text | var | swap.  A segment with
+ * no teacher entry above -inf is skipped: KL 0, delta 0, counted; an empty group counts as nothing.
+ *
+ * bl_distill_fwd: one wave per segment, lanes stride over it (any length).  delta [C + R] = candidates | logits, rounded once to
+ *   fp32; NO_BUG has none.  out[8] = location KL sum | repair KL sum | distilled location segments | distilled repair groups |
+ *   location segments where the student's first maximum is the teacher's | skipped segments | 0 | 0.  The sums: per-segment
+ *   values in ws (bl_distill_workspace_bytes(B, G) bytes, the caller's), then a second kernel in an order fixed by B and G
+ *   alone; fp64, rounded once to fp32; no atomics, bit-identical from launch to launch.  B, G, C, R may each be 0.
+ * bl_distill_bwd: g_loc_scores[i] = g_loc * delta[i] / tau (i < C), g_repair_logits[j] = g_rep * delta[C + j] / tau (j < R);
+ *   g_loc, g_rep: device scalars.  Elementwise, multi-workgroup, writes every entry.
+ * BL_EINVAL: null pointers, negative sizes, a temperature that is not finite and > 0, C > 0 with B == 0, R > 0 with G == 0.
+ * BL_ERANGE: sizes beyond int32. */
+int64_t bl_distill_workspace_bytes(int32_t B, int32_t G);
+int bl_distill_fwd(const float* loc_scores, const float* repair_logits, const float* teacher_loc, const float* teacher_repair,
+                   const int32_t* candidate_ptr, const int32_t* repair_group_ptr, const int32_t* repair_group_items, int32_t B,
+                   int32_t G, int64_t C, int64_t R, double tau, void* ws, float* delta, float* out, void* stream);
+int bl_distill_bwd(const float* delta, int64_t C, int64_t R, const float* g_loc, const float* g_rep, double tau,
+                   float* g_loc_scores, float* g_repair_logits, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Near-duplicate detection (buglab/data/deduplication/index.py:15-70: `DuplicationIndex.check_if_duplicate_and_add`, which
  * updates a 256-permutation MinHash one token at a time and keeps one Python dict per LSH band), in csrc/bl_dedup.hip.  The
  * arithmetic is the written specification of DESIGN.md "Near-duplicate detection"; all of it is integer work and every result is

@@ -24,7 +24,7 @@ takes in the reference (gnn.py:144-167), so `nn(**minibatch)` is unchanged.
 from __future__ import annotations
 
 from dataclasses import dataclass, field
-from typing import Any, Dict, List, NamedTuple, Optional, Sequence
+from typing import Any, Dict, List, NamedTuple, Optional, Sequence, Tuple
 
 import os
 
@@ -69,6 +69,9 @@ class BaseTensorizedBugLabGnn(NamedTuple):
     pair_rewrite_original_idx: Sequence[int]
     num_rewrite_locations_considered: int
     rewrite_logprobs: Optional[Sequence[float]]
+    # beyond the reference (knowledge distillation, buglab/models/distill.py): a teacher's distributions as two float32 arrays,
+    # (teacher_loc [candidates + 1], NO_BUG last; teacher_rewrite [candidate rewrites], by original rewrite index)
+    teacher_targets: Optional[Tuple[np.ndarray, np.ndarray]] = None
 
 
 REFERENCE_KEYS_1D = (
@@ -364,6 +367,19 @@ def collate_samples(samples: Sequence[BaseTensorizedBugLabGnn], num_edge_types: 
         ng = int(index[observed].max()) + 1 if observed.size else 0
         ptr, order = _csr(index[observed], ng)
         mb["gen_group_ptr"], mb["gen_group_items"], mb["gen_num_groups"] = ptr, observed[order].astype(I32), ng
+    with_teacher = sum(getattr(s, "teacher_targets", None) is not None for s in samples)
+    if with_teacher:  # knowledge distillation: the teacher's values beside the items of the two log-softmaxes
+        if with_teacher != B:
+            raise ValueError(f"collate_samples: {with_teacher} of the minibatch's {B} samples carry teacher targets; distillation needs "
+                             "every record annotated by buglab.models.distill, or none")
+        f32 = lambda parts: np.concatenate([np.asarray(p, dtype=np.float32).reshape(-1) for p in parts] + [np.zeros(0, np.float32)])
+        # (tensorize has checked every sample's lengths against its candidates and rewrites)
+        # the item order of the localization softmax: candidate rows in flat order, then one NO_BUG slot per graph
+        mb["teacher_loc_logprobs"] = f32([s.teacher_targets[0][:-1] for s in samples] + [[s.teacher_targets[0][-1] for s in samples]])
+        # the order of cat(text, var, swap) logits, each gathered through the sample's original rewrite indices
+        gather = lambda field: [s.teacher_targets[1][np.asarray(getattr(s, field), np.int64).reshape(-1)] for s in samples]
+        mb["teacher_repair_logprobs"] = f32(gather("text_rewrite_original_idx") + gather("candidate_rewrite_original_idx")
+                                            + gather("pair_rewrite_original_idx"))
     return mb
 
 
@@ -424,6 +440,9 @@ def pack_minibatch(mb: Dict[str, Any], out: Optional[np.ndarray] = None):
     if "rewrite_logprobs" in mb:
         meta["rewrite_logprobs"] = np.asarray(mb["rewrite_logprobs"], dtype=np.float32)
         meta["gen_num_groups"] = int(mb["gen_num_groups"])
+    if "teacher_loc_logprobs" in mb:
+        meta["teacher_loc_logprobs"] = np.asarray(mb["teacher_loc_logprobs"], dtype=np.float32)
+        meta["teacher_repair_logprobs"] = np.asarray(mb["teacher_repair_logprobs"], dtype=np.float32)
     if "seq_len" in gd:
         meta["seq"] = {"seq_batch": int(gd["seq_batch"]), "seq_len": int(gd["seq_len"])}
         meta["node_mappings"] = mb.get("node_mappings")
@@ -476,6 +495,9 @@ def upload_packed(blob: np.ndarray, meta: Dict[str, Any], device) -> Dict[str, A
     if "rewrite_logprobs" in meta:
         out["rewrite_logprobs"] = torch.from_numpy(meta["rewrite_logprobs"]).to(dev)
         out["gen_num_groups"] = meta["gen_num_groups"]
+    if "teacher_loc_logprobs" in meta:
+        for k in ("teacher_loc_logprobs", "teacher_repair_logprobs"):
+            out[k] = torch.from_numpy(meta[k]).to(dev)
     if "seq" in meta:
         out_gd.update(meta["seq"])
         out["node_mappings"] = meta["node_mappings"]

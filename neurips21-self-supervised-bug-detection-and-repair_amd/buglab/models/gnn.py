@@ -72,6 +72,41 @@ class GnnBugLabModule(ModuleWithMetrics):
         self._dropout_base_seed = int(dropout_base_seed)
         self._dropout_step = 0
 
+    # ---- knowledge distillation (beyond the reference; csrc/bl_distill.hip) --------------------------------------------------
+    # The switch is a training-time setting, not a property of the model: its attributes are never pickled (__getstate__), and a
+    # module restored from any checkpoint reads the class-level defaults.
+    _distillation = (0.0, 1.0)   # (weight, temperature)
+    _distill_stats = None        # (KL sums [2], counters [6]) of bl_distill_fwd, summed over the steps since the last reset
+    _distill_coef = None         # (key, device tensor [2]): the two KL sums' weights in the loss
+
+    @property
+    def distillation(self) -> Tuple[float, float]:
+        """(weight, temperature) of the soft-target term; weight 0 = off."""
+        return self._distillation
+
+    def set_distillation(self, weight: float = 0.0, temperature: float = 1.0) -> None:
+        """Train on a teacher's soft targets: in training mode the loss becomes
+            (1 - weight) * L_hard + weight * temperature^2 * (KL_loc / B + w_buggy * KL_rep / B)
+        with KL(teacher || student) at `temperature` summed over the location distributions and over the repair groups.  The
+        minibatches must carry `teacher_loc_logprobs` / `teacher_repair_logprobs` (records annotated by buglab.models.distill).
+        Validation and `predict` (eval mode) are untouched."""
+        weight, temperature = float(weight), float(temperature)
+        if not 0.0 <= weight <= 1.0:
+            raise ValueError(f"set_distillation: the weight must lie in [0, 1] (got {weight})")
+        if not (temperature > 0.0 and temperature < float("inf")):
+            raise ValueError(f"set_distillation: the temperature must be finite and > 0 (got {temperature})")
+        self._distillation = (weight, temperature)
+        self._distill_stats = self._distill_coef = None
+
+    def __getstate__(self):
+        state = dict(self.__dict__)
+        for name in ("_distillation", "_distill_stats", "_distill_coef"):
+            state.pop(name, None)
+        return state
+
+    def _distillation_active(self) -> bool:
+        return self.training and self.distillation[0] > 0.0
+
     @property
     def use_all_gnn_layer_outputs(self):
         return self._use_all_gnn_layer_outputs
@@ -96,6 +131,7 @@ class GnnBugLabModule(ModuleWithMetrics):
         # its own epoch index on reset) before they are dropped; its own turn then finds nothing and does nothing
         self._localization_module._reset_module_metrics()
         self._fused_stats = None
+        self._distill_stats = None
 
     def _module_metrics(self) -> Dict[str, Any]:
         acc = self._all_acc()
@@ -103,6 +139,14 @@ class GnnBugLabModule(ModuleWithMetrics):
             return {}
         loss, repair, samples, batches = (float(x) for x in acc.tolist())
         m = {}
+        ds = self._distill_stats
+        if ds is not None:  # ([location KL, repair KL], [distilled location segments, distilled repair groups, agreement, ..])
+            (kl_loc, kl_rep), (n_loc, n_rep, agree) = ds[0].tolist(), ds[1][:3].tolist()
+            if n_loc > 0:
+                m["Distillation KL (localization)"] = kl_loc / n_loc
+                m["Teacher agreement"] = agree / n_loc
+            if n_rep > 0:
+                m["Distillation KL (repair)"] = kl_rep / n_rep
         if samples > 0:
             m["Repair Loss"] = repair / samples
         if batches > 0:
@@ -175,7 +219,8 @@ class GnnBugLabModule(ModuleWithMetrics):
 
     def _forward_fused_loss(self, gnn_output, graph_data, has_bug, correct_candidate_node_idxs, target_rewrites,
                             rewrite_to_location_group, candidate_symbol_to_location_group, swapped_pair_to_call_location_group,
-                            correct_rewrite_idxs, correct_candidate_symbols, correct_swapped_pair, repair_group_ptr, repair_group_items):
+                            correct_rewrite_idxs, correct_candidate_symbols, correct_swapped_pair, repair_group_ptr, repair_group_items,
+                            teacher_loc_logprobs=None, teacher_repair_logprobs=None):
         """reference :221-251 with localizationmodule.py:63-124 and fixermodules' forward()s folded in (hip_ops.bug_loss)."""
         h, refs = self._head_inputs(gnn_output)
         B = has_bug.shape[0]
@@ -188,10 +233,27 @@ class GnnBugLabModule(ModuleWithMetrics):
                                   (rewrite_to_location_group, candidate_symbol_to_location_group, swapped_pair_to_call_location_group),
                                   (correct_rewrite_idxs, correct_candidate_symbols, correct_swapped_pair),
                                   int(repair_group_ptr.shape[0]) - 1)
+        w_buggy = self._buggy_samples_weight_schedule(self._epoch_idx)
         loss, stats = hip_ops.bug_loss(scores, logits, (text.shape[0], var.shape[0], swap.shape[0]), ix,
-                                       self._buggy_samples_weight_schedule(self._epoch_idx), self._localization_module._abstain_weight)
+                                       w_buggy, self._localization_module._abstain_weight)
         with torch.no_grad():  # :244-249 and the sub-modules' counters, without host syncs
             self._fused_stats = stats if self._fused_stats is None else self._fused_stats + stats
+        if teacher_loc_logprobs is not None:  # knowledge distillation (beyond the reference): the soft-target term
+            lam, tau = self.distillation
+            kl, dstats = hip_ops.distill_loss(scores, logits, teacher_loc_logprobs, teacher_repair_logprobs, ix, tau)
+            # loss = (1 - lam) L_hard + c KL_loc + c w_buggy KL_rep, c = lam tau^2 / B: one dot and one add; the weights are a
+            # device tensor built without a host copy and kept while (lam, tau, w_buggy, B) stay the same
+            key = (lam, tau, float(w_buggy), B, scores.device)
+            if self._distill_coef is None or self._distill_coef[0] != key:
+                c = lam * tau * tau / B
+                coef = torch.full((2,), c, dtype=torch.float32, device=scores.device)
+                coef[1] = c * float(w_buggy)
+                self._distill_coef = (key, coef)
+            loss = torch.add(torch.dot(kl, self._distill_coef[1]), loss, alpha=1.0 - lam)
+            with torch.no_grad():
+                kl_sum = kl.detach()
+                self._distill_stats = ((kl_sum, dstats) if self._distill_stats is None
+                                       else (self._distill_stats[0] + kl_sum, self._distill_stats[1] + dstats))
         return loss
 
     def _compute_repair_logprobs(self, gnn_output: GnnOutput, target_rewrites, rewrite_to_location_group,
@@ -246,17 +308,27 @@ class GnnBugLabModule(ModuleWithMetrics):
                 swapped_pair_to_call_location_group, correct_swapped_pair, pair_rewrite_idxs, rewrite_to_graph_id,
                 rewrite_logprobs: Optional[torch.Tensor] = None, repair_group_ptr=None, repair_group_items=None,
                 num_repair_groups=None, gen_group_ptr=None, gen_group_items=None, gen_num_groups=None,
-                dropout_seed: Optional[int] = None, **kwargs):
+                dropout_seed: Optional[int] = None, teacher_loc_logprobs: Optional[torch.Tensor] = None,
+                teacher_repair_logprobs: Optional[torch.Tensor] = None, **kwargs):
         """reference :144-251 (keyword-only arguments, visualisation extras ignored)."""
         if dropout_seed is None:
             dropout_seed = self._next_dropout_seed()
+        distill = self._distillation_active()
+        if distill:
+            if teacher_loc_logprobs is None or teacher_repair_logprobs is None:
+                raise ValueError("distillation is on (set_distillation) but the minibatch carries no teacher_loc_logprobs / "
+                                 "teacher_repair_logprobs: it needs records annotated by buglab.models.distill and a graph student")
+            if not (rewrite_logprobs is None and hip_ops.FUSED_LOSS and repair_group_ptr is not None and self._fused_loss_applicable()):
+                raise NotImplementedError("distillation is implemented on the fused-loss path of detector training only: not for "
+                                          "the selector branch (rewrite_logprobs) and not with hip_ops.FUSED_LOSS off")
         gnn_output = self._compute_gnn_output(graph_data, dropout_seed)
         if rewrite_logprobs is None and hip_ops.FUSED_LOSS and repair_group_ptr is not None and self._fused_loss_applicable():
             # detector training: everything between the scorers' logits and the loss in one kernel per direction
             return self._forward_fused_loss(gnn_output, graph_data, has_bug, correct_candidate_node_idxs, target_rewrites,
                                             rewrite_to_location_group, candidate_symbol_to_location_group,
                                             swapped_pair_to_call_location_group, correct_rewrite_idxs, correct_candidate_symbols,
-                                            correct_swapped_pair, repair_group_ptr, repair_group_items)
+                                            correct_swapped_pair, repair_group_ptr, repair_group_items,
+                                            teacher_loc_logprobs if distill else None, teacher_repair_logprobs if distill else None)
         swap_lp, text_lp, var_lp, (swap_sel, text_sel, var_sel) = self._compute_repair_logprobs(
             gnn_output, target_rewrites, rewrite_to_location_group, candidate_symbol_to_location_group,
             swapped_pair_to_call_location_group, repair_group_ptr, repair_group_items, num_repair_groups)
@@ -416,7 +488,32 @@ class GnnBugLabModel(AbstractNeuralModel, AbstractBugLabModel):
             swapped_pair_to_call=swapped_pair_to_call, correct_swapped_pair=correct_swapped_pair,
             pair_rewrite_original_idx=swapped_rewrite_original_ids,
             num_rewrite_locations_considered=len(repr_location_group_ids),
-            rewrite_logprobs=datapoint.get("candidate_rewrite_logprobs", None))
+            rewrite_logprobs=datapoint.get("candidate_rewrite_logprobs", None),
+            teacher_targets=self._teacher_targets(datapoint, graph_data.reference_nodes["candidate_nodes"]))
+
+    @staticmethod
+    def _teacher_targets(datapoint, candidate_nodes) -> Optional[Tuple[np.ndarray, np.ndarray]]:
+        """The teacher's distributions buglab.models.distill wrote into the record (beyond the reference), checked against the
+        sample: -> (teacher_loc float32 [candidates + 1], NO_BUG last; teacher_rewrite float32 [candidate rewrites])."""
+        keys = ("teacher_location_nodes", "teacher_location_logprobs", "teacher_rewrite_logprobs")
+        present = [k for k in keys if datapoint.get(k) is not None]
+        if not present:
+            return None
+        if len(present) != len(keys):
+            raise ValueError(f"teacher annotation: the record carries {present} but not {[k for k in keys if k not in present]}")
+        nodes = np.asarray(datapoint["teacher_location_nodes"], dtype=np.int64).reshape(-1)
+        loc = np.asarray(datapoint["teacher_location_logprobs"], dtype=np.float32).reshape(-1)
+        rewrites = np.asarray(datapoint["teacher_rewrite_logprobs"], dtype=np.float32).reshape(-1)
+        own = np.concatenate([np.asarray(candidate_nodes, dtype=np.int64).reshape(-1), [-1]])
+        if loc.shape[0] != nodes.shape[0]:
+            raise ValueError(f"teacher annotation: {loc.shape[0]} teacher_location_logprobs for {nodes.shape[0]} teacher_location_nodes")
+        if nodes.shape[0] != own.shape[0] or (nodes != own).any():
+            raise ValueError(f"teacher annotation: teacher_location_nodes {nodes.tolist()} are not the sample's candidate nodes + [-1] "
+                             f"{own.tolist()}")
+        if rewrites.shape[0] != len(datapoint["candidate_rewrites"]):
+            raise ValueError(f"teacher annotation: {rewrites.shape[0]} teacher_rewrite_logprobs for "
+                             f"{len(datapoint['candidate_rewrites'])} candidate_rewrites")
+        return loc, rewrites
 
     # minibatching: the reference appends element by element (:431-542) and builds ~15 tensors from
     # Python lists (:544-604); here samples are only collected and `finalize_minibatch` does one

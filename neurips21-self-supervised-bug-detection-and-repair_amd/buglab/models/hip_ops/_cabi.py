@@ -200,6 +200,10 @@ _SIGNATURES = {
     "bl_conf_group_stats": ([c_void_p, c_int64, c_void_p, c_void_p, c_int32, c_double, c_void_p, c_void_p, c_void_p], ctypes.c_int),
     "bl_conf_apply": ([c_void_p, c_int64, c_void_p, c_int32, c_int64, c_void_p, c_void_p, c_int32, c_int64, c_int64, c_double, c_double,
                        c_double, c_void_p], ctypes.c_int),
+    "bl_distill_workspace_bytes": ([c_int32, c_int32], c_int64),
+    "bl_distill_fwd": ([c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int64, c_int64, c_double,
+                        c_void_p, c_void_p, c_void_p, c_void_p], ctypes.c_int),
+    "bl_distill_bwd": ([c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_double, c_void_p, c_void_p, c_void_p], ctypes.c_int),
     "bl_dedup_sha1_u32": ([c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p], ctypes.c_int),
     "bl_dedup_minhash": ([c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int32, c_void_p, c_void_p], ctypes.c_int),
     "bl_dedup_lsh_insert_query": ([c_void_p, c_int32, c_int32, c_int32, c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p,

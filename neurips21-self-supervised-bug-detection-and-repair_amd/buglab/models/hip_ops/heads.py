@@ -15,7 +15,8 @@ from .gemm import segment_max, segment_max_bwd
 __all__ = ["_SegmentLogSoftmax", "segment_log_softmax", "_SegmentMaxPool", "segment_max_pool", "_MlpScore", "mlp_score",
            "_LocalizationScores", "localization_scores", "BUG_LOSS_STATS", "BugLossIndex", "_bug_loss_desc", "_BugLoss",
            "bug_loss", "_byte_mask", "_varmisuse_desc", "_varmisuse_workspace", "_VarMisuseHead", "varmisuse_head",
-           "VARMISUSE_RECORD_D", "VARMISUSE_RECORD_I", "varmisuse_predict"]
+           "VARMISUSE_RECORD_D", "VARMISUSE_RECORD_I", "varmisuse_predict", "DISTILL_OUT", "DISTILL_STATS", "distill_fwd", "distill_bwd",
+           "_DistillLoss", "distill_loss"]
 
 
 class _SegmentLogSoftmax(torch.autograd.Function):
@@ -243,6 +244,80 @@ class _BugLoss(torch.autograd.Function):
 def bug_loss(loc_scores, logits, sizes, ix: BugLossIndex, w_buggy: float = 1.0, abstain_weight: float = 0.0):
     """-> (loss scalar, stats [16]); see include/buglab_hip.h::bl_bug_loss_t.  logits = cat(text, var, swap) with `sizes` rows each."""
     return _BugLoss.apply(loc_scores.contiguous(), logits.contiguous(), tuple(int(n) for n in sizes), ix, float(w_buggy), float(abstain_weight))
+
+
+# ------------------------------------------------------------------------------------------------
+# knowledge distillation (csrc/bl_distill.hip; include/buglab_hip.h::bl_distill_fwd): the soft-target term beside the bug loss
+DISTILL_OUT = 8      # bl_distill_fwd's out: [location KL, repair KL | the DISTILL_STATS counters]
+DISTILL_STATS = ("distilled_location_segments", "distilled_repair_groups", "location_agreement", "skipped_segments")
+
+
+def distill_fwd(loc_scores, logits, teacher_loc, teacher_repair, candidate_ptr, repair_group_ptr, repair_group_items,
+                temperature: float, delta=None, out=None):
+    """bl_distill_fwd -> (delta [C + R], out [8]); `delta` / `out`: write into these buffers instead of fresh ones."""
+    C, R = int(loc_scores.shape[0]), int(logits.shape[0])
+    B, G = int(candidate_ptr.shape[0]) - 1, int(repair_group_ptr.shape[0]) - 1
+    if B < 0 or G < 0:
+        raise ValueError("distill_fwd: candidate_ptr and repair_group_ptr need at least one entry")
+    if teacher_loc.shape[0] != C + B or teacher_repair.shape[0] != R or repair_group_items.shape[0] != R:
+        raise ValueError(f"distill_fwd: teacher_loc has {teacher_loc.shape[0]} entries for {C} candidates + {B} graphs, teacher_repair "
+                         f"{teacher_repair.shape[0]} and repair_group_items {repair_group_items.shape[0]} for {R} logits")
+    dev = teacher_loc.device
+    lib = load_library()
+    if delta is None:
+        delta = torch.empty((C + R,), dtype=torch.float32, device=dev)
+    if out is None:
+        out = torch.empty((DISTILL_OUT,), dtype=torch.float32, device=dev)
+    if delta.shape[0] != C + R or out.shape[0] != DISTILL_OUT:
+        raise ValueError(f"distill_fwd: delta needs {C + R} entries and out {DISTILL_OUT}")
+    ws = torch.empty((int(lib.bl_distill_workspace_bytes(B, G)) // 8,), dtype=torch.float64, device=dev)
+    _check(lib.bl_distill_fwd(_p(_f32(loc_scores, "loc_scores")), _p(_f32(logits, "repair logits")), _f32(teacher_loc, "teacher_loc").data_ptr(),
+                              _p(_f32(teacher_repair, "teacher_repair")), _i32(candidate_ptr, "candidate_ptr").data_ptr(),
+                              _i32(repair_group_ptr, "repair_group_ptr").data_ptr(), _p(_i32(repair_group_items, "repair_group_items")),
+                              B, G, C, R, float(temperature), ws.data_ptr(), _p(_f32(delta, "delta")), _f32(out, "out").data_ptr(),
+                              _stream()), "bl_distill_fwd")
+    return delta, out
+
+
+def distill_bwd(delta, num_candidates: int, g_kl, temperature: float, g_loc_scores=None, g_logits=None):
+    """bl_distill_bwd: g_kl = the device gradients of (location KL, repair KL) -> (g_loc_scores [C], g_logits [R])."""
+    C = int(num_candidates)
+    R = int(delta.shape[0]) - C
+    dev = delta.device
+    if g_loc_scores is None:
+        g_loc_scores = torch.empty((C,), dtype=torch.float32, device=dev)
+    if g_logits is None:
+        g_logits = torch.empty((R,), dtype=torch.float32, device=dev)
+    if R < 0 or g_loc_scores.shape[0] != C or g_logits.shape[0] != R or g_kl.numel() != 2:
+        raise ValueError(f"distill_bwd: {delta.shape[0]} deltas do not split into {C} candidates and {g_logits.shape[0]} logits")
+    g = _f32(g_kl.contiguous().reshape(2), "g_kl")
+    _check(load_library().bl_distill_bwd(_p(_f32(delta, "delta")), C, R, g.data_ptr(), g[1:].data_ptr(), float(temperature),
+                                         _p(_f32(g_loc_scores, "g_loc_scores")), _p(_f32(g_logits, "g_logits")), _stream()), "bl_distill_bwd")
+    return g_loc_scores, g_logits
+
+
+class _DistillLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, loc_scores, logits, teacher_loc, teacher_repair, ix: BugLossIndex, temperature: float):
+        delta, out = distill_fwd(loc_scores, logits, teacher_loc, teacher_repair, ix.candidate_ptr, ix.repair_group_ptr,
+                                 ix.repair_group_items, temperature)
+        ctx.saved = (delta, int(loc_scores.shape[0]), temperature)
+        kl, stats = out[:2], out[2:]
+        ctx.mark_non_differentiable(stats)
+        return kl, stats
+
+    @staticmethod
+    def backward(ctx, g_kl, _g_stats):
+        delta, C, temperature = _take_saved(ctx)
+        g_scores, g_logits = distill_bwd(delta, C, g_kl, temperature)
+        return g_scores, g_logits, None, None, None, None
+
+
+def distill_loss(loc_scores, logits, teacher_loc, teacher_repair, ix: BugLossIndex, temperature: float = 1.0):
+    """-> (kl [2] = location KL sum, repair KL sum of KL(teacher || student) at `temperature`, differentiable in loc_scores and
+    logits; stats [6]: DISTILL_STATS, then two zeros).  See include/buglab_hip.h::bl_distill_fwd."""
+    return _DistillLoss.apply(loc_scores.contiguous(), logits.contiguous(), teacher_loc.contiguous(), teacher_repair.contiguous(), ix,
+                              float(temperature))
 
 
 # ------------------------------------------------------------------------------------------------

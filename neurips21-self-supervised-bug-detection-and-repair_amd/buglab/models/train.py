@@ -16,6 +16,11 @@ Options:
     --model-spec=<json>           Extra model kwargs as JSON (e.g. '{"hidden_state_size": 256}').
     --selector                    Train a bug selector on scored data (`candidate_rewrite_logprobs`, written by
                                   buglab.controllers.detectorscoring): rewrites at every location are tensorised.
+    --distill-weight=<w>          Knowledge distillation: the weight of the teacher's soft targets in the training loss,
+                                  (1 - w) * hard-label loss + w * t^2 * KL(teacher || student).  TRAIN_DATA_PATH must hold
+                                  records annotated by `python -m buglab.models.distill`; graph students only
+                                  (gnn-mlp, ggnn).  Validation stays on the hard-label loss. [default: 0]
+    --distill-temperature=<t>     The temperature t both distributions are softened with. [default: 1]
     -h --help                     Show this screen.
     --debug                       Enable debug routines. [default: False]
 
@@ -71,10 +76,13 @@ def run(arguments):
     if arguments.get("--model-spec"):
         model_spec.update(json.loads(arguments["--model-spec"]))
     model, nn, initialize_metadata = load_model(model_spec, model_path, arguments.get("--restore-path", None))
+    distill_weight = float(arguments.get("--distill-weight") or 0)
+    distill_temperature = float(arguments.get("--distill-temperature") or 1)
     trainer = ModelTrainer(model, model_path, max_num_epochs=int(arguments["--max-num-epochs"]),
                            minibatch_size=int(arguments["--minibatch-size"]), optimizer_creator=optimizer,
                            clip_gradient_norm=0.5, scheduler_creator=lambda o: LinearWarmupScheduler(o),
-                           enable_amp=arguments["--amp"])
+                           enable_amp=arguments["--amp"],
+                           distillation=(distill_weight, distill_temperature) if distill_weight > 0 else None)
     if nn is not None:
         trainer.neural_module = nn
         # continuing from a checkpoint: Adam's moments / warm-up position live in `<checkpoint>.optim` when this
@@ -124,6 +132,8 @@ def parse_args(argv=None):
     p.add_argument("--quiet", action="store_true")
     p.add_argument("--model-spec", default=None)
     p.add_argument("--selector", action="store_true")
+    p.add_argument("--distill-weight", default="0")
+    p.add_argument("--distill-temperature", default="1")
     p.add_argument("--debug", action="store_true")
     ns = p.parse_args(argv)
     d = {"MODEL_NAME": ns.MODEL_NAME, "TRAIN_DATA_PATH": ns.TRAIN_DATA_PATH, "VALID_DATA_PATH": ns.VALID_DATA_PATH,

@@ -13,7 +13,7 @@ import logging
 import os
 import time
 from pathlib import Path
-from typing import Callable, Dict, Iterable, List, Optional
+from typing import Callable, Dict, Iterable, List, Optional, Tuple
 
 import torch
 import torch.distributed as dist
@@ -110,7 +110,8 @@ class ModelTrainer:
     def __init__(self, model, save_location: Path, *, max_num_epochs: int = 100, minibatch_size: int = 200,
                  optimizer_creator: Optional[Callable] = None, clip_gradient_norm: Optional[float] = None,
                  scheduler_creator: Optional[Callable] = None, target_validation_metric: Optional[str] = None,
-                 target_validation_metric_higher_is_better: bool = False, enable_amp: bool = False):
+                 target_validation_metric_higher_is_better: bool = False, enable_amp: bool = False,
+                 distillation: Optional[Tuple[float, float]] = None):
         self.model = model
         self._save_location = Path(save_location)
         self._max_num_epochs = max_num_epochs
@@ -130,6 +131,10 @@ class ModelTrainer:
         # packed-row launchers also carry gnn-mlp's dense node update, which --amp never reduced).  Applied when training starts
         # (`train`), undone when it ends.
         self._enable_amp = bool(enable_amp)
+        # knowledge distillation (beyond the reference): (weight, temperature) of the soft-target term, set on the module when
+        # training starts (GnnBugLabModule.set_distillation); the training records must carry a teacher's distributions
+        # (buglab.models.distill), validation records need none
+        self._distillation = None if distillation is None else (float(distillation[0]), float(distillation[1]))
         self._nn = None
         self._use_multiprocessing = False
         self._train_epoch_end_hooks: List[Callable] = []
@@ -460,6 +465,15 @@ class ModelTrainer:
                 raise RuntimeError("ModelTrainer.train: no ROCm GPU visible; the BugLab hot path has no CPU fallback")
             device = torch.device("cuda", torch.cuda.current_device())
         self._nn = self.neural_module.to(device)
+        if self._distillation is not None:
+            if not hasattr(self._nn, "set_distillation"):
+                raise ValueError(f"distillation: {type(self._nn).__name__} cannot train on a teacher's soft targets (graph students only)")
+            prev_distillation = self._nn.distillation
+            self._nn.set_distillation(*self._distillation)
+            LOGGER.info("Distillation: weight %s on the teacher's soft targets at temperature %s (training minibatches only; "
+                        "validation stays on the hard-label loss).", *self._distillation)
+        else:
+            prev_distillation = None
         optimizer = self._optimizer_creator(self._nn.parameters())
         if self._clip is not None:
             if hasattr(optimizer, "clip"):
@@ -524,6 +538,8 @@ class ModelTrainer:
                         break
         finally:
             self._drop_prestarted_pool()
+            if prev_distillation is not None:
+                self._nn.set_distillation(*prev_distillation)
             if prev_gemm_mode is not None:
                 hip_ops.set_msg_gemm_mode(prev_gemm_mode)
             if prev_seq_mode is not None:
