@@ -1095,6 +1095,21 @@ int bl_adam_clip_step(float* param, const float* grad, float* m, float* v, int64
 int bl_adam_clip_step_dp(float* param, const float* grad, float* m, float* v, int64_t n, const float* grad_sqnorm,
                          const float* batch_total, float clip_norm, float lr, float beta1, float beta2, float eps,
                          int32_t step, void* stream);
+/* Weight averaging (beyond the reference): the two calls above, keeping an exponential moving average of the parameters in the
+ * SAME pass -- after the new value p_new of an element is written, ema = fma(ema_one_minus_decay, p_new - ema, ema).
+ * `param`, `m`, `v` come out bit-identical to the calls without the average.  ema_one_minus_decay = 1 - decay of THIS update,
+ * 0 < it <= 1 (the host owns the warm-up of the decay); `ema` must not overlap `param`.  In the data-parallel form
+ * *batch_total <= 0 leaves `ema` untouched as well. */
+int bl_adam_clip_step_ema(float* param, const float* grad, float* m, float* v, float* ema, int64_t n, const float* grad_sqnorm,
+                          float grad_prescale, float clip_norm, float lr, float beta1, float beta2, float eps, int32_t step,
+                          float ema_one_minus_decay, void* stream);
+int bl_adam_clip_step_dp_ema(float* param, const float* grad, float* m, float* v, float* ema, int64_t n, const float* grad_sqnorm,
+                             const float* batch_total, float clip_norm, float lr, float beta1, float beta2, float eps, int32_t step,
+                             float ema_one_minus_decay, void* stream);
+/* exchanges the contents of two fp32 buffers of n elements in one pass (evaluating / saving the averaged weights: the
+ * parameters' views stay where they are, the CONTENTS trade places).  Any 4-byte aligned pointers; n == 0 is a no-op;
+ * overlapping ranges are refused. */
+int bl_swap_f32(float* a, float* b, int64_t n, void* stream);
 
 #ifdef __cplusplus
 }

@@ -289,6 +289,11 @@ _SIGNATURES = {
     "bl_sqnorm": ([c_void_p, c_int64, c_void_p, c_void_p, c_void_p], ctypes.c_int),
     "bl_adam_clip_step_dp": ([c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_float, c_float, c_float, c_float, c_float, c_int32, c_void_p], ctypes.c_int),
     "bl_adam_clip_step": ([c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_float, c_float, c_float, c_float, c_float, c_float, c_int32, c_void_p], ctypes.c_int),
+    "bl_adam_clip_step_ema": ([c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_float, c_float, c_float, c_float, c_float,
+                               c_float, c_int32, c_float, c_void_p], ctypes.c_int),
+    "bl_adam_clip_step_dp_ema": ([c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_float, c_float, c_float,
+                                  c_float, c_float, c_int32, c_float, c_void_p], ctypes.c_int),
+    "bl_swap_f32": ([c_void_p, c_void_p, c_int64, c_void_p], ctypes.c_int),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 

@@ -1,4 +1,5 @@
-"""Optimiser kernels on flat buffers: ordered squared norm, clip + Adam (single device and data-parallel forms)."""
+"""Optimiser kernels on flat buffers: ordered squared norm, clip + Adam (single device and data-parallel forms), the same
+with a parameter average kept in the pass, and the buffer exchange that puts the average in the parameters' place."""
 from __future__ import annotations
 
 from typing import Optional
@@ -7,7 +8,7 @@ import torch
 
 from ._cabi import _check, _f32, load_library, _p, _stream
 
-__all__ = ["_SQNORM_SCRATCH", "sqnorm", "adam_clip_step", "adam_clip_step_dp"]
+__all__ = ["_SQNORM_SCRATCH", "sqnorm", "adam_clip_step", "adam_clip_step_dp", "adam_clip_step_ema", "adam_clip_step_dp_ema", "swap_buffers"]
 
 
 # ------------------------------------------------------------------------------------------------
@@ -43,3 +44,31 @@ def adam_clip_step_dp(param, grad, m, v, sqn, batch_total, *, clip=0.5, lr=1e-4,
                                             param.numel(), _p(sqn), _f32(batch_total).data_ptr(), float(clip), float(lr), float(beta1),
                                             float(beta2), float(eps), int(step), _stream()),
         "bl_adam_clip_step_dp")
+
+
+def adam_clip_step_ema(param, grad, m, v, ema, sqn, *, one_minus_decay, prescale=1.0, clip=0.5, lr=1e-4, beta1=0.9, beta2=0.999, eps=1e-8,
+                       step=1):
+    """adam_clip_step, and in the same pass ema += one_minus_decay * (p_new - ema) (one fma per element, buglab.runtime._averaging)."""
+    _check(
+        load_library().bl_adam_clip_step_ema(_f32(param).data_ptr(), _f32(grad).data_ptr(), _f32(m).data_ptr(), _f32(v).data_ptr(),
+                                             _f32(ema).data_ptr(), param.numel(), _p(sqn), float(prescale), float(clip), float(lr),
+                                             float(beta1), float(beta2), float(eps), int(step), float(one_minus_decay), _stream()),
+        "bl_adam_clip_step_ema")
+
+
+def adam_clip_step_dp_ema(param, grad, m, v, ema, sqn, batch_total, *, one_minus_decay, clip=0.5, lr=1e-4, beta1=0.9, beta2=0.999,
+                          eps=1e-8, step=1):
+    """adam_clip_step_dp with the parameter average; a zero batch_total leaves `ema` untouched too."""
+    _check(
+        load_library().bl_adam_clip_step_dp_ema(_f32(param).data_ptr(), _f32(grad).data_ptr(), _f32(m).data_ptr(), _f32(v).data_ptr(),
+                                                _f32(ema).data_ptr(), param.numel(), _p(sqn), _f32(batch_total).data_ptr(), float(clip),
+                                                float(lr), float(beta1), float(beta2), float(eps), int(step), float(one_minus_decay),
+                                                _stream()),
+        "bl_adam_clip_step_dp_ema")
+
+
+def swap_buffers(a: torch.Tensor, b: torch.Tensor):
+    """Exchange the contents of two fp32 buffers of equal size on the device (one pass, no temporary)."""
+    if a.numel() != b.numel():
+        raise ValueError(f"swap_buffers: {a.numel()} vs {b.numel()} elements")
+    _check(load_library().bl_swap_f32(_f32(a).data_ptr(), _f32(b).data_ptr(), a.numel(), _stream()), "bl_swap_f32")

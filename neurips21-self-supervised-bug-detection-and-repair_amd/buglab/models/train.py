@@ -21,6 +21,9 @@ Options:
                                   records annotated by `python -m buglab.models.distill`; graph students only
                                   (gnn-mlp, ggnn).  Validation stays on the hard-label loss. [default: 0]
     --distill-temperature=<t>     The temperature t both distributions are softened with. [default: 1]
+    --ema-decay=<d>               Weight averaging: validate, select and save an exponential moving average of the parameters
+                                  with decay d (0 < d < 1, e.g. 0.999; warmed up from 2/11) instead of the last iterate.  The
+                                  average is kept inside the fused Adam step; training itself is unchanged. [default: 0]
     -h --help                     Show this screen.
     --debug                       Enable debug routines. [default: False]
 
@@ -78,11 +81,13 @@ def run(arguments):
     model, nn, initialize_metadata = load_model(model_spec, model_path, arguments.get("--restore-path", None))
     distill_weight = float(arguments.get("--distill-weight") or 0)
     distill_temperature = float(arguments.get("--distill-temperature") or 1)
+    ema_decay = float(arguments.get("--ema-decay") or 0)
     trainer = ModelTrainer(model, model_path, max_num_epochs=int(arguments["--max-num-epochs"]),
                            minibatch_size=int(arguments["--minibatch-size"]), optimizer_creator=optimizer,
                            clip_gradient_norm=0.5, scheduler_creator=lambda o: LinearWarmupScheduler(o),
                            enable_amp=arguments["--amp"],
-                           distillation=(distill_weight, distill_temperature) if distill_weight > 0 else None)
+                           distillation=(distill_weight, distill_temperature) if distill_weight > 0 else None,
+                           ema_decay=ema_decay if ema_decay != 0 else None)
     if nn is not None:
         trainer.neural_module = nn
         # continuing from a checkpoint: Adam's moments / warm-up position live in `<checkpoint>.optim` when this
@@ -134,6 +139,7 @@ def parse_args(argv=None):
     p.add_argument("--selector", action="store_true")
     p.add_argument("--distill-weight", default="0")
     p.add_argument("--distill-temperature", default="1")
+    p.add_argument("--ema-decay", default="0")
     p.add_argument("--debug", action="store_true")
     ns = p.parse_args(argv)
     d = {"MODEL_NAME": ns.MODEL_NAME, "TRAIN_DATA_PATH": ns.TRAIN_DATA_PATH, "VALID_DATA_PATH": ns.VALID_DATA_PATH,

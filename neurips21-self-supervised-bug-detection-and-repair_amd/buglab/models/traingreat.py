@@ -12,6 +12,8 @@ Options:
     --restore-path=<path>         The path to previous model file for starting from previous checkpoint.
     --sequential                  Do not parallelize data loading. Makes debugging easier.
     --quiet                       Do not show progress bar.
+    --ema-decay=<d>               Weight averaging: validate, select and save an exponential moving average of the parameters
+                                  with decay d (0 < d < 1; warmed up from 2/11) instead of the last iterate. [default: 0]
     -h --help                     Show this screen.
     --debug                       Enable debug routines. [default: False]
 
@@ -115,10 +117,12 @@ def run(arguments, model_factory: Callable = default_model):
     else:
         nn = None
         model = model_factory()
+    ema_decay = float(arguments.get("--ema-decay") or 0)
     trainer = ModelTrainer(model, model_path, max_num_epochs=int(arguments["--max-num-epochs"]),
                            minibatch_size=int(arguments["--minibatch-size"]), optimizer_creator=optimizer,
                            clip_gradient_norm=0.25,  # as the original GREAT (reference traingreat.py:144)
-                           scheduler_creator=lambda o: LinearWarmupScheduler(o))
+                           scheduler_creator=lambda o: LinearWarmupScheduler(o),
+                           ema_decay=ema_decay if ema_decay != 0 else None)
     if nn is not None:
         trainer.neural_module = nn
         trainer.restore_optimizer_state_from = Path(restore)  # Adam's moments, when this trainer wrote them
@@ -141,6 +145,7 @@ def parse_args(argv=None):
     p.add_argument("--restore-path", default=None)
     p.add_argument("--sequential", action="store_true")
     p.add_argument("--quiet", action="store_true")
+    p.add_argument("--ema-decay", default="0")
     p.add_argument("--debug", action="store_true")
     ns = p.parse_args(argv)
     if ns.amp:

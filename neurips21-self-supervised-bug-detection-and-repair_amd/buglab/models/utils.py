@@ -23,9 +23,10 @@ def scatter_log_softmax(src: torch.Tensor, index: torch.Tensor, dim: int = -1, e
     return hip_ops.segment_log_softmax(src.float(), torch.from_numpy(ptr).to(src.device), torch.from_numpy(items).to(src.device), n, eps)
 
 
-def optimizer(p, lr: float = 0.0001) -> FlatAdam:
-    """reference :51-52 (`torch.optim.Adam(p, lr)`), as the fused flat-buffer Adam."""
-    return FlatAdam(p, lr=lr, clip_gradient_norm=0.0, num_warmup_steps=0)
+def optimizer(p, lr: float = 0.0001, ema_decay: float = 0.0) -> FlatAdam:
+    """reference :51-52 (`torch.optim.Adam(p, lr)`), as the fused flat-buffer Adam.  `ema_decay` > 0 (beyond the reference):
+    the optimiser also keeps an exponential moving average of the parameters (FlatAdam.enable_averaging)."""
+    return FlatAdam(p, lr=lr, clip_gradient_norm=0.0, num_warmup_steps=0, ema_decay=ema_decay)
 
 
 class LinearWarmupScheduler(AbstractScheduler):

@@ -6,21 +6,31 @@ i.e. ~60 per-tensor kernels per step plus a host-synchronising `clip_grad_norm_`
 parameters live in ONE fp32 buffer and all gradients in another (the parameters' `.data`/`.grad`
 are views into them), so a step is: [one RCCL all-reduce of the gradient buffer when data-parallel]
 -> one squared-norm reduction -> one fused clip+Adam kernel.  Nothing returns to the host.
+
+Weight averaging (beyond the reference, `enable_averaging`): an exponential moving average of the parameters lives in one more
+flat buffer and is moved in the SAME kernel pass (buglab.runtime._averaging has the rule and its fp64 twin);
+`averaged_parameters()` puts it in the parameters' place for validation and checkpoints by exchanging the two buffers' contents.
 """
 from __future__ import annotations
 
+import contextlib
+import logging
 from typing import Iterable, Optional
 
 import torch
 
 from buglab.models import hip_ops
+from buglab.runtime import _averaging
+
+LOGGER = logging.getLogger(__name__)
 
 
 class FlatAdam:
     TAIL = 4  # floats appended to the gradient buffer and all-reduced with it: [graphs on this rank, rank had a minibatch, -, -]
 
     def __init__(self, params: Iterable[torch.nn.Parameter], lr: float = 1e-4, clip_gradient_norm: float = 0.5,
-                 num_warmup_steps: int = 800, betas=(0.9, 0.999), eps: float = 1e-8, process_group=None, distributed: bool = True):
+                 num_warmup_steps: int = 800, betas=(0.9, 0.999), eps: float = 1e-8, process_group=None, distributed: bool = True,
+                 ema_decay: float = 0.0):
         self.distributed = distributed  # False: never all-reduce (a single-replica reference run inside a multi-rank job)
         self.params = [p for p in params if p.requires_grad]
         assert self.params, "no trainable parameters"
@@ -64,6 +74,54 @@ class FlatAdam:
         self._bucket_left = None
         self._works = []
         self._comm_stream = None
+        # weight averaging: off until enable_averaging() (no buffer exists, and the steps call what they always called)
+        self.ema = None
+        self.ema_decay = 0.0
+        self.ema_start_step = 0
+        self._averaged_in_place = False  # inside averaged_parameters(): flat_param holds the average, ema the raw iterate
+        if ema_decay != 0.0:
+            self.enable_averaging(ema_decay)
+
+    # ---- weight averaging -----------------------------------------------------------------------------------------------
+    def enable_averaging(self, decay: float) -> None:
+        """Keep an exponential moving average of the parameters from now on: `ema` starts as a copy of the current parameters
+        and every later step moves it in the fused kernel's pass.  The update index is k = step_count - ema_start_step, so
+        whatever happens to the step counter (the idle data-parallel step that is taken back) happens to k as well."""
+        decay = _averaging.validate_decay(decay)
+        self._refuse_inside_averaged("enable_averaging")
+        if self.ema is None:
+            self.ema = self.flat_param.clone()
+            self.ema_start_step = self.step_count
+        self.ema_decay = decay
+
+    def _ema_one_minus_decay(self) -> float:
+        return _averaging.one_minus_decay_f32(self.step_count - self.ema_start_step, self.ema_decay)
+
+    def _refuse_inside_averaged(self, what: str) -> None:
+        if self._averaged_in_place:
+            raise RuntimeError(f"FlatAdam.{what}: not inside averaged_parameters() (the parameters hold the average there)")
+
+    def _exchange_parameters_and_average(self) -> None:
+        hip_ops.swap_buffers(self.flat_param, self.ema)
+        hip_ops.invalidate_weight_packs()  # the parameters changed behind autograd's version counters
+
+    @contextlib.contextmanager
+    def averaged_parameters(self):
+        """Inside, the module's parameters hold the average (validation, model.save); on exit, also when the body raises, they
+        hold the raw iterate again.  The CONTENTS of flat_param and ema trade places on the device: pointers, the parameters'
+        `.data` / `.grad` views and the spans stay what they are.  No step, no nesting inside.  A no-op without averaging."""
+        if self.ema is None:
+            yield
+            return
+        self._refuse_inside_averaged("averaged_parameters")
+        hip_ops.join_side_stream()
+        self._exchange_parameters_and_average()
+        self._averaged_in_place = True
+        try:
+            yield
+        finally:
+            self._averaged_in_place = False
+            self._exchange_parameters_and_average()
 
     def zero_grad(self):
         hip_ops.join_side_stream()
@@ -91,14 +149,21 @@ class FlatAdam:
         return grad_weight
 
     def step(self, grad_weight: float = 1.0):
+        self._refuse_inside_averaged("step")
         hip_ops.join_side_stream()  # weight-gradient GEMMs accumulate into flat_grad on the side stream
         self.step_count += 1
         prescale = self.reduce_gradients(grad_weight)
         if self.flat_param.is_cuda:
             hip_ops.sqnorm(self.flat_grad, self.sqnorm)
-            hip_ops.adam_clip_step(self.flat_param, self.flat_grad, self.m, self.v, self.sqnorm, prescale=prescale,
-                                   clip=self.clip, lr=self.lr_at(self.step_count), beta1=self.beta1, beta2=self.beta2,
-                                   eps=self.eps, step=self.step_count)
+            if self.ema is None:
+                hip_ops.adam_clip_step(self.flat_param, self.flat_grad, self.m, self.v, self.sqnorm, prescale=prescale,
+                                       clip=self.clip, lr=self.lr_at(self.step_count), beta1=self.beta1, beta2=self.beta2,
+                                       eps=self.eps, step=self.step_count)
+            else:
+                hip_ops.adam_clip_step_ema(self.flat_param, self.flat_grad, self.m, self.v, self.ema, self.sqnorm,
+                                           one_minus_decay=self._ema_one_minus_decay(), prescale=prescale, clip=self.clip,
+                                           lr=self.lr_at(self.step_count), beta1=self.beta1, beta2=self.beta2, eps=self.eps,
+                                           step=self.step_count)
             hip_ops.invalidate_weight_packs()  # the kernel wrote the parameters behind autograd's version counters
         else:
             raise hip_ops.HipOpsUnavailable("FlatAdam.step: parameters are not on a ROCm device (no CPU fallback)")
@@ -109,7 +174,7 @@ class FlatAdam:
         import torch.distributed as dist
 
         if dist.is_available() and dist.is_initialized() and dist.get_world_size(self.process_group) > 1:
-            for t in (self.flat_param, self.m, self.v):
+            for t in (self.flat_param, self.m, self.v) + (() if self.ema is None else (self.ema,)):
                 dist.broadcast(t, src=src, group=self.process_group)
             hip_ops.invalidate_weight_packs()
 
@@ -236,6 +301,7 @@ class FlatAdam:
         divides by the global count it finds in the tail (on the device) and does nothing when that count is zero."""
         import torch.distributed as dist
 
+        self._refuse_inside_averaged("step_data_parallel")
         hip_ops.join_side_stream()
         B = int(local_graphs)
         self.tail.zero_()
@@ -279,8 +345,13 @@ class FlatAdam:
         if not self.flat_param.is_cuda:
             raise hip_ops.HipOpsUnavailable("FlatAdam.step_data_parallel: parameters are not on a ROCm device (no CPU fallback)")
         hip_ops.sqnorm(self.flat_grad, self.sqnorm)
-        hip_ops.adam_clip_step_dp(self.flat_param, self.flat_grad, self.m, self.v, self.sqnorm, self.tail, clip=self.clip,
-                                  lr=self.lr_at(self.step_count), beta1=self.beta1, beta2=self.beta2, eps=self.eps, step=self.step_count)
+        if self.ema is None:
+            hip_ops.adam_clip_step_dp(self.flat_param, self.flat_grad, self.m, self.v, self.sqnorm, self.tail, clip=self.clip,
+                                      lr=self.lr_at(self.step_count), beta1=self.beta1, beta2=self.beta2, eps=self.eps, step=self.step_count)
+        else:
+            hip_ops.adam_clip_step_dp_ema(self.flat_param, self.flat_grad, self.m, self.v, self.ema, self.sqnorm, self.tail,
+                                          one_minus_decay=self._ema_one_minus_decay(), clip=self.clip, lr=self.lr_at(self.step_count),
+                                          beta1=self.beta1, beta2=self.beta2, eps=self.eps, step=self.step_count)
 
     def previous_step_was_idle(self) -> bool:
         """True when NO rank had a minibatch in the most recent `step_data_parallel` (the epoch is over for everyone).
@@ -302,11 +373,33 @@ class FlatAdam:
         """Global L2 norm of the last reduced gradient (host sync; diagnostics only)."""
         return float(self.sqnorm.sqrt())
 
+    EMA_STATE_KEYS = ("param", "ema", "ema_decay", "ema_start_step")
+
     def state_dict(self):
-        return {"m": self.m, "v": self.v, "step": self.step_count}
+        """With averaging, the checkpoint next to this state holds the AVERAGE: the raw iterate (`param`) and the average
+        travel here, so that a continued run is the same run."""
+        self._refuse_inside_averaged("state_dict")
+        sd = {"m": self.m, "v": self.v, "step": self.step_count}
+        if self.ema is not None:
+            sd.update(param=self.flat_param, ema=self.ema, ema_decay=self.ema_decay, ema_start_step=self.ema_start_step)
+        return sd
 
     def load_state_dict(self, sd):
+        self._refuse_inside_averaged("load_state_dict")
         hip_ops.invalidate_weight_packs()
         self.m.copy_(sd["m"])
         self.v.copy_(sd["v"])
         self.step_count = int(sd["step"])
+        has_average = all(k in sd for k in self.EMA_STATE_KEYS)
+        if self.ema is not None and has_average:
+            self.flat_param.copy_(sd["param"])
+            self.ema.copy_(sd["ema"])
+            self.ema_start_step = int(sd["ema_start_step"])
+        elif self.ema is not None:
+            self.ema.copy_(self.flat_param)
+            self.ema_start_step = self.step_count
+            LOGGER.info("The optimiser state holds no parameter average: the average starts from the current parameters at step %s.",
+                        self.step_count)
+        elif has_average:
+            LOGGER.info("The optimiser state holds a parameter average (decay %s) but averaging is off: the parameters stay what the "
+                        "checkpoint holds (the average), the moments are restored.", sd["ema_decay"])

@@ -9,6 +9,7 @@ gradient buffer per step (buglab.runtime.optim.FlatAdam) weighted by B_rank / B_
 equals the single-process full-minibatch update; only rank 0 saves checkpoints."""
 from __future__ import annotations
 
+import contextlib
 import logging
 import os
 import time
@@ -111,7 +112,7 @@ class ModelTrainer:
                  optimizer_creator: Optional[Callable] = None, clip_gradient_norm: Optional[float] = None,
                  scheduler_creator: Optional[Callable] = None, target_validation_metric: Optional[str] = None,
                  target_validation_metric_higher_is_better: bool = False, enable_amp: bool = False,
-                 distillation: Optional[Tuple[float, float]] = None):
+                 distillation: Optional[Tuple[float, float]] = None, ema_decay: Optional[float] = None):
         self.model = model
         self._save_location = Path(save_location)
         self._max_num_epochs = max_num_epochs
@@ -135,6 +136,13 @@ class ModelTrainer:
         # training starts (GnnBugLabModule.set_distillation); the training records must carry a teacher's distributions
         # (buglab.models.distill), validation records need none
         self._distillation = None if distillation is None else (float(distillation[0]), float(distillation[1]))
+        # weight averaging (beyond the reference): the optimiser keeps an exponential moving average of the parameters
+        # (FlatAdam.enable_averaging); validation, early stopping and the checkpoint see the average, training the raw iterate
+        if ema_decay is not None:
+            from buglab.runtime._averaging import validate_decay
+
+            ema_decay = validate_decay(ema_decay)
+        self._ema_decay = ema_decay
         self._nn = None
         self._use_multiprocessing = False
         self._train_epoch_end_hooks: List[Callable] = []
@@ -481,6 +489,15 @@ class ModelTrainer:
             else:
                 LOGGER.warning("clip_gradient_norm=%s was requested but %s cannot apply it (only FlatAdam fuses the clip); "
                                "gradients are NOT clipped", self._clip, type(optimizer).__name__)
+        if self._ema_decay is not None:
+            if hasattr(optimizer, "enable_averaging"):
+                optimizer.enable_averaging(self._ema_decay)
+                LOGGER.info("Weight averaging: validation and checkpoints use an exponential moving average of the parameters "
+                            "(decay %s, warmed up from 2/11); training continues from the raw iterate.", self._ema_decay)
+            else:
+                LOGGER.warning("ema_decay=%s was requested but %s cannot keep a parameter average (only FlatAdam does); "
+                               "validation and checkpoints use the raw parameters", self._ema_decay, type(optimizer).__name__)
+        averaged = getattr(optimizer, "averaged_parameters", contextlib.nullcontext)
         self._restore_optimizer_state(optimizer, device)
         _, world = self._world()
         if world > 1 and hasattr(optimizer, "set_overlap_groups") and hasattr(self._nn, "overlap_parameter_groups"):
@@ -525,12 +542,14 @@ class ModelTrainer:
                     hook(self.model, self._nn, epoch, metrics)
                 if epoch + 1 < self._max_num_epochs:
                     self._prestart_loaders(training_data, epoch + 1, parallelize)  # they fill their queue during validation
-                target, improved = self._run_validation(validation_data, epoch, best, device, parallelize, show_progress_bar)
+                with averaged():  # the average in the parameters' place (a no-op context without averaging)
+                    target, improved = self._run_validation(validation_data, epoch, best, device, parallelize, show_progress_bar)
+                    if improved and rank == 0:
+                        self.model.save(self._save_location, self._nn)
                 if improved:
                     best, bad_epochs = target, 0
                     if rank == 0:
-                        self.model.save(self._save_location, self._nn)
-                        self._save_optimizer_state(optimizer)
+                        self._save_optimizer_state(optimizer)  # outside: the raw iterate and the average, each under its name
                 else:
                     bad_epochs += 1
                     if bad_epochs >= patience:

@@ -148,11 +148,16 @@ __global__ __launch_bounds__(256) void sqnorm_final_kernel(const float* __restri
   if (threadIdx.x == 0) out[0] = red[0] + red[1] + red[2] + red[3];
 }
 
+// EMA: the same pass also moves an exponential moving average of the parameters towards the value it just wrote,
+// ema += omd * (p_new - ema) with omd = 1 - decay of this update (one more read and write per element, no launch of its own).
+// The fma is written out: its rounding is fixed here, not by the contraction flags.  <false> is the kernel as it always was.
+template <bool EMA>
 __global__ __launch_bounds__(256) void adam_clip_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                         float* __restrict__ m, float* __restrict__ v, long long n,
                                                         const float* __restrict__ sqnorm, float prescale, float clip,
                                                         float lr_over_bc1, float beta1, float beta2, float eps,
-                                                        float inv_sqrt_bc2, const float* __restrict__ batch_total) {
+                                                        float inv_sqrt_bc2, const float* __restrict__ batch_total,
+                                                        float* __restrict__ ema, float omd) {
   float scale = prescale;
   if (batch_total) {  // data parallel: the summed gradient is weighted by graphs per rank; divide by the global count
     const float bt = batch_total[0];
@@ -170,8 +175,29 @@ __global__ __launch_bounds__(256) void adam_clip_kernel(float* __restrict__ p, c
     const float vi = beta2 * v[i] + (1.0f - beta2) * gi * gi;
     m[i] = mi;
     v[i] = vi;
-    p[i] -= lr_over_bc1 * mi / (sqrtf(vi) * inv_sqrt_bc2 + eps);
+    const float pi = p[i] - lr_over_bc1 * mi / (sqrtf(vi) * inv_sqrt_bc2 + eps);
+    p[i] = pi;
+    if (EMA) {
+      const float ei = ema[i];
+      ema[i] = __fmaf_rn(omd, pi - ei, ei);
+    }
   }
+}
+
+// a <-> b, element by element: any 4-byte aligned pair of buffers, nothing to tune
+__global__ __launch_bounds__(256) void swap_f32_kernel(float* __restrict__ a, float* __restrict__ b, long long n) {
+  const long long stride = (long long)gridDim.x * blockDim.x;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+    const float ai = a[i];
+    a[i] = b[i];
+    b[i] = ai;
+  }
+}
+
+// [a, a + n) and [b, b + n) floats share a byte
+static inline bool bl_ranges_overlap_f32(const float* a, const float* b, int64_t n) {
+  const uintptr_t ua = (uintptr_t)a, ub = (uintptr_t)b, bytes = (uintptr_t)n * sizeof(float);
+  return ua < ub + bytes && ub < ua + bytes;
 }
 
 // ================================================================================================
@@ -266,9 +292,9 @@ extern "C" int bl_adam_clip_step(float* param, const float* grad, float* m, floa
   const double bc1 = 1.0 - pow((double)beta1, (double)step);
   const double bc2 = 1.0 - pow((double)beta2, (double)step);
   const int blocks = (int)fmin(2048.0, (double)((n + 255) / 256));
-  hipLaunchKernelGGL(adam_clip_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, param, grad, m, v, (long long)n,
+  hipLaunchKernelGGL(adam_clip_kernel<false>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, param, grad, m, v, (long long)n,
                      grad_sqnorm, grad_prescale, clip_norm, (float)((double)lr / bc1), beta1, beta2, eps,
-                     (float)(1.0 / sqrt(bc2)), (const float*)nullptr);
+                     (float)(1.0 / sqrt(bc2)), (const float*)nullptr, (float*)nullptr, 0.f);
   BL_LAUNCH_CHECK("bl_adam_clip_step");
   return BL_OK;
 }
@@ -281,9 +307,60 @@ extern "C" int bl_adam_clip_step_dp(float* param, const float* grad, float* m, f
   const double bc1 = 1.0 - pow((double)beta1, (double)step);
   const double bc2 = 1.0 - pow((double)beta2, (double)step);
   const int blocks = (int)fmin(2048.0, (double)((n + 255) / 256));
-  hipLaunchKernelGGL(adam_clip_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, param, grad, m, v, (long long)n,
+  hipLaunchKernelGGL(adam_clip_kernel<false>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, param, grad, m, v, (long long)n,
                      grad_sqnorm, 1.0f, clip_norm, (float)((double)lr / bc1), beta1, beta2, eps, (float)(1.0 / sqrt(bc2)),
-                     batch_total);
+                     batch_total, (float*)nullptr, 0.f);
   BL_LAUNCH_CHECK("bl_adam_clip_step_dp");
+  return BL_OK;
+}
+
+// the two calls above with the parameter average kept in the same pass (ema_one_minus_decay = 1 - decay of THIS update)
+extern "C" int bl_adam_clip_step_ema(float* param, const float* grad, float* m, float* v, float* ema, int64_t n,
+                                     const float* grad_sqnorm, float grad_prescale, float clip_norm, float lr, float beta1,
+                                     float beta2, float eps, int32_t step, float ema_one_minus_decay, void* stream) {
+  if (n == 0) return BL_OK;
+  BL_CHECK_ARG(param && grad && m && v && ema, "bl_adam_clip_step_ema: null pointer");
+  BL_CHECK_ARG(n > 0 && !bl_ranges_overlap_f32(param, ema, n), "bl_adam_clip_step_ema: n < 0, or param and ema overlap");
+  BL_CHECK_ARG(clip_norm <= 0.f || grad_sqnorm, "bl_adam_clip_step_ema: clipping needs grad_sqnorm");
+  BL_CHECK_ARG(step >= 1, "bl_adam_clip_step_ema: step is 1-based");
+  BL_CHECK_ARG(ema_one_minus_decay > 0.f && ema_one_minus_decay <= 1.f, "bl_adam_clip_step_ema: need 0 < ema_one_minus_decay <= 1 (got %g)",
+               (double)ema_one_minus_decay);
+  const double bc1 = 1.0 - pow((double)beta1, (double)step);
+  const double bc2 = 1.0 - pow((double)beta2, (double)step);
+  const int blocks = (int)fmin(2048.0, (double)((n + 255) / 256));
+  hipLaunchKernelGGL(adam_clip_kernel<true>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, param, grad, m, v, (long long)n,
+                     grad_sqnorm, grad_prescale, clip_norm, (float)((double)lr / bc1), beta1, beta2, eps,
+                     (float)(1.0 / sqrt(bc2)), (const float*)nullptr, ema, ema_one_minus_decay);
+  BL_LAUNCH_CHECK("bl_adam_clip_step_ema");
+  return BL_OK;
+}
+
+extern "C" int bl_adam_clip_step_dp_ema(float* param, const float* grad, float* m, float* v, float* ema, int64_t n,
+                                        const float* grad_sqnorm, const float* batch_total, float clip_norm, float lr, float beta1,
+                                        float beta2, float eps, int32_t step, float ema_one_minus_decay, void* stream) {
+  if (n == 0) return BL_OK;
+  BL_CHECK_ARG(param && grad && m && v && ema && batch_total && (clip_norm <= 0.f || grad_sqnorm) && step >= 1,
+               "bl_adam_clip_step_dp_ema: null pointer or step < 1");
+  BL_CHECK_ARG(n > 0 && !bl_ranges_overlap_f32(param, ema, n), "bl_adam_clip_step_dp_ema: n < 0, or param and ema overlap");
+  BL_CHECK_ARG(ema_one_minus_decay > 0.f && ema_one_minus_decay <= 1.f, "bl_adam_clip_step_dp_ema: need 0 < ema_one_minus_decay <= 1 (got %g)",
+               (double)ema_one_minus_decay);
+  const double bc1 = 1.0 - pow((double)beta1, (double)step);
+  const double bc2 = 1.0 - pow((double)beta2, (double)step);
+  const int blocks = (int)fmin(2048.0, (double)((n + 255) / 256));
+  hipLaunchKernelGGL(adam_clip_kernel<true>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, param, grad, m, v, (long long)n,
+                     grad_sqnorm, 1.0f, clip_norm, (float)((double)lr / bc1), beta1, beta2, eps, (float)(1.0 / sqrt(bc2)),
+                     batch_total, ema, ema_one_minus_decay);
+  BL_LAUNCH_CHECK("bl_adam_clip_step_dp_ema");
+  return BL_OK;
+}
+
+extern "C" int bl_swap_f32(float* a, float* b, int64_t n, void* stream) {
+  if (n == 0) return BL_OK;
+  BL_CHECK_ARG(a && b && n > 0, "bl_swap_f32: null pointer or n < 0");
+  BL_CHECK_ARG((((uintptr_t)a | (uintptr_t)b) & 3u) == 0, "bl_swap_f32: pointers must be 4-byte aligned");
+  BL_CHECK_ARG(!bl_ranges_overlap_f32(a, b, n), "bl_swap_f32: the two ranges overlap");
+  const int blocks = (int)fmin(2048.0, (double)((n + 255) / 256));
+  hipLaunchKernelGGL(swap_f32_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, a, b, (long long)n);
+  BL_LAUNCH_CHECK("bl_swap_f32");
   return BL_OK;
 }
