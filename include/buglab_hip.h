@@ -1016,6 +1016,29 @@ int bl_attn_rows_times_v(const float* A, const bl_head_view_t* M, int32_t B, int
                          const bl_head_view_t* out, bl_dropout_t a_drop, const bl_packed_head_view_t* out_packed, void* stream);
 int bl_attn_transposed_times_v(const float* A, const bl_head_view_t* Bm, float bm_scale, int32_t B, int32_t H, int32_t L, int32_t dk,
                                const bl_head_view_t* out, bl_dropout_t a_drop, const bl_packed_head_view_t* out_packed, void* stream);
+/* Streaming (online-softmax) form of the same attention, any L % 4 == 0: multihead_attention.py:46-80 with the edge terms of
+ * relational_multihead_attention.py:72-178 (mode 0, no value biases) without a [B H L, L] array in either direction.
+ *   fwd  ctx[b, h, i, :] = sum_j Pd[i, j] v[b, h, j, :] and lse[(b H + h) L + i] = max_j s_ij + log sum_j e^(s_ij - max), where
+ *        s_ij = q_scale q_i . k_j + sum over the CSR entries (row b L + i, key j, code) of <q_scale q_i, bias[code][h, :]>, keys
+ *        >= lens[b] masked, P = softmax_j s, Pd = dropout(P) with mask element ((b H + h) L + i) L + j (bl_rel_attn_probs_fwd's).
+ *   bwd  recomputes P tile by tile from q, k, the entries and lse; dS = P (mask g_Pd / (1 - p) - delta) with delta_i = sum_j P_ij mask
+ *        g_Pd_ij / (1 - p) summed from the recomputed tiles first (delta: fp32 [B H L] scratch of the caller, written and read here);
+ *        g_q = (dS.K + sum dS_ij bias[code]) q_scale, g_k = dS^T.(q_scale q), g_v = Pd^T.g_ctx: every row written by one owner in a
+ *        fixed order (bitwise reproducible, no float atomics); g_bias_f / g_bias_r [T, H dk] += sum dS_ij q_scale q_i (per
+ *        workgroup table, then atomics, as bl_rel_attn_probs_bwd).
+ * q, k, v, ctx, g_ctx, g_q, g_k, g_v are head views (16-byte aligned base, strides multiples of 4); lse fp32 [B H L]; the edge
+ * CSR may be NULL (all three); bias_f / bias_r [T, H dk] are read only when there is a CSR but must not be NULL.  With dropout
+ * B H L^2 < 2^32.  bl_rel_attn_stream_ok: L % 4 == 0, dk == 32, 2 T dk <= 1024; no upper bound on L. */
+int32_t bl_rel_attn_stream_ok(int32_t L, int32_t dk, int32_t T);
+int bl_rel_attn_stream_fwd(const bl_head_view_t* q, float q_scale, const bl_head_view_t* k, const bl_head_view_t* v, const int32_t* row_ptr,
+                           const int32_t* ekey, const int32_t* ecode, int32_t B, int32_t L, int32_t H, int32_t dk, int32_t T,
+                           const float* bias_f, const float* bias_r, const int32_t* lens, bl_dropout_t drop, const bl_head_view_t* ctx,
+                           float* lse, void* stream);
+int bl_rel_attn_stream_bwd(const bl_head_view_t* g_ctx, const float* lse, const bl_head_view_t* q, float q_scale, const bl_head_view_t* k,
+                           const bl_head_view_t* v, const int32_t* row_ptr, const int32_t* ekey, const int32_t* ecode, int32_t B, int32_t L,
+                           int32_t H, int32_t dk, int32_t T, const float* bias_f, const float* bias_r, const int32_t* lens,
+                           bl_dropout_t drop, float* delta, const bl_head_view_t* g_q, const bl_head_view_t* g_k,
+                           const bl_head_view_t* g_v, float* g_bias_f, float* g_bias_r, void* stream);
 /* `rat` edge value biases (relational_multihead_attention.py:155-178): ctx[b, h, i, :] += P[(b, h, i), key] * vb[code][h, :] */
 int bl_rel_value_bias_fwd(const int32_t* row_ptr, const int32_t* ekey, const int32_t* ecode, int32_t B, int32_t L, int32_t H,
                           int32_t dk, const float* P, const float* vb_f, const float* vb_r, float* ctx, void* stream);

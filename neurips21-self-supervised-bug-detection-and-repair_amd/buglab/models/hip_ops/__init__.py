@@ -23,7 +23,7 @@ from __future__ import annotations
 import sys
 import types
 
-from . import _cabi, _switches, _streams
+from . import _cabi, _switches, _streams, seq as _seq
 from ._cabi import *  # noqa: F401,F403
 from ._streams import *  # noqa: F401,F403
 from ._autograd import *  # noqa: F401,F403
@@ -40,7 +40,9 @@ from .optim import *  # noqa: F401,F403
 # Names whose one copy lives in its owner module but that callers read / set on the package (bench.py, tests, tools): the
 # switches (`hip_ops.USE_SIDE_STREAM = False`), and CALL_COUNT, LIB_PATH and `_lib` (the CDLL handle: tools point it at a tuning
 # build) of the C-ABI module.  The package itself never holds them: no star import above carries one.
-_FORWARDED = {**{name: _switches for name in _switches.__all__}, **{name: _cabi for name in _cabi.FORWARDED_BY_PACKAGE}}
+# STREAMING_ATTENTION is the one switch owned by a domain module (seq.py, next to attention_path, which reads it).
+_FORWARDED = {**{name: _switches for name in _switches.__all__}, **{name: _cabi for name in _cabi.FORWARDED_BY_PACKAGE},
+              "STREAMING_ATTENTION": _seq}
 
 
 class _HipOpsModule(types.ModuleType):

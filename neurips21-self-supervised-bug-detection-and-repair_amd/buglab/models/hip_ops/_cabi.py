@@ -222,6 +222,14 @@ _SIGNATURES = {
                               bl_dropout_t, POINTER(bl_packed_head_view_t), c_void_p], ctypes.c_int),
     "bl_attn_transposed_times_v": ([c_void_p, POINTER(bl_head_view_t), c_float, c_int32, c_int32, c_int32, c_int32, POINTER(bl_head_view_t),
                                     bl_dropout_t, POINTER(bl_packed_head_view_t), c_void_p], ctypes.c_int),
+    "bl_rel_attn_stream_ok": ([c_int32, c_int32, c_int32], c_int32),
+    "bl_rel_attn_stream_fwd": ([POINTER(bl_head_view_t), c_float, POINTER(bl_head_view_t), POINTER(bl_head_view_t), c_void_p, c_void_p, c_void_p,
+                                c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, bl_dropout_t, POINTER(bl_head_view_t),
+                                c_void_p, c_void_p], ctypes.c_int),
+    "bl_rel_attn_stream_bwd": ([POINTER(bl_head_view_t), c_void_p, POINTER(bl_head_view_t), c_float, POINTER(bl_head_view_t),
+                                POINTER(bl_head_view_t), c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p,
+                                c_void_p, bl_dropout_t, c_void_p, POINTER(bl_head_view_t), POINTER(bl_head_view_t), POINTER(bl_head_view_t), c_void_p,
+                                c_void_p, c_void_p], ctypes.c_int),
     "bl_great_layer_ok": ([c_int32, c_int32, c_int32, c_int32, c_int32, c_int32], c_int32),
     "bl_great_layer_saved_bytes": ([c_int32, c_int32, c_int32, c_int32, c_int32, c_int32], c_int64),
     "bl_great_layer_workspace_bytes": ([c_int32, c_int32, c_int32, c_int32, c_int32, c_int32], c_int64),

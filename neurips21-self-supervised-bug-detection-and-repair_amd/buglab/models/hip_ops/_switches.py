@@ -52,6 +52,8 @@ LINEAR_X6_MIN_ROWS = 1024
 FUSED_LOSS = os.environ.get("BL_FUSED_LOSS", "1") != "0"
 
 FUSED_ATTENTION = os.environ.get("BL_FUSED_ATTENTION", "1") != "0"  # seq-great: scores -> probabilities in one kernel
+# (the three-valued streaming-attention switch, hip_ops.STREAMING_ATTENTION / BL_STREAMING_ATTENTION = auto | 1 | 0, is owned by
+# seq.py, next to attention_path() which interprets it; the package forwards it there exactly as it forwards the names above here)
 
 # one relational transformer encoder layer per C call (csrc/bl_great_layer.hip)
 FUSED_GREAT_LAYER = os.environ.get("BL_FUSED_GREAT_LAYER", "1") != "0"  # A/B switch: 0 = the op-by-op path

@@ -2,19 +2,20 @@
 from __future__ import annotations
 
 import ctypes
+import os
 from typing import NamedTuple, Optional
 
 import torch
 
 from . import _switches, _streams
-from ._cabi import bl_great_layer_grads_t, bl_great_layer_t, _check, Dropout, _f32, _i32, load_library, NO_DROPOUT, _p, _stream
+from ._cabi import bl_great_layer_grads_t, bl_great_layer_t, bl_head_view_t, _check, Dropout, _f32, _i32, load_library, NO_DROPOUT, _p, _stream
 from ._streams import _timed
 from ._autograd import _grad_target, _in_seq_gemm_mode, _seq_gemm_mode_code, _take_saved
 from .gemm import gemm_rows, gemm_wgrad, layernorm_bwd
 from .weights import _packed_layer_weights
 
-__all__ = ["_AddLayerNorm", "add_layernorm", "RelEdges", "_group_ptr_cache", "_uniform_group_ptr", "_RelAttention",
-           "rel_attention", "_GruScan", "gru_scan", "great_layer_ok", "_great_desc", "_GreatLayer", "great_layer"]
+__all__ = ["_AddLayerNorm", "add_layernorm", "RelEdges", "_group_ptr_cache", "_uniform_group_ptr", "ATTN_STORED_MAX_L", "attention_path",
+           "_RelAttention", "rel_attention", "_GruScan", "gru_scan", "great_layer_ok", "_great_desc", "_GreatLayer", "great_layer"]
 
 
 # ------------------------------------------------------------------------------------------------
@@ -79,6 +80,102 @@ def _uniform_group_ptr(G: int, L: int, device):
     return t
 
 
+# The attention without an [L, L] array (csrc/bl_attn_stream.hip): "auto" = only where neither stored-P path takes the shape
+# (L > ATTN_STORED_MAX_L), "1" = wherever bl_rel_attn_stream_ok holds and the mode allows, "0" = never.  An A/B switch like those
+# of _switches.py, assigned on the package (`hip_ops.STREAMING_ATTENTION = "1"`) and forwarded to this module, its one owner; it
+# is read here at call time and is deliberately not in `__all__` (a star-imported copy would go stale).
+STREAMING_ATTENTION = os.environ.get("BL_STREAMING_ATTENTION", "auto")
+ATTN_STORED_MAX_L = 1024  # bl_masked_softmax_* / bl_softmax_bwd and K^T in LDS (bl_rel_attn_probs_ok) stop here
+
+
+def _streaming_switch() -> str:
+    v = STREAMING_ATTENTION
+    v = {True: "1", False: "0"}.get(v, v) if isinstance(v, bool) else str(v).strip().lower()
+    if v not in ("auto", "1", "0"):
+        raise ValueError(f"STREAMING_ATTENTION / BL_STREAMING_ATTENTION must be 'auto', '1' or '0' (got {STREAMING_ATTENTION!r})")
+    return v
+
+
+def attention_path(L: int, dk: int, T: int, scalar_bias: bool = False, value_biases: bool = False) -> str:
+    """Which kernels _RelAttention runs for the shape: "fused" (scores -> probabilities in one kernel, P stored), "rowwise" (GEMM +
+    edge terms + masked softmax, P stored) or "stream" (online softmax, nothing of size L x L).  A pure function of the shape, the
+    mode and the switches; raises ValueError, before any launch, when no path takes the shape."""
+    L, dk, T = int(L), int(dk), int(T)
+    lib = load_library()
+    switch = _streaming_switch()
+    why_not = None  # why the streaming kernels cannot take it
+    if scalar_bias:
+        why_not = "the scalar key-bias mode has no streaming form"
+    elif value_biases:
+        why_not = "edge value biases (seq-rat) have no streaming form"
+    elif not lib.bl_rel_attn_stream_ok(L, dk, T):
+        why_not = f"bl_rel_attn_stream_ok(L={L}, dk={dk}, T={T}) is 0 (needs L % 4 == 0, dk == 32, 2 T dk <= 1024)"
+    stored_ok = L <= ATTN_STORED_MAX_L
+    if switch == "1" and why_not is None:
+        return "stream"
+    if stored_ok:
+        return "fused" if (_switches.FUSED_ATTENTION and not scalar_bias and lib.bl_rel_attn_probs_ok(L, dk, T)) else "rowwise"
+    if switch == "0":
+        why_not = "streaming attention is switched off (STREAMING_ATTENTION = 0)"
+    if why_not is None:
+        return "stream"
+    raise ValueError(f"rel_attention: sequence length L={L} exceeds the limit of {ATTN_STORED_MAX_L} keys of the stored-probability "
+                     f"kernels, and the streaming attention cannot take the shape: {why_not}")
+
+
+def _qkv_head_views(t, L, H, dk):
+    """q / k / v (or their gradients) as head views of a [B L, H 3 dk] matrix, per head [q | k | v]: no permuted copies."""
+    W = 3 * H * dk
+    return [bl_head_view_t(t.data_ptr() + 4 * which * dk, L * W, 3 * dk, W) for which in range(3)]
+
+
+def _row_head_view(t, L, H, dk):
+    """[B L, H dk] as a [B, H, L, dk] head view."""
+    return bl_head_view_t(t.data_ptr(), L * H * dk, dk, H * dk)
+
+
+def _edge_ptrs(edges):
+    if edges.num_entries > 0:
+        return _i32(edges.row_ptr).data_ptr(), _i32(edges.key).data_ptr(), _i32(edges.code).data_ptr()
+    return None, None, None
+
+
+def _stream_attention_fwd(ctx, qkv, lens, edges, bias_f, bias_r, B, L, H, dk, T, drop):
+    lib = load_library()
+    G, D = B * H, H * dk
+    scale = float(dk) ** -0.5
+    out = torch.empty((B * L, D), dtype=torch.float32, device=qkv.device)
+    lse = torch.empty((G * L,), dtype=torch.float32, device=qkv.device)
+    q, k, v = _qkv_head_views(qkv, L, H, dk)
+    o = _row_head_view(out, L, H, dk)
+    with _timed("attn_stream_fwd", 4.0 * G * L * L * dk, nbytes=4.0 * G * L * (4 * dk + 1)):
+        _check(lib.bl_rel_attn_stream_fwd(ctypes.byref(q), scale, ctypes.byref(k), ctypes.byref(v), *_edge_ptrs(edges), B, L, H, dk, T,
+                                          _f32(bias_f).data_ptr(), _f32(bias_r).data_ptr(), _i32(lens).data_ptr(), drop.c(), ctypes.byref(o),
+                                          lse.data_ptr(), _stream()), "bl_rel_attn_stream_fwd")
+    # (the backward recomputes the probabilities from qkv and lse and sums delta from them: the context itself is not kept)
+    ctx.saved = (qkv, lse, lens, edges, bias_f, bias_r, B, L, H, dk, T, drop, scale)
+    return out
+
+
+def _stream_attention_bwd(ctx, g_out):
+    qkv, lse, lens, edges, bias_f, bias_r, B, L, H, dk, T, drop, scale = _take_saved(ctx)
+    lib = load_library()
+    G, D = B * H, H * dk
+    g_out = _f32(g_out.contiguous())
+    g_qkv = torch.empty((B * L, 3 * D), dtype=torch.float32, device=g_out.device)
+    delta = torch.empty((G * L,), dtype=torch.float32, device=g_out.device)
+    (g_bf, r_bf), (g_br, r_br) = _grad_target(bias_f), _grad_target(bias_r)
+    q, k, v = _qkv_head_views(qkv, L, H, dk)
+    gq, gk, gv = _qkv_head_views(g_qkv, L, H, dk)
+    go = _row_head_view(g_out, L, H, dk)
+    with _timed("attn_stream_bwd", 18.0 * G * L * L * dk, nbytes=4.0 * G * L * (10 * dk + 4)):
+        _check(lib.bl_rel_attn_stream_bwd(ctypes.byref(go), lse.data_ptr(), ctypes.byref(q), scale, ctypes.byref(k), ctypes.byref(v),
+                                          *_edge_ptrs(edges), B, L, H, dk, T, bias_f.data_ptr(), bias_r.data_ptr(), _i32(lens).data_ptr(),
+                                          drop.c(), delta.data_ptr(), ctypes.byref(gq), ctypes.byref(gk), ctypes.byref(gv),
+                                          g_bf.data_ptr(), g_br.data_ptr(), _stream()), "bl_rel_attn_stream_bwd")
+    return g_qkv, None, None, r_bf, r_br, None, None, None, None, None, None, None, None, None
+
+
 class _RelAttention(torch.autograd.Function):
     """Relational multi-head self-attention between the QKV projection and the output projection
     (reference multihead_attention.py:46-80, relational_multihead_attention.py:72-178).  Q.K^T, P.V and their four
@@ -89,6 +186,9 @@ class _RelAttention(torch.autograd.Function):
     def forward(ctx, qkv, lens, edges: RelEdges, bias_f, bias_r, vb_f, vb_r, B, L, H, dk, T, scalar_bias, drop: Dropout):
         lib = load_library()
         _f32(qkv, "qkv")
+        ctx.path = attention_path(L, dk, T, scalar_bias, vb_f is not None)
+        if ctx.path == "stream":
+            return _stream_attention_fwd(ctx, qkv, lens, edges, bias_f, bias_r, B, L, H, dk, T, drop)
         G, D = B * H, H * dk
         st = _stream()
         scale = float(dk) ** -0.5
@@ -137,6 +237,8 @@ class _RelAttention(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_out):
+        if ctx.path == "stream":
+            return _stream_attention_bwd(ctx, g_out)
         qs, kt, vt, P, Pd, lens, edges, bias_f, bias_r, vb_f, vb_r, B, L, H, dk, T, mode, drop, gptr, scale = _take_saved(ctx)
         lib = load_library()
         G, D = B * H, H * dk

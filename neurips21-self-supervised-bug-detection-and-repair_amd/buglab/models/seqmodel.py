@@ -141,6 +141,9 @@ class SeqBugLabModel(AbstractNeuralModel, AbstractBugLabModel):
         self._init()
         from functools import partial
 
+        if layer_type != "gru" and max_seq_size > MAX_POSITIONS:  # (the GRU reads no positions: reference seqmodel.py:363)
+            raise ValueError(f"max_seq_size = {max_seq_size} exceeds the {MAX_POSITIONS} rows of the positional table (MAX_POSITIONS): a "
+                             f"`seq-{layer_type}` model cannot place tokens beyond position {MAX_POSITIONS - 1}")
         self._edge_kinds_seen = set()
         self.edge_types: Optional[List[str]] = None
         self._dropout_rate, self._representation_size, self._layer_type = dropout_rate, representation_size, layer_type
