@@ -70,6 +70,15 @@ enum {
       return BL_EINVAL;           \
     }                             \
   } while (0)
+// the same for a size the kernels were not built for, such as an index space that int32 indices cannot address
+#define BL_CHECK_RANGE(cond, ...) \
+  do {                            \
+    if (!(cond)) {                \
+      bl_set_error(__VA_ARGS__);  \
+      return BL_ERANGE;           \
+    }                             \
+  } while (0)
+static inline bool bl_fits_int32(int64_t v) { return v <= (int64_t)0x7fffffff; }
 #define BL_LAUNCH_CHECK(name)                                            \
   do {                                                                   \
     hipError_t e_ = hipGetLastError();                                   \

@@ -12,14 +12,14 @@
 // bl_conf_loc_stats / bl_conf_group_stats   one WAVE per segment, lanes stride over its entries (three passes: maximum, the
 //   sums, the centred second moment), so a segment may be longer than a wave or a workgroup.  Each segment's six (three)
 //   partials are written first; a second kernel sums every column over the segments in an order that depends on nothing but
-//   the number of segments (thread t takes segments t, t + 256, ..., then a fixed tree): bit-reproducible, whatever the
-//   geometry of the first launch.
+//   the number of segments (thread t takes segments t, t + 256, ..., then bl_tree_sum_f64), whatever the geometry of the
+//   first launch.
 // bl_conf_apply   one wave per location segment and per repair group of a minibatch's flat output, in place: fp64 inside,
 //   rounded once to fp32.  A wave reads everything it needs of its segment before the pass that writes, and no two segments
 //   share an entry.
-// Plain vector loads and stores only, no atomics.
+// Plain vector loads and stores only, no atomics; the reductions and the first-maximum rule are bl_segment_f64.h's.
 #include "bl_common.h"
-#include "bl_first_max.h"  // rp_better, rp_wave_argmax
+#include "bl_segment_f64.h"
 
 #pragma clang fp contract(off)
 
@@ -28,16 +28,6 @@ constexpr int CF_THREADS = 256;
 constexpr int CF_WAVES = CF_THREADS / BL_WAVE;
 constexpr int CF_LOC_COLS = 6;    // F | dF/dbeta | dF/dbias | d2F/dbeta2 | d2F/dbeta dbias | d2F/dbias2
 constexpr int CF_GROUP_COLS = 3;  // F | dF/dbeta | d2F/dbeta2
-
-__device__ __forceinline__ double cf_wave_sum(double v) {
-#pragma unroll
-  for (int o = BL_WAVE / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, BL_WAVE);
-  return v;
-}
-
-__device__ __forceinline__ bool cf_counts(double l) { return l > -__builtin_huge_val(); }  // false for -inf and NaN
-
-__device__ __forceinline__ int64_t cf_clamp(int64_t v, int64_t hi) { return v < 0 ? (int64_t)0 : (v > hi ? hi : v); }
 
 // One segment's terms, by one wave.  v: its n entries; y: the target's place; NOBUG: the last entry takes the bias.
 // r = F, dF/dbeta, dF/dbias, d2F/dbeta2, d2F/dbeta dbias, d2F/dbias2 (the same in every lane).
@@ -56,14 +46,14 @@ __device__ __forceinline__ void cf_segment_stats(const float* __restrict__ v, in
   int im = -1;
   for (int i = lane; i < n; i += BL_WAVE) {
     const double l = (double)v[i];
-    if (!cf_counts(l)) continue;
+    if (!bl_has_prob(l)) continue;
     const double z = z_of(i, l);
-    if (rp_better(z, i, m, im)) {
+    if (bl_better(z, i, m, im)) {
       m = z;
       im = i;
     }
   }
-  rp_wave_argmax(m, im);
+  bl_wave_argmax(m, im);
   if (im < 0 || y < 0 || y >= n) {  // nothing with a probability, or a target outside the segment: the host sends neither
 #pragma unroll
     for (int c = 0; c < CF_LOC_COLS; ++c) r[c] = __builtin_nan("");
@@ -72,33 +62,33 @@ __device__ __forceinline__ void cf_segment_stats(const float* __restrict__ v, in
   double zp = 0.0, s1 = 0.0;
   for (int i = lane; i < n; i += BL_WAVE) {
     const double l = (double)v[i];
-    if (!cf_counts(l)) continue;
+    if (!bl_has_prob(l)) continue;
     const double w = exp(z_of(i, l) - m);
     if (i != im) zp += w;
     s1 += w * l;
   }
-  zp = cf_wave_sum(zp);
-  s1 = cf_wave_sum(s1);
+  zp = bl_wave_sum_f64(zp);
+  s1 = bl_wave_sum_f64(s1);
   const double Z = 1.0 + zp;
   const double E = s1 / Z;  // the mean of l under the calibrated distribution
   double var = 0.0;
   for (int i = lane; i < n; i += BL_WAVE) {
     const double l = (double)v[i];
-    if (!cf_counts(l)) continue;
+    if (!bl_has_prob(l)) continue;
     const double w = exp(z_of(i, l) - m);
     const double d = l - E;
     var += w * (d * d);
   }
-  var = cf_wave_sum(var);
+  var = bl_wave_sum_f64(var);
   const double ly = (double)v[y];
   r[0] = log1p(zp) + (m - z_of(y, ly));  // two terms >= 0
   r[1] = E - ly;
   r[3] = var / Z;
   if (NOBUG) {
     const double ll = (double)v[n - 1];
-    const double p = cf_counts(ll) ? exp(z_of(n - 1, ll) - m) / Z : 0.0;
+    const double p = bl_has_prob(ll) ? exp(z_of(n - 1, ll) - m) / Z : 0.0;
     r[2] = p - (y == n - 1 ? 1.0 : 0.0);
-    r[4] = cf_counts(ll) ? p * (ll - E) : 0.0;
+    r[4] = bl_has_prob(ll) ? p * (ll - E) : 0.0;
     r[5] = p * (1.0 - p);
   }
 }
@@ -109,9 +99,10 @@ __global__ __launch_bounds__(CF_THREADS) void conf_stats_kernel(const float* __r
                                                                 int nseg, double beta, double bias, double* __restrict__ partials) {
   const int s = blockIdx.x * CF_WAVES + threadIdx.x / BL_WAVE, lane = threadIdx.x % BL_WAVE;
   if (s >= nseg) return;  // whole waves leave; nothing below synchronises the workgroup
-  const int64_t a = cf_clamp(seg_off[s], n_vals), b = cf_clamp(seg_off[s + 1], n_vals);
+  int64_t a;
+  const int n = (int)bl_csr_row(seg_off, s, n_vals, a);
   double r[CF_LOC_COLS];
-  cf_segment_stats<NOBUG>(vals + a, (int)(b > a ? b - a : 0), tgt[s], beta, bias, lane, r);
+  cf_segment_stats<NOBUG>(vals + a, n, tgt[s], beta, bias, lane, r);
   if (lane == 0) {
     if (NOBUG) {
 #pragma unroll
@@ -130,12 +121,7 @@ __global__ __launch_bounds__(CF_THREADS) void conf_reduce_kernel(const double* _
   const double* p = partials + (int64_t)blockIdx.x * nseg;
   double acc = 0.0;
   for (int i = threadIdx.x; i < nseg; i += CF_THREADS) acc += p[i];
-  s_acc[threadIdx.x] = acc;
-  __syncthreads();
-  for (int o = CF_THREADS / 2; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) s_acc[threadIdx.x] += s_acc[threadIdx.x + o];
-    __syncthreads();
-  }
+  bl_tree_sum_f64<CF_THREADS>(acc, s_acc);
   if (threadIdx.x == 0) out[blockIdx.x] = s_acc[0];
 }
 
@@ -153,29 +139,29 @@ __device__ __forceinline__ void cf_segment_apply(float* __restrict__ flat, int n
     const int64_t j = at(i);
     if (j < 0) continue;
     const double l = (double)flat[j];
-    if (!cf_counts(l)) continue;
+    if (!bl_has_prob(l)) continue;
     const double z = z_of(i, l);
-    if (rp_better(z, i, m, im)) {
+    if (bl_better(z, i, m, im)) {
       m = z;
       im = i;
     }
   }
-  rp_wave_argmax(m, im);
+  bl_wave_argmax(m, im);
   if (im < 0) return;  // wave-uniform
   double zp = 0.0;
   for (int i = lane; i < n; i += BL_WAVE) {
     const int64_t j = at(i);
     if (j < 0 || i == im) continue;
     const double l = (double)flat[j];
-    if (cf_counts(l)) zp += exp(z_of(i, l) - m);
+    if (bl_has_prob(l)) zp += exp(z_of(i, l) - m);
   }
-  zp = cf_wave_sum(zp);  // every load above has returned before any lane goes on to store
+  zp = bl_wave_sum_f64(zp);  // every load above has returned before any lane goes on to store
   const double lz = log1p(zp);
   for (int i = lane; i < n; i += BL_WAVE) {
     const int64_t j = at(i);
     if (j < 0) continue;
     const double l = (double)flat[j];
-    if (cf_counts(l)) flat[j] = (float)((z_of(i, l) - m) - lz);
+    if (bl_has_prob(l)) flat[j] = (float)((z_of(i, l) - m) - lz);
   }
 }
 
@@ -185,14 +171,15 @@ __global__ __launch_bounds__(CF_THREADS) void conf_apply_kernel(float* __restric
                                                                 int64_t item_base, double beta, double bias, double repair_beta) {
   const int s = blockIdx.x * CF_WAVES + threadIdx.x / BL_WAVE, lane = threadIdx.x % BL_WAVE;
   if (s < B) {  // sample s: its candidates flat[candidate_ptr[s] : candidate_ptr[s + 1]], then NO_BUG at flat[C + s]
-    const int64_t c0 = cf_clamp(candidate_ptr[s], C), c1 = cf_clamp(candidate_ptr[s + 1], C);
-    const int nc = (int)(c1 > c0 ? c1 - c0 : 0);
+    int64_t c0;
+    const int nc = (int)bl_csr_row(candidate_ptr, s, C, c0);
     cf_segment_apply(flat, nc + 1, [&](int i) { return i < nc ? c0 + i : C + s; }, beta, bias, true, lane);
   } else if (s - B < G) {
     const int g = s - B;
-    const int64_t g0 = cf_clamp(group_ptr[g], n_items), g1 = cf_clamp(group_ptr[g + 1], n_items);
+    int64_t g0;
+    const int ng = (int)bl_csr_row(group_ptr, g, n_items, g0);
     cf_segment_apply(
-        flat, (int)(g1 > g0 ? g1 - g0 : 0),
+        flat, ng,
         [&](int i) {
           const int32_t it = group_items[g0 + i];
           return (it >= 0 && (int64_t)it < n_items) ? item_base + it : (int64_t)-1;
@@ -206,10 +193,7 @@ bool cf_scale_ok(double beta) { return beta > 0.0 && beta < __builtin_huge_val()
 int cf_stats(const char* who, bool nobug, const float* vals, int64_t n_vals, const int32_t* seg_off, const int32_t* tgt, int32_t nseg,
              double beta, double bias, double* partials, double* out, void* stream) {
   BL_CHECK_ARG(nseg >= 0 && n_vals >= 0, "%s: negative size (nseg %d, n_vals %lld)", who, (int)nseg, (long long)n_vals);
-  if (n_vals > (int64_t)0x7fffffff) {
-    bl_set_error("%s: pool beyond int32 offsets (n_vals %lld)", who, (long long)n_vals);
-    return BL_ERANGE;
-  }
+  BL_CHECK_RANGE(bl_fits_int32(n_vals), "%s: pool beyond int32 offsets (n_vals %lld)", who, (long long)n_vals);
   BL_CHECK_ARG(cf_scale_ok(beta) && bias - bias == 0.0, "%s: beta must be finite and > 0 and the bias finite (beta %g, bias %g)", who, beta,
                bias);
   BL_CHECK_ARG(out, "%s: null out", who);
@@ -248,10 +232,8 @@ extern "C" int bl_conf_apply(float* flat, int64_t n_flat, const int32_t* candida
   BL_CHECK_ARG(B >= 0 && G >= 0 && C >= 0 && n_flat >= 0 && n_items >= 0 && item_base >= 0,
                "bl_conf_apply: negative size (B %d, G %d, C %lld, n_flat %lld, n_items %lld, item_base %lld)", (int)B, (int)G, (long long)C,
                (long long)n_flat, (long long)n_items, (long long)item_base);
-  if (n_flat > (int64_t)0x7fffffff || (int64_t)B + (int64_t)G > (int64_t)0x7fffffff - CF_WAVES) {
-    bl_set_error("bl_conf_apply: index space beyond int32 (n_flat %lld, B %d, G %d)", (long long)n_flat, (int)B, (int)G);
-    return BL_ERANGE;
-  }
+  BL_CHECK_RANGE(bl_fits_int32(n_flat) && bl_fits_int32((int64_t)B + (int64_t)G + CF_WAVES),
+                 "bl_conf_apply: index space beyond int32 (n_flat %lld, B %d, G %d)", (long long)n_flat, (int)B, (int)G);
   BL_CHECK_ARG(cf_scale_ok(beta) && cf_scale_ok(repair_beta) && bias - bias == 0.0,
                "bl_conf_apply: beta and repair_beta must be finite and > 0 and the bias finite (beta %g, repair_beta %g, bias %g)", beta,
                repair_beta, bias);

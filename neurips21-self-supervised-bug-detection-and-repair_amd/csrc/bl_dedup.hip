@@ -21,6 +21,7 @@
 //                         a duplicate iff, in some band, the smallest number filed under its key is below i.  That is the answer
 //                         of inserting the documents one at a time in number order, for every batch split.
 #include "bl_common.h"
+#include "bl_segment_f64.h"  // bl_clamp_off
 
 namespace {
 constexpr int DD_THREADS = 256;
@@ -28,7 +29,6 @@ constexpr int DD_CHUNK = 1024;  // token hashes staged in LDS per pass
 constexpr uint32_t DD_EMPTY = 0xFFFFFFFFu;
 constexpr uint64_t DD_MERSENNE = (1ull << 61) - 1;
 
-__device__ __forceinline__ int64_t dd_clamp(int64_t v, int64_t hi) { return v < 0 ? (int64_t)0 : (v > hi ? hi : v); }
 __device__ __forceinline__ uint32_t dd_rotl(uint32_t x, int n) { return (x << n) | (x >> (32 - n)); }
 
 // byte i of the padded message: the token, 0x80, zeros, the bit length as a big-endian uint64 in the last 8 bytes
@@ -45,7 +45,7 @@ __global__ __launch_bounds__(DD_THREADS) void dedup_sha1_kernel(const uint8_t* _
                                                                 uint32_t* __restrict__ out) {
   const int64_t t = (int64_t)blockIdx.x * DD_THREADS + threadIdx.x;
   if (t >= ntokens) return;
-  const int64_t o0 = dd_clamp(tok_off[t], nbytes), o1 = dd_clamp(tok_off[t + 1], nbytes);
+  const int64_t o0 = bl_clamp_off(tok_off[t], nbytes), o1 = bl_clamp_off(tok_off[t + 1], nbytes);
   const int64_t len = o1 > o0 ? o1 - o0 : 0;
   const uint8_t* msg = bytes + o0;
   const int64_t total = (len + 9 + 63) / 64 * 64;  // 56 bytes and more need a second block, 120 and more a third
@@ -108,7 +108,7 @@ __global__ __launch_bounds__(DD_THREADS) void dedup_minhash_kernel(const uint32_
   const int k = threadIdx.x;
   const bool live = k < num_perm;
   const uint64_t a = live ? perm_a[k] : 1u, b = live ? perm_b[k] : 0u;
-  const int64_t t0 = dd_clamp(doc_off[doc], nhashes), t1 = dd_clamp(doc_off[doc + 1], nhashes);
+  const int64_t t0 = bl_clamp_off(doc_off[doc], nhashes), t1 = bl_clamp_off(doc_off[doc + 1], nhashes);
   uint32_t best = 0xFFFFFFFFu;
   for (int64_t base = t0; base < t1; base += DD_CHUNK) {
     const int n = (int)(t1 - base < DD_CHUNK ? t1 - base : DD_CHUNK);
@@ -189,10 +189,8 @@ extern "C" int bl_dedup_sha1_u32(const uint8_t* bytes, int64_t nbytes, const int
   BL_CHECK_ARG(ntokens == 0 || (tok_off && out), "bl_dedup_sha1_u32: null tok_off / out");
   BL_CHECK_ARG(nbytes == 0 || bytes, "bl_dedup_sha1_u32: null bytes with nbytes %lld", (long long)nbytes);
   const int64_t blocks = (ntokens + DD_THREADS - 1) / DD_THREADS;
-  if (blocks > 0x7fffffff) {
-    bl_set_error("bl_dedup_sha1_u32: %lld tokens in one call, at most %lld", (long long)ntokens, (long long)0x7fffffff * DD_THREADS);
-    return BL_ERANGE;
-  }
+  BL_CHECK_RANGE(bl_fits_int32(blocks), "bl_dedup_sha1_u32: %lld tokens in one call, at most %lld", (long long)ntokens,
+                 (long long)0x7fffffff * DD_THREADS);
   if (ntokens == 0) return BL_OK;
   hipLaunchKernelGGL(dedup_sha1_kernel, dim3((unsigned)blocks), dim3(DD_THREADS), 0, (hipStream_t)stream, bytes, nbytes, tok_off,
                      ntokens, out);
@@ -209,10 +207,7 @@ extern "C" int bl_dedup_minhash(const uint32_t* hashes, int64_t nhashes, const i
                (long long)ndocs);
   BL_CHECK_ARG(ndocs == 0 || (doc_off && perm_a && perm_b && sigs), "bl_dedup_minhash: null doc_off / perm_a / perm_b / sigs");
   BL_CHECK_ARG(nhashes == 0 || hashes, "bl_dedup_minhash: null hashes with nhashes %lld", (long long)nhashes);
-  if (ndocs > 0x7fffffff) {
-    bl_set_error("bl_dedup_minhash: %lld documents in one call, at most %d", (long long)ndocs, 0x7fffffff);
-    return BL_ERANGE;
-  }
+  BL_CHECK_RANGE(bl_fits_int32(ndocs), "bl_dedup_minhash: %lld documents in one call, at most %d", (long long)ndocs, 0x7fffffff);
   if (ndocs == 0) return BL_OK;
   const int threads = (num_perm + BL_WAVE - 1) / BL_WAVE * BL_WAVE;
   hipLaunchKernelGGL(dedup_minhash_kernel, dim3((unsigned)ndocs), dim3(threads), 0, (hipStream_t)stream, hashes, nhashes, doc_off, perm_a,
@@ -241,10 +236,8 @@ extern "C" int bl_dedup_lsh_insert_query(const uint32_t* sigs, int32_t num_perm,
                (long long)(total - query_from));
   const int64_t nins = (total - insert_from) * bands, nq = (total - query_from) * bands;
   const int64_t bins = (nins + DD_THREADS - 1) / DD_THREADS, bq = (nq + DD_THREADS - 1) / DD_THREADS;
-  if (total >= 0x7fffffff || bins > 0x7fffffff || bq > 0x7fffffff) {
-    bl_set_error("bl_dedup_lsh_insert_query: %lld documents: document numbers and launch sizes are 31-bit", (long long)total);
-    return BL_ERANGE;
-  }
+  BL_CHECK_RANGE(total < 0x7fffffff && bl_fits_int32(bins) && bl_fits_int32(bq),
+                 "bl_dedup_lsh_insert_query: %lld documents: document numbers and launch sizes are 31-bit", (long long)total);
   if (bins > 0) {
     hipLaunchKernelGGL(dedup_lsh_insert_kernel, dim3((unsigned)bins), dim3(DD_THREADS), 0, (hipStream_t)stream, sigs, (int)num_perm,
                        (int)bands, (int)rows, table, slots, insert_from, total - insert_from, status);

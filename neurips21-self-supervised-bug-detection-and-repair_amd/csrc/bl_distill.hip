@@ -17,11 +17,11 @@
 // distill_segment_kernel   one WAVE per segment, lanes stride over its entries (three passes: the maxima, the sums, KL and
 //   delta), so a segment may be longer than a wave.  Lane 0 writes the segment's KL and its flags.
 // distill_reduce_kernel    out[c], one workgroup each, sums its column over its range of segments in an order that depends on
-//   nothing but the number of segments (thread t takes t, t + 256, ..., then a fixed tree): bit-reproducible.
+//   nothing but the number of segments (thread t takes t, t + 256, ..., then bl_tree_sum_f64).
 // distill_bwd_kernel       elementwise: g * delta / tau.
-// Plain vector loads and stores only, no atomics.
+// Plain vector loads and stores only, no atomics; the reductions and the first-maximum rule are bl_segment_f64.h's.
 #include "bl_common.h"
-#include "bl_first_max.h"  // rp_better, rp_wave_argmax
+#include "bl_segment_f64.h"
 
 #pragma clang fp contract(off)
 
@@ -30,16 +30,6 @@ constexpr int DS_THREADS = 256;
 constexpr int DS_WAVES = DS_THREADS / BL_WAVE;
 constexpr int DS_OUT = 8;
 constexpr double DS_DISTILLED = 1.0, DS_AGREE = 2.0, DS_SKIPPED = 4.0;  // a segment's flags, summed into one double
-
-__device__ __forceinline__ double ds_wave_sum(double v) {
-#pragma unroll
-  for (int o = BL_WAVE / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, BL_WAVE);
-  return v;
-}
-
-__device__ __forceinline__ bool ds_counts(double t) { return t > -__builtin_huge_val(); }  // false for -inf and NaN
-
-__device__ __forceinline__ int64_t ds_clamp(int64_t v, int64_t hi) { return v < 0 ? (int64_t)0 : (v > hi ? hi : v); }
 
 // One segment by one wave.  at(i, z, t, dst): entry i's student logit, teacher value and where its delta goes (-1: nowhere);
 // returns false for an entry to leave out.  -> the segment's KL and flags (the same in every lane).
@@ -52,22 +42,22 @@ __device__ __forceinline__ void ds_segment(int n, At at, double tau, float* __re
     int64_t dst;
     if (!at(i, z, t, dst)) continue;
     const double a = z / tau;
-    // (a NaN logit may enter as a lane's first entry: bl_first_max.h leaves NaNs to its callers, and here the segment's sums
+    // (a NaN logit may enter as a lane's first entry: bl_segment_f64.h leaves NaNs to its callers, and here the segment's sums
     // and with them the loss are NaN whichever entry the maximum falls on; only the agreement counter could differ)
-    if (rp_better(a, i, ms, is)) {
+    if (bl_better(a, i, ms, is)) {
       ms = a;
       is = i;
     }
-    if (ds_counts(t)) {
+    if (bl_has_prob(t)) {
       const double u = t / tau;
-      if (rp_better(u, i, mt, it)) {
+      if (bl_better(u, i, mt, it)) {
         mt = u;
         it = i;
       }
     }
   }
-  rp_wave_argmax(ms, is);
-  rp_wave_argmax(mt, it);
+  bl_wave_argmax(ms, is);
+  bl_wave_argmax(mt, it);
   kl = 0.0;
   if (it < 0) {  // wave-uniform: no teacher entry with a probability (or no entry at all)
     for (int i = lane; i < n; i += BL_WAVE) {
@@ -84,10 +74,10 @@ __device__ __forceinline__ void ds_segment(int n, At at, double tau, float* __re
     int64_t dst;
     if (!at(i, z, t, dst)) continue;
     ss += exp(z / tau - ms);
-    if (ds_counts(t)) st += exp(t / tau - mt);
+    if (bl_has_prob(t)) st += exp(t / tau - mt);
   }
-  ss = ds_wave_sum(ss);
-  st = ds_wave_sum(st);
+  ss = bl_wave_sum_f64(ss);
+  st = bl_wave_sum_f64(st);
   const double ls = log(ss), lt = log(st);
   double acc = 0.0;
   for (int i = lane; i < n; i += BL_WAVE) {
@@ -97,14 +87,14 @@ __device__ __forceinline__ void ds_segment(int n, At at, double tau, float* __re
     const double da = z / tau - ms;
     const double q = exp(da) / ss;
     double p = 0.0;
-    if (ds_counts(t)) {
+    if (bl_has_prob(t)) {
       const double du = t / tau - mt;
       p = exp(du) / st;
       if (p > 0.0) acc += p * ((du - lt) - (da - ls));
     }
     if (dst >= 0) delta[dst] = (float)(q - p);
   }
-  kl = ds_wave_sum(acc);
+  kl = bl_wave_sum_f64(acc);
   flags = DS_DISTILLED + (is == it ? DS_AGREE : 0.0);
 }
 
@@ -118,8 +108,8 @@ __global__ __launch_bounds__(DS_THREADS) void distill_segment_kernel(
   if (s >= S) return;  // whole waves leave; nothing below synchronises the workgroup
   double kl, flags;
   if (s < B) {
-    const int64_t c0 = ds_clamp(candidate_ptr[s], C), c1 = ds_clamp(candidate_ptr[s + 1], C);
-    const int nc = (int)(c1 > c0 ? c1 - c0 : 0);
+    int64_t c0;
+    const int nc = (int)bl_csr_row(candidate_ptr, s, C, c0);
     ds_segment(
         nc + 1,
         [&](int i, double& z, double& t, int64_t& dst) {
@@ -137,9 +127,10 @@ __global__ __launch_bounds__(DS_THREADS) void distill_segment_kernel(
         tau, delta, lane, kl, flags);
   } else {
     const int g = s - B;
-    const int64_t g0 = ds_clamp(group_ptr[g], R), g1 = ds_clamp(group_ptr[g + 1], R);
+    int64_t g0;
+    const int ng = (int)bl_csr_row(group_ptr, g, R, g0);
     ds_segment(
-        (int)(g1 > g0 ? g1 - g0 : 0),
+        ng,
         [&](int i, double& z, double& t, int64_t& dst) {
           const int32_t item = group_items[g0 + i];
           if (item < 0 || (int64_t)item >= R) return false;  // the host never sends one
@@ -173,12 +164,7 @@ __global__ __launch_bounds__(DS_THREADS) void distill_reduce_kernel(const double
       }
     }
   }
-  s_acc[threadIdx.x] = acc;
-  __syncthreads();
-  for (int o = DS_THREADS / 2; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) s_acc[threadIdx.x] += s_acc[threadIdx.x + o];
-    __syncthreads();
-  }
+  bl_tree_sum_f64<DS_THREADS>(acc, s_acc);
   if (threadIdx.x == 0) out[c] = (float)s_acc[0];
 }
 
@@ -198,10 +184,8 @@ bool ds_tau_ok(double tau) { return tau > 0.0 && tau < __builtin_huge_val(); }
 int ds_check_sizes(const char* who, int64_t B, int64_t G, int64_t C, int64_t R) {
   BL_CHECK_ARG(B >= 0 && G >= 0 && C >= 0 && R >= 0, "%s: negative size (B %lld, G %lld, C %lld, R %lld)", who, (long long)B, (long long)G,
                (long long)C, (long long)R);
-  if (C + R > (int64_t)0x7fffffff - DS_THREADS || B + G > (int64_t)0x7fffffff - DS_WAVES || C + B > (int64_t)0x7fffffff) {
-    bl_set_error("%s: index space beyond int32 (B %lld, G %lld, C %lld, R %lld)", who, (long long)B, (long long)G, (long long)C, (long long)R);
-    return BL_ERANGE;
-  }
+  BL_CHECK_RANGE(bl_fits_int32(C + R + DS_THREADS) && bl_fits_int32(B + G + DS_WAVES) && bl_fits_int32(C + B),
+                 "%s: index space beyond int32 (B %lld, G %lld, C %lld, R %lld)", who, (long long)B, (long long)G, (long long)C, (long long)R);
   return BL_OK;
 }
 }  // namespace

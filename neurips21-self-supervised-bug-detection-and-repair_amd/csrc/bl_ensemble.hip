@@ -7,17 +7,17 @@
 // canonical layout per sample: locations = np.unique(reference_nodes) ascending then NO_BUG, rewrites by original index.
 //
 // One launch, one workgroup per sample (4 waves):
-//   consensus only: wave w computes the first-maximum location of members w, w + 4, ... (wave64 arg-max, NaN as Python's
-//                   `max` treats it), results in LDS;
+//   consensus only: wave w computes the first-maximum location of members w, w + 4, ... (bl_wave_argmax of bl_segment_f64.h,
+//                   NaN as Python's `max` treats it), results in LDS;
 //   every kind:     the threads stride over the sample's location and rewrite entries; each entry folds the present members
 //                   in member order: r = a_0 + w, r = logaddexp(r, a_m + w), w = -log(M') -- numpy's logaddexp, in fp64.
 // No atomics, a fixed member order: results are bit-identical from run to run.
 #include "bl_common.h"
+#include "bl_segment_f64.h"
 
 namespace {
 constexpr int EN_THREADS = 256;
 constexpr int EN_WAVES = EN_THREADS / BL_WAVE;
-constexpr int EN_NONE = 0x7fffffff;
 
 // numpy's npy_logaddexp: equal inputs (infinities of one sign included) -> x + ln 2; a NaN input -> NaN
 __device__ __forceinline__ double en_logaddexp(double x, double y) {
@@ -45,10 +45,8 @@ __global__ __launch_bounds__(EN_THREADS) void ensemble_combine_kernel(const floa
   __shared__ int s_arg[BL_ENSEMBLE_MAX_MEMBERS];
   const int b = blockIdx.x;
   const int tid = threadIdx.x, lane = tid % BL_WAVE, wave = tid / BL_WAVE;
-  auto clamp = [](int64_t v, int64_t hi) { return v < 0 ? (int64_t)0 : (v > hi ? hi : v); };
-  const int64_t l0 = clamp(loc_off[b], total_loc), l1 = clamp(loc_off[b + 1], total_loc);
-  const int64_t r0 = clamp(rw_off[b], total_rw), r1 = clamp(rw_off[b + 1], total_rw);
-  const int64_t nloc = l1 > l0 ? l1 - l0 : 0, nrw = r1 > r0 ? r1 - r0 : 0;
+  int64_t l0, r0;
+  const int64_t nloc = bl_csr_row(loc_off, b, total_loc, l0), nrw = bl_csr_row(rw_off, b, total_rw, r0);
 
   // a member is absent from a sample when its gather indices there are -1 (the host writes all of them or none)
   if (tid < M) s_active[tid] = nloc > 0 && loc_idx[(int64_t)tid * total_loc + l0] >= 0;
@@ -60,26 +58,18 @@ __global__ __launch_bounds__(EN_THREADS) void ensemble_combine_kernel(const floa
     for (int m = wave; m < M; m += EN_WAVES) {
       if (!s_active[m]) continue;  // wave-uniform
       float bv = 0.0f;
-      int bi = EN_NONE;
+      int bi = -1;
       for (int64_t i = lane; i < nloc; i += BL_WAVE) {
         const float v = en_load(src, n_src, loc_idx, total_loc, m, l0 + i);
-        if (v == v && (bi == EN_NONE || v > bv)) {
+        if (v == v && bl_better(v, (int)i, bv, bi)) {
           bv = v;
           bi = (int)i;
         }
       }
-#pragma unroll
-      for (int o = BL_WAVE / 2; o > 0; o >>= 1) {
-        const float ov = __shfl_xor(bv, o, BL_WAVE);
-        const int oi = __shfl_xor(bi, o, BL_WAVE);
-        if (oi != EN_NONE && (bi == EN_NONE || ov > bv || (ov == bv && oi < bi))) {
-          bv = ov;
-          bi = oi;
-        }
-      }
+      bl_wave_argmax(bv, bi);
       if (lane == 0) {
         const float first = en_load(src, n_src, loc_idx, total_loc, m, l0);
-        s_arg[m] = (first != first || bi == EN_NONE) ? 0 : bi;
+        s_arg[m] = (first != first || bi < 0) ? 0 : bi;  // a NaN in front wins
       }
     }
     __syncthreads();
@@ -127,16 +117,11 @@ extern "C" int bl_ensemble_combine(const float* src, int64_t n_src, const int32_
   BL_CHECK_ARG(B >= 0 && n_src >= 0 && total_loc >= 0 && total_rw >= 0,
                "bl_ensemble_combine: negative size (B %d, n_src %lld, total_loc %lld, total_rw %lld)", (int)B, (long long)n_src,
                (long long)total_loc, (long long)total_rw);
-  if (M > BL_ENSEMBLE_MAX_MEMBERS) {
-    bl_set_error("bl_ensemble_combine: M = %d members, at most %d supported", (int)M, BL_ENSEMBLE_MAX_MEMBERS);
-    return BL_ERANGE;
-  }
-  const int64_t imax = 0x7fffffff;
-  if (n_src > imax || (int64_t)M * total_loc > imax || (int64_t)M * total_rw > imax) {
-    bl_set_error("bl_ensemble_combine: index space beyond int32 (n_src %lld, M x total_loc %lld, M x total_rw %lld)", (long long)n_src,
+  BL_CHECK_RANGE(M <= BL_ENSEMBLE_MAX_MEMBERS, "bl_ensemble_combine: M = %d members, at most %d supported", (int)M,
+                 BL_ENSEMBLE_MAX_MEMBERS);
+  BL_CHECK_RANGE(bl_fits_int32(n_src) && bl_fits_int32((int64_t)M * total_loc) && bl_fits_int32((int64_t)M * total_rw),
+                 "bl_ensemble_combine: index space beyond int32 (n_src %lld, M x total_loc %lld, M x total_rw %lld)", (long long)n_src,
                  (long long)M * total_loc, (long long)M * total_rw);
-    return BL_ERANGE;
-  }
   BL_CHECK_ARG(loc_off && rw_off, "bl_ensemble_combine: null offset pointer");
   BL_CHECK_ARG(B == 0 || (src && loc_idx && out_loc), "bl_ensemble_combine: null src / loc_idx / out_loc");
   BL_CHECK_ARG(total_rw == 0 || (rw_idx && out_rw), "bl_ensemble_combine: null rw_idx / out_rw with %lld rewrite entries",

@@ -15,7 +15,7 @@
 //   1  predicted location: first maximum over the location entries in the order the host sends (the key order of the dict
 //      `predict` yields), by the rule of Python's max(): a NaN in front wins, a NaN elsewhere never does.  With assume_buggy the
 //      last entry (NO_BUG) is left out and the sum of exp(x - max) over the remaining entries is taken: per thread in stride
-//      order, wave butterfly, waves in wave order.
+//      order, then bl_block_sum_f64.
 //   2  best rewrite AT A NODE, for the predicted node and for the target's node in one pass over the rewrites: the host's loop
 //      that starts from -inf and takes a candidate only if it is strictly greater -- the lowest original index among the maxima;
 //      a NaN never wins; nothing but -inf (or no rewrite at that node) is "none".  Nodes are compared by identity (key_node /
@@ -23,31 +23,11 @@
 //   3  thread 0 writes confidence and warned | location_correct | repair_given_location | repaired.
 // Plain vector loads and stores only, no atomics; bit-identical from run to run.
 #include "bl_common.h"
-#include "bl_first_max.h"  // rp_load, rp_at, rp_better, rp_wave_argmax
+#include "bl_segment_f64.h"
 
 namespace {
 constexpr int EV_THREADS = 256;
 constexpr int EV_WAVES = EV_THREADS / BL_WAVE;
-
-// the workgroup's first maximum from every thread's candidate; all threads return the same pair.  s_v / s_i: EV_WAVES entries.
-__device__ __forceinline__ void ev_block_argmax(double& v, int& i, double* s_v, int* s_i) {
-  const int lane = threadIdx.x % BL_WAVE, wave = threadIdx.x / BL_WAVE;
-  rp_wave_argmax(v, i);
-  __syncthreads();  // the previous use of s_v / s_i has been read
-  if (lane == 0) {
-    s_v[wave] = v;
-    s_i[wave] = i;
-  }
-  __syncthreads();
-  v = s_v[0];
-  i = s_i[0];
-#pragma unroll
-  for (int w = 1; w < EV_WAVES; ++w)
-    if (s_i[w] >= 0 && rp_better(s_v[w], s_i[w], v, i)) {
-      v = s_v[w];
-      i = s_i[w];
-    }
-}
 
 __global__ __launch_bounds__(EV_THREADS) void eval_judge_kernel(
     const float* __restrict__ src, int64_t n_src, const int32_t* __restrict__ loc_idx, const int32_t* __restrict__ loc_off,
@@ -57,46 +37,37 @@ __global__ __launch_bounds__(EV_THREADS) void eval_judge_kernel(
   __shared__ double s_v[EV_WAVES];
   __shared__ int s_i[EV_WAVES];
   __shared__ double s_sum[EV_WAVES];
-  const int b = blockIdx.x, tid = threadIdx.x, lane = tid % BL_WAVE, wave = tid / BL_WAVE;
-  auto clamp = [](int64_t v, int64_t hi) { return v < 0 ? (int64_t)0 : (v > hi ? hi : v); };
-  const int64_t l0 = clamp(loc_off[b], total_loc), l1 = clamp(loc_off[b + 1], total_loc);
-  const int64_t r0 = clamp(rw_off[b], total_rw), r1 = clamp(rw_off[b + 1], total_rw);
-  const int n_all = (int)(l1 > l0 ? l1 - l0 : 0);
+  const int b = blockIdx.x, tid = threadIdx.x;
+  int64_t l0, r0;
+  const int n_all = (int)bl_csr_row(loc_off, b, total_loc, l0);
   const int n_loc = assume_buggy ? (n_all > 0 ? n_all - 1 : 0) : n_all;  // the entries the maximum is taken over
-  const int n_rw = (int)(r1 > r0 ? r1 - r0 : 0);
+  const int n_rw = (int)bl_csr_row(rw_off, b, total_rw, r0);
 
   // ---- 1: the predicted location
   double bv = 0.0;
   int bi = -1;
   for (int i = tid; i < n_loc; i += EV_THREADS) {
-    const double v = rp_load(src, n_src, loc_idx[l0 + i]);
-    if (v == v && rp_better(v, i, bv, bi)) {
+    const double v = bl_load_f64(src, n_src, loc_idx[l0 + i]);
+    if (v == v && bl_better(v, i, bv, bi)) {
       bv = v;
       bi = i;
     }
   }
-  ev_block_argmax(bv, bi, s_v, s_i);
+  bl_block_argmax<EV_WAVES>(bv, bi, s_v, s_i);
   int pred = -1;  // a sample without an entry to choose from (the host raises before it sends one)
   double conf = __builtin_nan("");
   if (n_loc > 0) {
-    const double first = rp_load(src, n_src, loc_idx[l0]);
+    const double first = bl_load_f64(src, n_src, loc_idx[l0]);
     pred = (first != first || bi < 0) ? 0 : bi;  // a NaN in front, or nothing but NaNs: Python's max() keeps the first
     conf = pred == bi ? bv : first;
   }
-  if (assume_buggy && n_loc > 0) {
+  if (assume_buggy && n_loc > 0) {  // uniform over the workgroup
     // log-sum-exp of the remaining entries: shift by their greatest non-NaN value (0 where that is infinite or absent, as
     // torch.logsumexp), every thread's terms in stride order, then the fixed tree
     const double shift = (bi >= 0 && bv - bv == 0.0) ? bv : 0.0;
     double sum = 0.0;
-    for (int i = tid; i < n_loc; i += EV_THREADS) sum += exp(rp_load(src, n_src, loc_idx[l0 + i]) - shift);
-#pragma unroll
-    for (int o = BL_WAVE / 2; o > 0; o >>= 1) sum += __shfl_xor(sum, o, BL_WAVE);
-    if (lane == 0) s_sum[wave] = sum;
-    __syncthreads();
-    sum = s_sum[0];
-#pragma unroll
-    for (int w = 1; w < EV_WAVES; ++w) sum += s_sum[w];
-    conf = conf - (shift + log(sum));
+    for (int i = tid; i < n_loc; i += EV_THREADS) sum += exp(bl_load_f64(src, n_src, loc_idx[l0 + i]) - shift);
+    conf = conf - (shift + log(bl_block_sum_f64<EV_WAVES>(sum, s_sum)));
   }
 
   // ---- 2: the best rewrite at the predicted node and at the target's node
@@ -109,19 +80,19 @@ __global__ __launch_bounds__(EV_THREADS) void eval_judge_kernel(
   for (int i = tid; i < n_rw; i += EV_THREADS) {
     const int32_t node = rw_node[r0 + i];
     if (node < 0 || (node != pnode && node != tnode)) continue;
-    const double v = rp_load(src, n_src, rw_idx[r0 + i]);
-    if (!(v > -__builtin_huge_val())) continue;  // NaN and -inf never beat the -inf the host's loop starts from
-    if (node == pnode && rp_better(v, i, pv, pi)) {
+    const double v = bl_load_f64(src, n_src, rw_idx[r0 + i]);
+    if (!bl_has_prob(v)) continue;  // NaN and -inf never beat the -inf the host's loop starts from
+    if (node == pnode && bl_better(v, i, pv, pi)) {
       pv = v;
       pi = i;
     }
-    if (node == tnode && rp_better(v, i, tv, ti)) {
+    if (node == tnode && bl_better(v, i, tv, ti)) {
       tv = v;
       ti = i;
     }
   }
-  ev_block_argmax(pv, pi, s_v, s_i);
-  ev_block_argmax(tv, ti, s_v, s_i);
+  bl_block_argmax<EV_WAVES>(pv, pi, s_v, s_i);
+  bl_block_argmax<EV_WAVES>(tv, ti, s_v, s_i);
 
   // ---- 3: the verdicts
   if (tid == 0) {
@@ -143,11 +114,9 @@ extern "C" int bl_eval_judge(const float* src, int64_t n_src, const int32_t* loc
   BL_CHECK_ARG(B >= 0 && n_src >= 0 && total_loc >= 0 && total_rw >= 0,
                "bl_eval_judge: negative size (B %d, n_src %lld, total_loc %lld, total_rw %lld)", (int)B, (long long)n_src,
                (long long)total_loc, (long long)total_rw);
-  if (n_src > (int64_t)0x7fffffff || total_loc > (int64_t)0x7fffffff || total_rw > (int64_t)0x7fffffff) {
-    bl_set_error("bl_eval_judge: index space beyond int32 (n_src %lld, total_loc %lld, total_rw %lld)", (long long)n_src,
+  BL_CHECK_RANGE(bl_fits_int32(n_src) && bl_fits_int32(total_loc) && bl_fits_int32(total_rw),
+                 "bl_eval_judge: index space beyond int32 (n_src %lld, total_loc %lld, total_rw %lld)", (long long)n_src,
                  (long long)total_loc, (long long)total_rw);
-    return BL_ERANGE;
-  }
   BL_CHECK_ARG(offset >= 0 && capacity >= 0 && offset <= capacity && (int64_t)B <= capacity - offset,
                "bl_eval_judge: samples %lld .. %lld do not fit the outcome buffers of %lld samples", (long long)offset,
                (long long)offset + (long long)B, (long long)capacity);

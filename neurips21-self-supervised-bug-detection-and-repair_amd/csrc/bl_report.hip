@@ -12,7 +12,7 @@
 // bl_report_summarize  one workgroup (4 waves) per sample.
 //   1  predicted location: first maximum over the sample's location entries in the order the host sends (the key order of the
 //      dict `predict` yields), by the rule of Python's max(): the first entry stays unless a later one is GREATER -- so a NaN
-//      in front wins, a NaN elsewhere never does.  Threads stride over the entries; fixed reduction tree.
+//      in front wins, a NaN elsewhere never does.  Threads stride over the entries; bl_block_argmax.
 //   2  the waves stride over the sample's range groups; the lanes of a wave stride over the group's rewrites, which the host
 //      lists group by group (grp_rw, a stable sort of the rewrites by group: the CSR form of rw_grp), so neither the number of
 //      rewrites nor of groups is bounded by LDS.  Per group: the first maximum (same rule), best_range_logprob = loc + max.
@@ -25,7 +25,7 @@
 //   comparisons, exact, no atomics.  Without by_confidence the rank is the number of kept samples in front: a compaction.
 // Plain vector loads and stores only; bit-identical from run to run.
 #include "bl_common.h"
-#include "bl_first_max.h"  // rp_load, rp_at, rp_better, rp_wave_argmax
+#include "bl_segment_f64.h"
 
 namespace {
 constexpr int RP_THREADS = 256;
@@ -44,39 +44,25 @@ __global__ __launch_bounds__(RP_THREADS) void report_summarize_kernel(
   __shared__ double s_max[RP_WAVES];
   __shared__ int s_tgt[RP_WAVES];  // -1: this wave did not meet the target's group; else 0 / 1 = that group's verdict
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid % BL_WAVE, wave = tid / BL_WAVE;
-  auto clamp = [](int64_t v, int64_t hi) { return v < 0 ? (int64_t)0 : (v > hi ? hi : v); };
-  const int64_t l0 = clamp(loc_off[b], total_loc), l1 = clamp(loc_off[b + 1], total_loc);
-  const int64_t r0 = clamp(rw_off[b], total_rw), r1 = clamp(rw_off[b + 1], total_rw);
-  const int64_t g0 = clamp(grp_off[b], total_grp), g1 = clamp(grp_off[b + 1], total_grp);
-  const int n_loc = (int)(l1 > l0 ? l1 - l0 : 0);
+  int64_t l0, g0;
+  const int n_loc = (int)bl_csr_row(loc_off, b, total_loc, l0);
+  const int64_t r0 = bl_clamp_off(rw_off[b], total_rw);
+  const int64_t n_grp = bl_csr_row(grp_off, b, total_grp, g0);
 
   // ---- 1: the predicted location
   double bv = 0.0;
   int bi = -1;
   for (int i = tid; i < n_loc; i += RP_THREADS) {
-    const double v = rp_load(src, n_src, loc_idx[l0 + i]);
-    if (v == v && rp_better(v, i, bv, bi)) {
+    const double v = bl_load_f64(src, n_src, loc_idx[l0 + i]);
+    if (v == v && bl_better(v, i, bv, bi)) {
       bv = v;
       bi = i;
     }
   }
-  rp_wave_argmax(bv, bi);
-  if (lane == 0) {
-    s_v[wave] = bv;
-    s_i[wave] = bi;
-  }
-  __syncthreads();
-  bv = s_v[0];
-  bi = s_i[0];
-#pragma unroll
-  for (int w = 1; w < RP_WAVES; ++w)
-    if (s_i[w] >= 0 && rp_better(s_v[w], s_i[w], bv, bi)) {
-      bv = s_v[w];
-      bi = s_i[w];
-    }
+  bl_block_argmax<RP_WAVES>(bv, bi, s_v, s_i);
   int pred = bi < 0 ? 0 : bi;  // nothing but NaNs: Python's max() keeps the first
   if (n_loc > 0) {
-    const double first = rp_load(src, n_src, loc_idx[l0]);
+    const double first = bl_load_f64(src, n_src, loc_idx[l0]);
     if (first != first) pred = 0;
   }
 
@@ -84,20 +70,21 @@ __global__ __launch_bounds__(RP_THREADS) void report_summarize_kernel(
   const int tg = tgt_grp[b];
   double wmax = -__builtin_huge_val();
   int wtgt = -1;
-  for (int64_t g = g0 + wave; g < g1; g += RP_WAVES) {  // uniform over the wave
-    const int64_t q0 = clamp(grp_rw_off[g], total_rw), q1 = clamp(grp_rw_off[g + 1], total_rw);
+  for (int64_t g = g0 + wave; g < g0 + n_grp; g += RP_WAVES) {  // uniform over the wave
+    int64_t q0;
+    const int64_t n_q = bl_csr_row(grp_rw_off, g, total_rw, q0);
     double gv = 0.0;
     int gi = -1;  // position in grp_rw: ascending = by original rewrite index within the group
-    for (int64_t q = q0 + lane; q < q1; q += BL_WAVE) {
-      const double v = rp_load(src, n_src, rp_at(rw_idx, total_rw, grp_rw[q], -1));
-      if (v == v && rp_better(v, (int)(q - q0), gv, gi)) {
+    for (int64_t q = q0 + lane; q < q0 + n_q; q += BL_WAVE) {
+      const double v = bl_load_f64(src, n_src, bl_at_i32(rw_idx, total_rw, grp_rw[q], -1));
+      if (v == v && bl_better(v, (int)(q - q0), gv, gi)) {
         gv = v;
         gi = (int)(q - q0);
       }
     }
-    rp_wave_argmax(gv, gi);
-    if (q1 > q0) {
-      const double first = rp_load(src, n_src, rp_at(rw_idx, total_rw, grp_rw[q0], -1));
+    bl_wave_argmax(gv, gi);
+    if (n_q > 0) {
+      const double first = bl_load_f64(src, n_src, bl_at_i32(rw_idx, total_rw, grp_rw[q0], -1));
       if (first != first || gi < 0) {
         gv = first == first ? gv : first;
         gi = 0;
@@ -105,7 +92,7 @@ __global__ __launch_bounds__(RP_THREADS) void report_summarize_kernel(
     }
     const int32_t rw = gi >= 0 ? grp_rw[q0 + gi] : -1;  // the rewrite's place among the minibatch's rewrites
     const int gl = grp_loc[g];                          // the group's node: a position among the sample's location entries
-    const double locv = (gl >= 0 && gl < n_loc) ? rp_load(src, n_src, loc_idx[l0 + gl]) : __builtin_nan("");
+    const double locv = (gl >= 0 && gl < n_loc) ? bl_load_f64(src, n_src, loc_idx[l0 + gl]) : __builtin_nan("");
     const double best = gi >= 0 ? locv + gv : __builtin_nan("");
     const bool shown = grp_shown[g] != 0;
     if (lane == 0) {
@@ -114,7 +101,7 @@ __global__ __launch_bounds__(RP_THREADS) void report_summarize_kernel(
     }
     if (shown && best > wmax) wmax = best;
     if (shown && tg >= 0 && g - g0 == (int64_t)tg)
-      wtgt = (gl != pred) ? 1 : (rp_at(rw_eq_target, total_rw, rw, 0) == 0 ? 1 : 0);
+      wtgt = (gl != pred) ? 1 : (bl_at_i32(rw_eq_target, total_rw, rw, 0) == 0 ? 1 : 0);
   }
   if (lane == 0) {
     s_max[wave] = wmax;
@@ -135,9 +122,8 @@ __global__ __launch_bounds__(RP_THREADS) void report_summarize_kernel(
     out_sample_i[B + b] = pred == n_loc - 1 ? 1 : 0;
     out_sample_i[2 * B + b] = wrong;
     out_sample_d[b] = pl;
-    out_sample_d[B + b] = rp_load(src, n_src, nobug_idx[b]);
+    out_sample_d[B + b] = bl_load_f64(src, n_src, nobug_idx[b]);
   }
-  (void)r1;
 }
 
 // sample j (key kj) comes before sample i (key ki) in the report
@@ -186,12 +172,9 @@ extern "C" int bl_report_summarize(const float* src, int64_t n_src, const int32_
   BL_CHECK_ARG(B >= 0 && n_src >= 0 && total_loc >= 0 && total_rw >= 0 && total_grp >= 0,
                "bl_report_summarize: negative size (B %d, n_src %lld, total_loc %lld, total_rw %lld, total_grp %lld)", (int)B,
                (long long)n_src, (long long)total_loc, (long long)total_rw, (long long)total_grp);
-  if (n_src > (int64_t)0x7fffffff || total_loc > (int64_t)0x7fffffff || total_rw > (int64_t)0x7fffffff ||
-      total_grp > (int64_t)0x7fffffff) {
-    bl_set_error("bl_report_summarize: index space beyond int32 (n_src %lld, total_loc %lld, total_rw %lld, total_grp %lld)",
+  BL_CHECK_RANGE(bl_fits_int32(n_src) && bl_fits_int32(total_loc) && bl_fits_int32(total_rw) && bl_fits_int32(total_grp),
+                 "bl_report_summarize: index space beyond int32 (n_src %lld, total_loc %lld, total_rw %lld, total_grp %lld)",
                  (long long)n_src, (long long)total_loc, (long long)total_rw, (long long)total_grp);
-    return BL_ERANGE;
-  }
   BL_CHECK_ARG(B == 0 || (src && loc_off && rw_off && grp_off && tgt_grp && ground_loc && nobug_idx),
                "bl_report_summarize: null src / loc_off / rw_off / grp_off / tgt_grp / ground_loc / nobug_idx");
   BL_CHECK_ARG(B == 0 || (out_sample_i && out_sample_d), "bl_report_summarize: null out_sample_i / out_sample_d");
@@ -212,10 +195,8 @@ extern "C" int bl_report_summarize(const float* src, int64_t n_src, const int32_
 extern "C" int bl_report_order(const double* keys, const int32_t* keep, int64_t n, int64_t k, int32_t by_confidence, int32_t* out,
                                int32_t* out_count, void* stream) {
   BL_CHECK_ARG(n >= 0, "bl_report_order: negative size (n %lld)", (long long)n);
-  if (n > (int64_t)BL_REPORT_MAX_SAMPLES) {
-    bl_set_error("bl_report_order: n = %lld samples, at most %lld supported", (long long)n, (long long)BL_REPORT_MAX_SAMPLES);
-    return BL_ERANGE;
-  }
+  BL_CHECK_RANGE(n <= (int64_t)BL_REPORT_MAX_SAMPLES, "bl_report_order: n = %lld samples, at most %lld supported", (long long)n,
+                 (long long)BL_REPORT_MAX_SAMPLES);
   BL_CHECK_ARG(out_count, "bl_report_order: null out_count");
   BL_CHECK_ARG(n == 0 || (keys && keep && out), "bl_report_order: null keys / keep / out");
   if (n == 0) {

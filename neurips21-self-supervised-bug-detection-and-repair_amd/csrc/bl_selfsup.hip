@@ -12,25 +12,21 @@
 // bl_score_targets   one thread per sample: out[b] = src[tgt_loc[b]] (+ src[tgt_rw[b]] when tgt_rw[b] >= 0).
 // bl_selector_sample one workgroup (4 waves) per sample; the threads stride over the sample's n_b + 1 entries (its rewrites by
 //                    original index, then NO_BUG), so n_b is not bounded by LDS:
-//   pass 1  g_i, written to out_logprob; z = sum_i exp(g_i / T)          (block reduction, fixed order)
+//   pass 1  g_i, written to out_logprob; z = sum_i exp(g_i / T)          (bl_block_sum_f64)
 //   pass 2  p_i = exp(g_i / T) / z, or 1 / (n_b + 1) when u_eps[b] < epsilon; entropy; number of entries with p_i > 0;
 //           Gumbel key_i = log p_i - log(-log u_i), kept in LDS for the first SS_KEY_CACHE entries and recomputed beyond
 //   draws   k_b = min(K, #{p_i > 0}) rounds of a block arg-max over the keys that come after the previous winner in the order
 //           (key descending, index ascending): the k_b largest keys, ties to the lower index.
 // No max subtraction in the softmax: exp(g / T) is computed as the reference computes it, so an overflow or a sum of zero gives
-// the reference's inf / nan.  0 * log 0 is nan in the entropy, as in NumPy.  No atomics; a fixed reduction tree: bit-identical
-// from run to run.
+// the reference's inf / nan.  0 * log 0 is nan in the entropy, as in NumPy.  No atomics; the reductions are bl_segment_f64.h's:
+// bit-identical from run to run.
 #include "bl_common.h"
+#include "bl_segment_f64.h"
 
 namespace {
 constexpr int SS_THREADS = 256;
 constexpr int SS_WAVES = SS_THREADS / BL_WAVE;
 constexpr int SS_KEY_CACHE = 2048;  // 16 KiB of LDS; longer samples recompute the keys of the entries beyond
-
-__device__ __forceinline__ double ss_load(const float* src, int64_t n_src, int32_t j) {
-  // an index outside src (the host never sends one) reads as NaN instead of out of bounds
-  return (j >= 0 && (int64_t)j < n_src) ? (double)src[j] : __builtin_nan("");
-}
 
 __global__ __launch_bounds__(SS_THREADS) void score_targets_kernel(const float* __restrict__ src, int64_t n_src,
                                                                    const int32_t* __restrict__ tgt_loc,
@@ -38,27 +34,9 @@ __global__ __launch_bounds__(SS_THREADS) void score_targets_kernel(const float* 
                                                                    double* __restrict__ out) {
   const int b = blockIdx.x * SS_THREADS + threadIdx.x;
   if (b >= B) return;
-  const double loc = ss_load(src, n_src, tgt_loc[b]);
+  const double loc = bl_load_f64(src, n_src, tgt_loc[b]);
   const int32_t r = tgt_rw[b];
-  out[b] = r >= 0 ? loc + ss_load(src, n_src, r) : loc;
-}
-
-__device__ __forceinline__ double ss_wave_sum(double v) {
-#pragma unroll
-  for (int o = BL_WAVE / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, BL_WAVE);
-  return v;
-}
-
-// sum over the workgroup, the same value (and the same order of additions) in every thread
-__device__ __forceinline__ double ss_block_sum(double v, double* s_red) {
-  v = ss_wave_sum(v);
-  __syncthreads();  // s_red may still be read from the previous reduction
-  if (threadIdx.x % BL_WAVE == 0) s_red[threadIdx.x / BL_WAVE] = v;
-  __syncthreads();
-  double t = s_red[0];
-#pragma unroll
-  for (int w = 1; w < SS_WAVES; ++w) t += s_red[w];
-  return t;
+  out[b] = r >= 0 ? loc + bl_load_f64(src, n_src, r) : loc;
 }
 
 // (key, index) a comes before b: larger key, then lower index
@@ -78,23 +56,22 @@ __global__ __launch_bounds__(SS_THREADS) void selector_sample_kernel(
   __shared__ double s_red[SS_WAVES];
   __shared__ double s_bk[SS_WAVES];
   __shared__ int s_bi[SS_WAVES];
-  const int b = blockIdx.x, tid = threadIdx.x, lane = tid % BL_WAVE, wave = tid / BL_WAVE;
-  auto clamp = [](int64_t v, int64_t hi) { return v < 0 ? (int64_t)0 : (v > hi ? hi : v); };
-  const int64_t r0 = clamp(rw_off[b], total_rw), r1 = clamp(rw_off[b + 1], total_rw);
-  const int n = (int)(r1 > r0 ? r1 - r0 : 0);  // candidate rewrites; entry n is NO_BUG
-  const int64_t e0 = r0 + b;                   // the sample's n + 1 entries in out_logprob / out_p / u
+  const int b = blockIdx.x, tid = threadIdx.x;
+  int64_t r0;
+  const int n = (int)bl_csr_row(rw_off, b, total_rw, r0);  // candidate rewrites; entry n is NO_BUG
+  const int64_t e0 = r0 + b;                                // the sample's n + 1 entries in out_logprob / out_p / u
   double* lp = out_logprob + e0;
   double* pp = out_p + e0;
   const double* uu = u + e0;
 
   double z = 0.0;
   for (int i = tid; i <= n; i += SS_THREADS) {
-    const double g = i < n ? ss_load(src, n_src, rw_idx[r0 + i]) + ss_load(src, n_src, rw_loc_idx[r0 + i])
-                           : ss_load(src, n_src, nobug_idx[b]);
+    const double g = i < n ? bl_load_f64(src, n_src, rw_idx[r0 + i]) + bl_load_f64(src, n_src, rw_loc_idx[r0 + i])
+                           : bl_load_f64(src, n_src, nobug_idx[b]);
     lp[i] = g;
     z += exp(g / temperature);
   }
-  z = ss_block_sum(z, s_red);
+  z = bl_block_sum_f64<SS_WAVES>(z, s_red);
 
   const bool uniform = u_eps[b] < epsilon;
   const double p_uniform = 1.0 / (double)(n + 1);
@@ -106,8 +83,8 @@ __global__ __launch_bounds__(SS_THREADS) void selector_sample_kernel(
     cnt += p > 0.0 ? 1.0 : 0.0;
     if (i < SS_KEY_CACHE) s_key[i] = p > 0.0 ? ss_key(p, uu[i]) : __builtin_nan("");  // NaN: not eligible
   }
-  ent = ss_block_sum(ent, s_red);
-  const int eligible = (int)ss_block_sum(cnt, s_red);  // exact: at most 2^31 ones; also orders the s_key writes
+  ent = bl_block_sum_f64<SS_WAVES>(ent, s_red);
+  const int eligible = (int)bl_block_sum_f64<SS_WAVES>(cnt, s_red);  // exact: at most 2^31 ones; also orders the s_key writes
   if (tid == 0) out_entropy[b] = -ent;
   const int kb = K < eligible ? K : eligible;
 
@@ -131,37 +108,12 @@ __global__ __launch_bounds__(SS_THREADS) void selector_sample_kernel(
         k = ss_key(p, uu[i]);
       }
       if (!ss_before(pk, pi, k, i)) continue;  // already drawn
-      if (bi < 0 || ss_before(k, i, bk, bi)) {
+      if (bl_better(k, i, bk, bi)) {
         bk = k;
         bi = i;
       }
     }
-#pragma unroll
-    for (int o = BL_WAVE / 2; o > 0; o >>= 1) {
-      const double ok = __shfl_xor(bk, o, BL_WAVE);
-      const int oi = __shfl_xor(bi, o, BL_WAVE);
-      if (oi >= 0 && (bi < 0 || ss_before(ok, oi, bk, bi))) {
-        bk = ok;
-        bi = oi;
-      }
-    }
-    __syncthreads();  // the previous round's s_bk / s_bi have been read
-    if (lane == 0) {
-      s_bk[wave] = bk;
-      s_bi[wave] = bi;
-    }
-    __syncthreads();
-    bk = s_bk[0];
-    bi = s_bi[0];
-#pragma unroll
-    for (int w = 1; w < SS_WAVES; ++w) {
-      const double ok = s_bk[w];
-      const int oi = s_bi[w];
-      if (oi >= 0 && (bi < 0 || ss_before(ok, oi, bk, bi))) {
-        bk = ok;
-        bi = oi;
-      }
-    }
+    bl_block_argmax<SS_WAVES>(bk, bi, s_bk, s_bi);
     if (tid == 0) out_selected[(int64_t)b * K + r] = bi;
     pk = bk;
     pi = bi;
@@ -172,10 +124,7 @@ __global__ __launch_bounds__(SS_THREADS) void selector_sample_kernel(
 extern "C" int bl_score_targets(const float* src, int64_t n_src, const int32_t* tgt_loc, const int32_t* tgt_rw, int32_t B, double* out,
                                 void* stream) {
   BL_CHECK_ARG(B >= 0 && n_src >= 0, "bl_score_targets: negative size (B %d, n_src %lld)", (int)B, (long long)n_src);
-  if (n_src > (int64_t)0x7fffffff) {
-    bl_set_error("bl_score_targets: n_src %lld beyond int32 indices", (long long)n_src);
-    return BL_ERANGE;
-  }
+  BL_CHECK_RANGE(bl_fits_int32(n_src), "bl_score_targets: n_src %lld beyond int32 indices", (long long)n_src);
   BL_CHECK_ARG(B == 0 || (src && tgt_loc && tgt_rw && out), "bl_score_targets: null src / tgt_loc / tgt_rw / out");
   if (B == 0) return BL_OK;
   hipLaunchKernelGGL(score_targets_kernel, dim3((B + SS_THREADS - 1) / SS_THREADS), dim3(SS_THREADS), 0, (hipStream_t)stream, src, n_src,
@@ -191,15 +140,11 @@ extern "C" int bl_selector_sample(const float* src, int64_t n_src, const int32_t
   BL_CHECK_ARG(B >= 0 && n_src >= 0 && total_rw >= 0, "bl_selector_sample: negative size (B %d, n_src %lld, total_rw %lld)", (int)B,
                (long long)n_src, (long long)total_rw);
   BL_CHECK_ARG(K >= 1, "bl_selector_sample: K = %d rewrites per sample, need at least 1", (int)K);
-  if (K > BL_SELECTOR_MAX_K) {
-    bl_set_error("bl_selector_sample: K = %d rewrites per sample, at most %d supported", (int)K, BL_SELECTOR_MAX_K);
-    return BL_ERANGE;
-  }
-  if (n_src > (int64_t)0x7fffffff || total_rw + (int64_t)B > (int64_t)0x7fffffff) {
-    bl_set_error("bl_selector_sample: index space beyond int32 (n_src %lld, total_rw + B %lld)", (long long)n_src,
+  BL_CHECK_RANGE(K <= BL_SELECTOR_MAX_K, "bl_selector_sample: K = %d rewrites per sample, at most %d supported", (int)K,
+                 BL_SELECTOR_MAX_K);
+  BL_CHECK_RANGE(bl_fits_int32(n_src) && bl_fits_int32(total_rw + (int64_t)B),
+                 "bl_selector_sample: index space beyond int32 (n_src %lld, total_rw + B %lld)", (long long)n_src,
                  (long long)(total_rw + B));
-    return BL_ERANGE;
-  }
   BL_CHECK_ARG(temperature == temperature && temperature != 0.0, "bl_selector_sample: temperature %g (the reference divides by it)",
                temperature);
   BL_CHECK_ARG(epsilon == epsilon, "bl_selector_sample: epsilon is NaN");

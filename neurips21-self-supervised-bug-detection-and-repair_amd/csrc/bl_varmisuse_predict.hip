@@ -14,13 +14,14 @@
 //     1  first-index maxima on the fp32 logits (exact): the localization column over positions < lens_att, the pointer column
 //        over the candidates among them (the others hold -inf), and the pointer maximum over candidates that are targets.  A NaN
 //        never wins (strict >);
-//     2  the three sums of exp(double(v) - double(max)) in fp64: per thread in stride order, wave butterfly, waves in wave
-//        order -- a fixed order, so a rerun is bit-identical;
+//     2  the three sums of exp(double(v) - double(max)) in fp64: per thread in stride order, then bl_block_sum_f64
+//        (bl_segment_f64.h) -- a fixed order, so a rerun is bit-identical;
 //     3  thread 0 writes the record.
 // fp64 on purpose (as bl_evaluate.hip): the record's log-probabilities are what a host would compute from the fp32 logits in
 // Python floats, and they are compared and ranked across minibatches.
 // Plain vector loads and stores only, no atomics.
 #include "bl_common.h"
+#include "bl_segment_f64.h"
 #include "bl_varmisuse_rows.h"
 
 namespace {
@@ -33,19 +34,6 @@ __global__ __launch_bounds__(VM_ROW_THREADS) void vm_predict_rows(bl_varmisuse_h
   float mu, rs, a0, a1;
   vm_row_logits<NK>(d, row, lane, mu, rs, a0, a1);
   if (lane == 0) reinterpret_cast<float2*>(logits)[row] = vm_masked_logits(d, row, a0, a1);
-}
-
-// the workgroup's sum, waves combined in wave order; every thread gets the result
-__device__ __forceinline__ double block_sum_f64(double s, double* sd) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (lane == 0) sd[wave] = s;
-  __syncthreads();
-  double t = sd[0];
-  for (int w = 1; w < VM_SAMPLE_WAVES; ++w) t += sd[w];
-  __syncthreads();
-  return t;
 }
 
 __global__ __launch_bounds__(VM_SAMPLE_THREADS) void vm_predict_samples(bl_varmisuse_head_t d, const float* __restrict__ logits,
@@ -82,9 +70,10 @@ __global__ __launch_bounds__(VM_SAMPLE_THREADS) void vm_predict_samples(bl_varmi
       if (tgt[i]) s2 += exp((double)v.y - dm2);
     }
   }
-  s0 = block_sum_f64(s0, sd);
-  s1 = block_sum_f64(s1, sd);
-  s2 = block_sum_f64(s2, sd);
+  // three reductions through one sd: each call's leading barrier comes after every thread has read the previous call's sums
+  s0 = bl_block_sum_f64<VM_SAMPLE_WAVES>(s0, sd);
+  s1 = bl_block_sum_f64<VM_SAMPLE_WAVES>(s1, sd);
+  s2 = bl_block_sum_f64<VM_SAMPLE_WAVES>(s2, sd);
   if (tid != 0) return;
   // ---- 3: the record
   const double ninf = -__builtin_huge_val();

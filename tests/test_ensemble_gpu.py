@@ -76,7 +76,37 @@ with gzip.open(os.path.join(ROOT, "tests", "golden", "ensemble_predictions.json.
     FIXTURE = json.load(f)
 
 
-@pytest.mark.parametrize("case", FIXTURE["cases"], ids=lambda c: c["name"])
+def _wide_case(kind):
+    """A case in the fixture's format whose samples have 65 location entries (64 nodes and NO_BUG: one more than a wave), which
+    the fixture's samples (at most 9) never reach; expected values from the float64 restatement (tests/ensemble_ref.py) on the
+    fp32 inputs.  Sample 0: every member's maximum is the entry past the wave, so there is consensus; sample 1: one member's
+    maximum is tied with an earlier entry, so the first-maximum rule breaks it; sample 2: a member is absent, and another has
+    a NaN and a -inf among its entries."""
+    rng = np.random.default_rng(65)
+    M, n_nodes, n_rw = 3, 64, 70
+    nodes = sorted(rng.choice(500, n_nodes, replace=False).tolist())
+    samples = []
+    for s in range(3):
+        members = []
+        for m in range(M):
+            loc = rng.normal(-3.0, 1.0, n_nodes + 1).astype(np.float32)
+            rw = rng.normal(-2.0, 1.0, n_rw).astype(np.float32)
+            loc[64] = 2.0 + m  # the greatest, in lane 0's second round
+            if s == 1 and m == 1:
+                loc[7] = loc[64]
+            if s == 2 and m == 1:
+                loc[5], loc[9], rw[3] = np.nan, -np.inf, -np.inf
+            members.append(None if (s == 2 and m == 0) else [loc.tolist(), rw.tolist()])
+        samples.append({"nodes": nodes, "n_rw": n_rw, "members": members})
+    expected = []
+    for i, s in enumerate(samples):
+        preds = [None if mem is None else (dict(zip(nodes + [-1], mem[0])), mem[1]) for mem in s["members"]]
+        loc, rw = R.combine(kind, preds)
+        expected.append({"id": i, "location_logprobs": [[k, float(v)] for k, v in loc.items()], "rewrite_logprobs": [float(v) for v in rw]})
+    return {"name": f"{kind}_m3_65_entries", "M": M, "kind": kind, "samples": samples, "expected": expected}
+
+
+@pytest.mark.parametrize("case", FIXTURE["cases"] + [_wide_case("avg"), _wide_case("consensus")], ids=lambda c: c["name"])
 def test_combine_kernel_reproduces_the_reference(case):
     from buglab.models import hip_ops
 

@@ -41,6 +41,8 @@ def _case(name):
         return t
     if name == "widest":                 # the widest row the head takes
         return _head_case(D=1024, B=2, L=8, seed=5)
+    if name == "longer_than_a_workgroup":  # 257 positions: thread 0 takes two, every wave and the block reductions are live
+        return _head_case(D=64, B=2, L=257, seed=7, full_lengths=True)
     raise KeyError(name)
 
 
@@ -80,7 +82,7 @@ def _twin(logits, tensors):
     return judge_great_host(logits.cpu().numpy(), logits.shape[0] // B, lens_att.numpy(), err.numpy(), tgt.numpy())
 
 
-@pytest.mark.parametrize("name", ["odd_L_full_length", "no_bug_no_candidates", "ties", "widest"])
+@pytest.mark.parametrize("name", ["odd_L_full_length", "no_bug_no_candidates", "ties", "widest", "longer_than_a_workgroup"])
 def test_kernel_matches_training_logits_and_twin(name):
     from buglab.models import hip_ops
 
@@ -104,6 +106,8 @@ def test_kernel_matches_training_logits_and_twin(name):
         assert got_i[1, 1] == -1 and math.isnan(got_d[5, 1]) and got_d[1, 1] == -math.inf and (got_d[6] == -math.inf).all()
     if name == "odd_L_full_length":
         assert int(tensors[5][0]) == 23
+    if name == "longer_than_a_workgroup":
+        assert int(tensors[5][0]) == 257
     again_d, again_i = _buffers(B, 1.5, 5)
     again = _predict(dev, again_d, again_i, 0)
     assert torch.equal(again.view(torch.int32), logits.view(torch.int32))
