@@ -827,6 +827,44 @@ int bl_eval_judge(const float* src, int64_t n_src, const int32_t* loc_idx, const
                   int64_t capacity, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Paired bootstrap of the evaluation counts (buglab/models/compare.py), in csrc/bl_bootstrap.hip.  BEYOND THE REFERENCE: it
+ * has no counterpart -- its evaluate.py prints point estimates only.  What is resampled are the counts of
+ * buglab/models/evaluate.py:139-173 (the numerators and denominators of every metric and of the per-scout tables): each
+ * replicate draws n samples with replacement and counts them again, for M models over the SAME draws.
+ *
+ * The draw contract (buglab/models/_compare.py::draw_indices is the same arithmetic in NumPy).  Replicate r >= 0 draws n
+ * sample positions; for j in [0, n), all arithmetic uint64, wrapping:
+ *   mix(z):  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9;  z = (z ^ (z >> 27)) * 0x94D049BB133111EB;  return z ^ (z >> 31)
+ *   base   = mix(seed * 0x9E3779B97F4A7C15 + 0x9E3779B97F4A7C15)
+ *   h      = mix(r * n + j + base) >> 32
+ *   index  = (h * n) >> 32
+ * (splitmix64 as a counter generator).  A draw depends on (seed, r, j, n) alone: not on the grid, not on how a run is cut
+ * into calls.  The multiply-shift maps h to an index with a relative bias below n / 2^32.  Seed 0, n = 10: replicate 0 draws
+ * 2 9 6 4 2 1 5 5 5 3, replicate 1 draws 3 6 3 2 2 0 3 0 2 2.
+ *
+ * packed [n]: one uint32 per sample, shared by the M models.  Bits 0-7: the sample's scout id (0 = "NoBug": the sample has no
+ * bug; 1 .. K - 1: the bug kinds, as ColumnarEvaluationReport.scout_names numbers them).  Model m owns bits 8 + 4m .. 11 + 4m:
+ * warned | location_correct << 1 | (repair_given_location == 1) << 2 | repaired << 3.
+ *
+ * out [R, C] int32, C = K + M (4 + 2K); row i holds replicate r0 + i:
+ *   columns 0 .. K - 1               scout_total[k]: draws whose sample has scout k;
+ *   model m, from column K + m (4 + 2K):  repaired | repaired_and_buggy | warned_and_buggy | silent_and_not_buggy |
+ *                                    loc_ok[k] (K entries: location_correct and scout k) |
+ *                                    rep_ok[k] (K entries: bit 2 set and scout k; the entry for k = 0 is always 0).
+ * "buggy" is scout != 0.  A scout id >= K (the caller's mistake) counts as buggy and enters no [k] column.  The rest derives:
+ * n_buggy = n - scout_total[0], located = sum loc_ok, repair_ok = sum rep_ok.  Integer counts: any summation order gives the
+ * same bits, so the result equals the twin's exactly and every call gives the same result.
+ *
+ * One launch, one workgroup per replicate, the words gathered from global memory (L2); integer LDS adds, no float atomics,
+ * one plain store per output element; no synchronisation, no allocation.  R == 0 is a no-op.
+ * BL_EINVAL: null packed / out, n < 1, R < 0, r0 < 0 (or r0 + R beyond int64), M outside [1, BL_BOOTSTRAP_MAX_MODELS], K outside
+ * [1, BL_BOOTSTRAP_MAX_SCOUTS].  BL_ERANGE: n >= 2^31. */
+#define BL_BOOTSTRAP_MAX_MODELS 6
+#define BL_BOOTSTRAP_MAX_SCOUTS 64
+int bl_bootstrap_counts(const uint32_t* packed, int64_t n, int32_t M, int32_t K, uint64_t seed, int64_t r0, int64_t R,
+                        int32_t* out /* [R, C] */, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Confidence calibration (buglab/models/calibrate.py), in csrc/bl_confidence.hip.  BEYOND THE REFERENCE: it has no
  * counterpart; what is calibrated is the confidence its evaluate.py:60-140 thresholds and its visualize.py ranks by.  One
  * inverse temperature beta and a NO_BUG bias rescale the localization distribution, one repair_beta the repair groups:

@@ -86,7 +86,9 @@ def prediction_minibatches(model, tagged: Iterable[Tuple[Any, Any]], device, par
     `extend(layout, datapoints, device)` runs in the collate worker, after the layout; its result is the minibatch's
     "selfsup" entry (with `extend_sees_minibatch` it is called as `extend(layout, datapoints, device, minibatch)`: the
     sequence models' minibatch carries their node -> token maps).  `rejected(tag)` is called (from the tensorising side, in input order) for a datapoint `tensorize`
-    rejects.  Call under `torch.no_grad()` and `model._tensorize_all_location_rewrites()`."""
+    rejects.  The tags of a minibatch are in the order of its samples (`minibatch_iterator` appends a sample and its tag
+    together), which is also the order `extend` sees the datapoints in: `evaluate_on_device(..., positions_out=)` relies on it.
+    Call under `torch.no_grad()` and `model._tensorize_all_location_rewrites()`."""
     side: Dict[int, Any] = {}  # id(tensorised sample) -> (the sample: keeps the id unique, its datapoint)
 
     def tensorized():

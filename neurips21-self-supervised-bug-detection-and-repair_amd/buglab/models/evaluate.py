@@ -313,13 +313,15 @@ class ColumnarEvaluationReport(EvaluationReport):
 
 
 def evaluate_on_device(model, nn, data: Iterable[Any], device, *, assume_buggy: bool = False, eval_only_no_bug: bool = False,
-                       parallelize: bool = True) -> ColumnarEvaluationReport:
+                       parallelize: bool = True, positions_out: Optional[list] = None) -> ColumnarEvaluationReport:
     """`evaluate_predictions(model.predict(data, nn, device, parallelize), ...)` without the per-sample host work: the
     minibatches `predict` forms (same `tensorize`, same 50 samples), the same forward, and one hip_ops.eval_judge launch per
     minibatch that writes the verdicts into outcome buffers kept on the device until the end (24 bytes per sample, one copy
     back).  `has_bug` and the scout names never go to the device.  With `eval_only_no_bug` every sample still runs, as in
     `predict`, so that a sequence model's minibatches -- and with them its fp32 values -- are those of the host path; the buggy
-    samples are left out of the report.  Single models only: an ensemble keeps the host path."""
+    samples are left out of the report.  Single models only: an ensemble keeps the host path.  `positions_out`, when given,
+    receives the position in `data` of every judged sample, in the order of the outcome columns before `eval_only_no_bug`
+    (a datapoint `tensorize` rejects has none): what buglab/models/compare.py pairs two models' samples by."""
     from buglab.controllers import _batching as Bt
     from buglab.models import _evaluate as E
     from buglab.models import hip_ops
@@ -348,10 +350,13 @@ def evaluate_on_device(model, nn, data: Iterable[Any], device, *, assume_buggy: 
     n = 0
     nn.eval()
     with torch.no_grad(), model._tensorize_all_location_rewrites():
-        for mb, _tags in Bt.prediction_minibatches(model, ((d, None) for d in data), device, parallelize, extend, lambda tag: None,
-                                                   extend_sees_minibatch=True):
+        for mb, tags in Bt.prediction_minibatches(model, ((d, i) for i, d in enumerate(data)), device, parallelize, extend,
+                                                  lambda tag: None, extend_sees_minibatch=True):
             flat = Bt.flat_prediction_output(nn, mb)
             B = len(mb["selfsup"]["scouts"])
+            if positions_out is not None:
+                assert len(tags) == B
+                positions_out.extend(tags)
             if n + B > capacity:  # a stream of unknown length: double, on the device
                 capacity = max(2 * capacity, n + B)
                 _, new_conf, new_verdict = grown = buffers(capacity)

@@ -9,7 +9,7 @@ from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import POINTER, Structure, c_double, c_float, c_int8, c_int32, c_int64, c_uint32, c_void_p
+from ctypes import POINTER, Structure, c_double, c_float, c_int8, c_int32, c_int64, c_uint32, c_uint64, c_void_p
 from typing import List, NamedTuple, Optional, Sequence, Tuple
 
 import torch
@@ -196,6 +196,7 @@ _SIGNATURES = {
     "bl_report_order": ([c_void_p, c_void_p, c_int64, c_int64, c_int32, c_void_p, c_void_p, c_void_p], ctypes.c_int),
     "bl_eval_judge": ([c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int32,
                        c_int32, c_void_p, c_void_p, c_int64, c_int64, c_void_p], ctypes.c_int),
+    "bl_bootstrap_counts": ([c_void_p, c_int64, c_int32, c_int32, c_uint64, c_int64, c_int64, c_void_p, c_void_p], ctypes.c_int),
     "bl_conf_loc_stats": ([c_void_p, c_int64, c_void_p, c_void_p, c_int32, c_double, c_double, c_void_p, c_void_p, c_void_p], ctypes.c_int),
     "bl_conf_group_stats": ([c_void_p, c_int64, c_void_p, c_void_p, c_int32, c_double, c_void_p, c_void_p, c_void_p], ctypes.c_int),
     "bl_conf_apply": ([c_void_p, c_int64, c_void_p, c_int32, c_int64, c_void_p, c_void_p, c_int32, c_int64, c_int64, c_double, c_double,

@@ -10,7 +10,7 @@ from ._cabi import _check, _f32, _i32, load_library, _p, _req, _stream
 
 __all__ = ["ENSEMBLE_KINDS", "ENSEMBLE_MAX_MEMBERS", "ensemble_combine", "SELECTOR_MAX_K", "_f64", "score_targets",
            "selector_sample", "REPORT_MAX_SAMPLES", "REPORT_INDEX_FIELDS", "report_summarize", "report_order", "EVAL_INDEX_FIELDS", "eval_judge",
-           "conf_loc_stats", "conf_group_stats", "conf_apply", "DEDUP_MAX_PERM",
+           "BOOTSTRAP_MAX_MODELS", "BOOTSTRAP_MAX_SCOUTS", "bootstrap_counts", "conf_loc_stats", "conf_group_stats", "conf_apply", "DEDUP_MAX_PERM",
            "DEDUP_EMPTY_SLOT", "_i64", "dedup_sha1_u32", "dedup_minhash", "dedup_lsh_insert_query"]
 
 
@@ -161,6 +161,35 @@ def eval_judge(src, ix, out_conf, out_verdict, offset: int, *, assume_buggy: boo
     _check(load_library().bl_eval_judge(src.data_ptr(), src.numel(), p("loc_idx"), p("loc_off"), p("key_node"), total_loc, p("rw_idx"),
                                         p("rw_off"), p("rw_node"), total_rw, p("tgt_rw"), B, int(bool(assume_buggy)),
                                         out_conf.data_ptr(), out_verdict.data_ptr(), offset, N, _stream()), "bl_eval_judge")
+
+
+# ------------------------------------------------------------------------------------------------
+# paired bootstrap of the evaluation counts (csrc/bl_bootstrap.hip; include/buglab_hip.h::bl_bootstrap_counts)
+BOOTSTRAP_MAX_MODELS = 6   # BL_BOOTSTRAP_MAX_MODELS
+BOOTSTRAP_MAX_SCOUTS = 64  # BL_BOOTSTRAP_MAX_SCOUTS
+
+
+def bootstrap_counts(packed, M: int, K: int, seed: int, r0: int, R: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The counts of bootstrap replicates r0 .. r0 + R - 1 over the packed outcome words of n samples, int32 [R, K + M (4 + 2K)]
+    (the columns: include/buglab_hip.h; the words: buglab/models/_compare.py::pack_outcomes).  packed int32 [n]: the uint32
+    words as the int32 with the same bits.  `out`: at least R rows of a larger buffer to fill (the first R are written and
+    returned).  Exactly buglab/models/_compare.py::bootstrap_counts_host.  No sync."""
+    _i32(packed, "packed")
+    M, K, R = int(M), int(K), int(R)
+    if packed.dim() != 1 or packed.shape[0] < 1:
+        raise ValueError(f"bootstrap_counts: packed {tuple(packed.shape)} must be [n] with n >= 1")
+    if not 1 <= M <= BOOTSTRAP_MAX_MODELS or not 1 <= K <= BOOTSTRAP_MAX_SCOUTS or R < 0 or int(r0) < 0:
+        raise ValueError(f"bootstrap_counts: need 1 <= M <= {BOOTSTRAP_MAX_MODELS}, 1 <= K <= {BOOTSTRAP_MAX_SCOUTS}, R >= 0 and "
+                         f"r0 >= 0 (got M {M}, K {K}, R {R}, r0 {r0})")
+    C = K + M * (4 + 2 * K)
+    if out is None:
+        out = torch.empty((R, C), dtype=torch.int32, device=packed.device)
+    elif _i32(out, "out").dim() != 2 or out.shape[0] < R or out.shape[1] != C or out.device != packed.device:
+        raise ValueError(f"bootstrap_counts: out {tuple(out.shape)} must be [>= {R}, {C}] on {packed.device}")
+    if R:
+        _check(load_library().bl_bootstrap_counts(packed.data_ptr(), packed.shape[0], M, K, int(seed) & 0xFFFFFFFFFFFFFFFF, int(r0), R,
+                                                  out.data_ptr(), _stream()), "bl_bootstrap_counts")
+    return out[:R]
 
 
 # ------------------------------------------------------------------------------------------------
