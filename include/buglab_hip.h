@@ -864,6 +864,35 @@ int bl_eval_judge(const float* src, int64_t n_src, const int32_t* loc_idx, const
 int bl_bootstrap_counts(const uint32_t* packed, int64_t n, int32_t M, int32_t K, uint64_t seed, int64_t r0, int64_t R,
                         int32_t* out /* [R, C] */, void* stream);
 
+/* bl_bootstrap_curve_counts: the same replicates counted per candidate threshold (buglab/models/operatingpoint.py; the NumPy
+ * twin is buglab/models/_operatingpoint.py::curve_counts_host).  BEYOND THE REFERENCE, which prints the six threshold curves
+ * as point estimates.  The thresholds are fixed once, per model, and every sample carries the index of the first threshold it
+ * passes, so a replicate is a histogram over those indices and a prefix sum -- no ranking inside a replicate.
+ *
+ * packed [n]: the words above, unchanged; has_bug = (word & 0xFF) != 0, and of model m's bits at 8 + 4m: warned = bit 0,
+ * loc_ok = bit 1, rep_ok = bit 2.  bins [M, n] int16: bins[m, i] in [0, G] is the number of model m's thresholds that sample i
+ * does NOT pass (thresholds descend, so "bin <= g" is "passes threshold g"); G passes none, and so does any value outside
+ * [0, G).  The draws are those of the contract above, word for word: for the same (seed, r, n), replicate r of this function
+ * and of bl_bootstrap_counts count the same samples.
+ *
+ * out [R, 1 + M * 5 * G] int32; row i holds replicate r0 + i:
+ *   column 0                      num_buggy: draws with has_bug;
+ *   then [M][5][G]                for model m, counter c and threshold g the count over the draws with bin <= g (inclusive
+ *                                 cumulative over the bins) of, in the order of _curves_of_ranked in buglab/models/evaluate.py:
+ *                                   det_true = has_bug & loc_ok | det_false = warned & ~loc_ok |
+ *                                   full_true = has_bug & loc_ok & rep_ok | full_false = warned & (~loc_ok | ~rep_ok) |
+ *                                   false_alarm = warned & ~has_bug
+ * applied to the bits as written (a word may hold combinations no model produces).  Integer counts: any order gives the same
+ * bits, so the result equals the twin's exactly and every call gives the same result.
+ *
+ * One launch, one workgroup per (replicate, model) striding over the replicates; integer LDS adds into one [5][G] table (20 KB
+ * at G = BL_CURVE_MAX_BINS), the prefix sum in LDS, one plain store per output element; no synchronisation, no allocation.
+ * R == 0 is a no-op.  BL_EINVAL: null packed / bins / out, n < 1, R < 0, r0 < 0 (or r0 + R beyond int64), M outside
+ * [1, BL_BOOTSTRAP_MAX_MODELS], G outside [1, BL_CURVE_MAX_BINS].  BL_ERANGE: n >= 2^31. */
+#define BL_CURVE_MAX_BINS 1024
+int bl_bootstrap_curve_counts(const uint32_t* packed, const int16_t* bins /* [M, n] */, int64_t n, int32_t M, int32_t G,
+                              uint64_t seed, int64_t r0, int64_t R, int32_t* out /* [R, 1 + M * 5 * G] */, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Confidence calibration (buglab/models/calibrate.py), in csrc/bl_confidence.hip.  BEYOND THE REFERENCE: it has no
  * counterpart; what is calibrated is the confidence its evaluate.py:60-140 thresholds and its visualize.py ranks by.  One

@@ -251,9 +251,12 @@ class ComparisonReport:
         self.num_paired, self.num_replicates, self.seed, self.confidence = int(num_paired), int(num_replicates), int(seed), float(confidence)
         self.metrics, self.deltas, self.p_values, self.mcnemar = metrics, deltas, p_values, mcnemar
         self.models = models if models is not None else [{"name": n, "num_samples": self.num_paired, "num_dropped": 0} for n in self.names]
+        self.curve_bands: Optional[List[Dict[str, Any]]] = None  # compare.py --curves: per model, the bands of its threshold curves
 
     def to_dict(self) -> Dict[str, Any]:
+        bands = {} if self.curve_bands is None else {"curve_bands": self.curve_bands}
         return {
+            **bands,
             "models": self.models, "scout_names": self.scout_names, "num_paired": self.num_paired,
             "num_replicates": self.num_replicates, "seed": self.seed, "confidence": self.confidence,
             "metrics": {k: [iv._asdict() for iv in v] for k, v in self.metrics.items()},

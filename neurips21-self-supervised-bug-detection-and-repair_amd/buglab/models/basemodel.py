@@ -61,6 +61,17 @@ class AbstractBugLabModel:
     def confidence_calibration(self, value) -> None:
         self._confidence_calibration = value
 
+    @property
+    def warning_operating_point(self):
+        """The `OperatingPoint` fitted by buglab/models/operatingpoint.py (beyond the reference), or None: the confidence at
+        which a warning is shown, read by `visualize --at-operating-point` and `evaluate --at-operating-point`.  Pickled with
+        the model; a checkpoint written before the field existed has none."""
+        return getattr(self, "_warning_operating_point", None)
+
+    @warning_operating_point.setter
+    def warning_operating_point(self, value) -> None:
+        self._warning_operating_point = value
+
     def _compute_rewrite_data(self, datapoint, candidate_node_idxs: Sequence[int]):
         """Same 16-tuple as reference basemodel.py:80-238.
 

@@ -180,6 +180,18 @@ def judged_confidence(collected: CollectedPool, cal: Optional[ConfidenceCalibrat
     return np.exp(host[:cap][:n].numpy()), host[cap:].view(torch.int32).view(4, cap)[1, :n].numpy() != 0
 
 
+def drop_operating_point(model) -> bool:
+    """A warning operating point (buglab/models/operatingpoint.py) is a threshold on the confidences the model reported when
+    it was fitted; a new calibration changes those, so the point is dropped, with one warning.  -> whether there was one."""
+    point = getattr(model, "warning_operating_point", None)
+    if point is None:
+        return False
+    LOGGER.warning("The model's warning operating point %s was fitted on other confidences and is dropped; fit it again on the "
+                   "calibrated model (python -m buglab.models.operatingpoint).", point)
+    model.warning_operating_point = None
+    return True
+
+
 def calibrate_model(model, nn, data: Iterable[Any], device, *, parallelize: bool = False, fit_bias: bool = True,
                     fit_repair: bool = True, num_bins: int = 15, report: Optional[Dict[str, Any]] = None) -> ConfidenceCalibration:
     """Fits a `ConfidenceCalibration` for (model, nn) on `data` on the device and stores it on `model` (replacing an earlier
@@ -192,6 +204,7 @@ def calibrate_model(model, nn, data: Iterable[Any], device, *, parallelize: bool
         raise ValueError("calibrate_model: no sample of the data could be tensorised")
     cal, details = fit_on_device(collected, fit_bias=fit_bias, fit_repair=fit_repair)
     model.confidence_calibration = cal
+    drop_operating_point(model)
     if report is not None:
         n, nb = collected.num_samples, collected.num_buggy
         loss = lambda beta, bias: float(hip_ops.conf_loc_stats(*collected.loc, beta, bias)[0]) / n

@@ -3,7 +3,7 @@
 Usage:
     python -m buglab.models.compare DATA MODEL [MODEL ...] [--num-replicates 10000] [--seed 0] [--confidence 0.95]
                                     [--limit-num-elements N] [--sequential] [--assume-buggy] [--eval-only-no-bug]
-                                    [--host-bootstrap] [--report-json FILE]
+                                    [--host-bootstrap] [--report-json FILE] [--curves [--max-bins G]]
 
 Paired bootstrap comparison of trained models -- BEYOND THE REFERENCE, which has no counterpart: its evaluate.py prints point
 estimates such as "Accuracy (Localization & Repair) 71.30% (1426/2000)" and nothing that says whether a second model's 72.1% is
@@ -61,9 +61,11 @@ def bootstrap_counts_device(packed: np.ndarray, M: int, K: int, seed: int, num_r
 
 def compare_reports(reports: Sequence[Any], *, num_replicates: int = 10000, seed: int = 0, confidence: float = 0.95,
                     host_bootstrap: bool = False, device=None, names: Optional[Sequence[str]] = None,
-                    models: Optional[List[Dict[str, Any]]] = None) -> ComparisonReport:
+                    models: Optional[List[Dict[str, Any]]] = None, curves: bool = False, max_bins: int = 256) -> ComparisonReport:
     """`reports`: M `ColumnarEvaluationReport`s over the same samples in the same order, the baseline first.  The counts come
-    from `device` (hip_ops.bootstrap_counts) or, with `host_bootstrap`, from the NumPy twin."""
+    from `device` (hip_ops.bootstrap_counts) or, with `host_bootstrap`, from the NumPy twin.  `curves`: the report also
+    carries, per model, the bands of its six threshold curves at up to `max_bins` thresholds of its own
+    (buglab/models/operatingpoint.py::report_curve_bands), over the same seed and replicate numbers."""
     if num_replicates < 1:
         raise ValueError(f"num_replicates must be at least 1 (got {num_replicates})")
     packed, K, scout_names = C.pack_outcomes(reports)
@@ -77,7 +79,13 @@ def compare_reports(reports: Sequence[Any], *, num_replicates: int = 10000, seed
         counts = C.bootstrap_counts_host(packed, M, K, seed, 0, int(num_replicates))
     else:
         counts = bootstrap_counts_device(packed, M, K, seed, int(num_replicates), "cuda" if device is None else device)
-    return C.summarize(packed, M, K, counts, names=names, scout_names=scout_names, seed=seed, confidence=confidence, models=models)
+    report = C.summarize(packed, M, K, counts, names=names, scout_names=scout_names, seed=seed, confidence=confidence, models=models)
+    if curves:
+        from buglab.models.operatingpoint import report_curve_bands
+
+        report.curve_bands = report_curve_bands(reports, num_replicates=int(num_replicates), seed=seed, confidence=confidence,
+                                                max_bins=max_bins, device=device, host_bootstrap=host_bootstrap)
+    return report
 
 
 def _rows_of(report, rows: np.ndarray):
@@ -136,7 +144,8 @@ def paired_reports(evaluated: Sequence[Tuple[Any, List[int]]], num_samples: int,
 
 def compare_models(models: Sequence[Tuple[Any, Any]], data, device, *, num_replicates: int = 10000, seed: int = 0,
                    confidence: float = 0.95, assume_buggy: bool = False, eval_only_no_bug: bool = False, parallelize: bool = True,
-                   host_bootstrap: bool = False, names: Optional[Sequence[str]] = None) -> ComparisonReport:
+                   host_bootstrap: bool = False, names: Optional[Sequence[str]] = None, curves: bool = False, max_bins: int = 256
+                   ) -> ComparisonReport:
     """`models`: (model, nn) pairs, the baseline first; `data`: the datapoints, read once into a list that every model sees in
     that order."""
     if not 1 <= len(models) <= C.MAX_MODELS:
@@ -148,7 +157,7 @@ def compare_models(models: Sequence[Tuple[Any, Any]], data, device, *, num_repli
     reports, _, dropped = paired_reports(evaluated, len(data), eval_only_no_bug)
     info = [{"name": name, "num_samples": len(data), "num_dropped": d} for name, d in zip(names, dropped)]
     return compare_reports(reports, num_replicates=num_replicates, seed=seed, confidence=confidence, host_bootstrap=host_bootstrap,
-                           device=device, names=names, models=info)
+                           device=device, names=names, models=info, curves=curves, max_bins=max_bins)
 
 
 def parse_args(argv=None) -> argparse.Namespace:
@@ -164,6 +173,9 @@ def parse_args(argv=None) -> argparse.Namespace:
     p.add_argument("--eval-only-no-bug", action="store_true", help="Compare on the NO_BUG samples only (applied after pairing).")
     p.add_argument("--host-bootstrap", action="store_true", help="Resample with the NumPy twin instead of the device kernel.")
     p.add_argument("--report-json", default=None, help="Also write the report as data.")
+    p.add_argument("--curves", action="store_true",
+                   help="--report-json also gets, per model, the bands of its six threshold curves (the printed text gains nothing).")
+    p.add_argument("--max-bins", type=int, default=256, help="Thresholds per model of --curves, at most 1024.")
     return p.parse_args(argv)
 
 
@@ -183,7 +195,8 @@ def run(args: argparse.Namespace) -> ComparisonReport:
     models = [AbstractNeuralModel.restore_model(Path(name), device) for name in args.MODEL]
     report = compare_models(models, data, device, num_replicates=args.num_replicates, seed=args.seed, confidence=args.confidence,
                             assume_buggy=args.assume_buggy, eval_only_no_bug=args.eval_only_no_bug, parallelize=not args.sequential,
-                            host_bootstrap=args.host_bootstrap, names=[str(name) for name in args.MODEL])
+                            host_bootstrap=args.host_bootstrap, names=[str(name) for name in args.MODEL], curves=args.curves,
+                            max_bins=args.max_bins)
     sys.stdout.write(report.format())
     if args.report_json is not None:
         with open(args.report_json, "w", encoding="utf-8") as f:

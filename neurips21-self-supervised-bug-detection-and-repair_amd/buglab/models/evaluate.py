@@ -10,6 +10,8 @@ Options:
     --sequential               Do not parallelize data loading. Makes debugging easier.
     --on-device                Judge every predict minibatch on the device (single models only; same report).
     --report-json=<path>       Also write the report as data: summary, per-scout tables and curves.
+    --at-operating-point       After the report, what the checkpoint's warning operating point gives on this data
+                               (buglab/models/operatingpoint.py): warnings raised, precisions and recalls at that threshold.
     --minibatch-size=<size>    Accepted for command-line compatibility (the reference parses and ignores it too).
     --restore-path=<path>      Accepted for command-line compatibility (unused by the reference's run()).
     --quiet                    Accepted for command-line compatibility.
@@ -375,10 +377,46 @@ def evaluate_on_device(model, nn, data: Iterable[Any], device, *, assume_buggy: 
                                     eval_only_no_bug)
 
 
-def report_to_json(report: EvaluationReport) -> str:
-    """summary, per-scout tables and curves as data (NaN where the text says NaN)."""
-    return json.dumps({"summary": report.summary(), "per_scout": report.per_scout(),
-                       "curves": {k: v.tolist() for k, v in report.curves().items()}}, indent=1, sort_keys=True) + "\n"
+def at_operating_point(report: EvaluationReport, point) -> Dict[str, Any]:
+    """What the report's samples give when a warning is shown only at or above `point.threshold_logprob` (an `OperatingPoint` of
+    buglab/models/operatingpoint.py): the five counts of the threshold curves there (`curve_counts_point` with that one
+    threshold), the warnings raised, and the precisions and recalls by the formulas of `_curves_of_ranked`."""
+    from buglab.models import _operatingpoint as P
+
+    columns = report if isinstance(report, ColumnarEvaluationReport) else ColumnarEvaluationReport.from_outcomes(report.outcomes)
+    out: Dict[str, Any] = {"threshold_logprob": float(point.threshold_logprob), "num_samples": int(columns.confidence.shape[0])}
+    if columns.confidence.shape[0] == 0:
+        counts = np.zeros((1, P.num_columns(1, 1)), np.int32)
+    else:
+        packed, _, _ = P.pack_outcomes([columns])
+        counts = P.curve_counts_point(packed, P.bin_of(columns.confidence, [point.threshold_logprob])[None, :], 1, 1)
+    out["num_buggy_samples"] = int(counts[0, 0])
+    out.update({name: int(counts[0, 1 + c]) for c, name in enumerate(P.COUNTERS)})
+    out["num_warnings"] = out["det_true"] + out["det_false"]
+    curves = P.curves_from_counts(counts, 1, 1)
+    out.update({name: float(curves[name][0, 0, 0]) for name in ("detection_precision", "precision", "detection_recall", "recall")})
+    return out
+
+
+def format_at_operating_point(at: Dict[str, Any]) -> str:
+    pct = lambda x: "NaN" if x != x else f"{x:.2%}"
+    return "\n".join([
+        "=" * 34,
+        f"At the warning operating point (probability >= {math.exp(at['threshold_logprob']):.6f}): {at['num_warnings']} warnings "
+        f"on {at['num_samples']} samples",
+        f"Detection Precision {pct(at['detection_precision'])} ({at['det_true']}/{at['det_true'] + at['det_false']})",
+        f"Precision (Detect and Repair) {pct(at['precision'])} ({at['full_true']}/{at['full_true'] + at['full_false']})",
+        f"Detection Recall {pct(at['detection_recall'])} ({at['det_true']}/{at['num_buggy_samples']})",
+        f"Recall (Detect and Repair) {pct(at['recall'])} ({at['full_true']}/{at['num_buggy_samples']})",
+    ]) + "\n"
+
+
+def report_to_json(report: EvaluationReport, at: Optional[Dict[str, Any]] = None) -> str:
+    """summary, per-scout tables and curves as data (NaN where the text says NaN); with `at` (`at_operating_point`), that too."""
+    blob = {"summary": report.summary(), "per_scout": report.per_scout(), "curves": {k: v.tolist() for k, v in report.curves().items()}}
+    if at is not None:
+        blob["at_operating_point"] = at
+    return json.dumps(blob, indent=1, sort_keys=True) + "\n"
 
 
 def run(arguments):
@@ -396,9 +434,16 @@ def run(arguments):
         predictions = model.predict(data, nn, device, parallelize=not arguments["--sequential"])
         report = evaluate_predictions(predictions, arguments["--assume-buggy"], arguments["--eval-only-no-bug"])
     sys.stdout.write(report.format())
+    at = None
+    if arguments.get("--at-operating-point"):
+        if getattr(model, "warning_operating_point", None) is None:
+            raise ValueError("--at-operating-point: the checkpoint carries no warning operating point; fit one with "
+                             "python -m buglab.models.operatingpoint")
+        at = at_operating_point(report, model.warning_operating_point)
+        sys.stdout.write(format_at_operating_point(at))
     if arguments.get("--report-json") is not None:
         with open(arguments["--report-json"], "w", encoding="utf-8") as f:
-            f.write(report_to_json(report))
+            f.write(report_to_json(report, at))
     return report.summary()
 
 
@@ -412,6 +457,7 @@ if __name__ == "__main__":
     p.add_argument("--sequential", action="store_true")
     p.add_argument("--on-device", action="store_true")
     p.add_argument("--report-json", default=None)
+    p.add_argument("--at-operating-point", action="store_true")
     p.add_argument("--minibatch-size", default=300)
     p.add_argument("--restore-path", default=None)
     p.add_argument("--quiet", action="store_true")
@@ -419,4 +465,4 @@ if __name__ == "__main__":
     ns = p.parse_args()
     run({"MODEL_FILENAME": ns.MODEL_FILENAME, "TEST_DATA_PATH": ns.TEST_DATA_PATH, "--assume-buggy": ns.assume_buggy,
          "--eval-only-no-bug": ns.eval_only_no_bug, "--limit-num-elements": ns.limit_num_elements, "--sequential": ns.sequential,
-         "--on-device": ns.on_device, "--report-json": ns.report_json})
+         "--on-device": ns.on_device, "--report-json": ns.report_json, "--at-operating-point": ns.at_operating_point})

@@ -197,6 +197,8 @@ _SIGNATURES = {
     "bl_eval_judge": ([c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int32,
                        c_int32, c_void_p, c_void_p, c_int64, c_int64, c_void_p], ctypes.c_int),
     "bl_bootstrap_counts": ([c_void_p, c_int64, c_int32, c_int32, c_uint64, c_int64, c_int64, c_void_p, c_void_p], ctypes.c_int),
+    "bl_bootstrap_curve_counts": ([c_void_p, c_void_p, c_int64, c_int32, c_int32, c_uint64, c_int64, c_int64, c_void_p, c_void_p],
+                                  ctypes.c_int),
     "bl_conf_loc_stats": ([c_void_p, c_int64, c_void_p, c_void_p, c_int32, c_double, c_double, c_void_p, c_void_p, c_void_p], ctypes.c_int),
     "bl_conf_group_stats": ([c_void_p, c_int64, c_void_p, c_void_p, c_int32, c_double, c_void_p, c_void_p, c_void_p], ctypes.c_int),
     "bl_conf_apply": ([c_void_p, c_int64, c_void_p, c_int32, c_int64, c_void_p, c_void_p, c_int32, c_int64, c_int64, c_double, c_double,

@@ -10,7 +10,7 @@ from ._cabi import _check, _f32, _i32, load_library, _p, _req, _stream
 
 __all__ = ["ENSEMBLE_KINDS", "ENSEMBLE_MAX_MEMBERS", "ensemble_combine", "SELECTOR_MAX_K", "_f64", "score_targets",
            "selector_sample", "REPORT_MAX_SAMPLES", "REPORT_INDEX_FIELDS", "report_summarize", "report_order", "EVAL_INDEX_FIELDS", "eval_judge",
-           "BOOTSTRAP_MAX_MODELS", "BOOTSTRAP_MAX_SCOUTS", "bootstrap_counts", "conf_loc_stats", "conf_group_stats", "conf_apply", "DEDUP_MAX_PERM",
+           "BOOTSTRAP_MAX_MODELS", "BOOTSTRAP_MAX_SCOUTS", "bootstrap_counts", "CURVE_MAX_BINS", "CURVE_COUNTERS", "bootstrap_curve_counts", "conf_loc_stats", "conf_group_stats", "conf_apply", "DEDUP_MAX_PERM",
            "DEDUP_EMPTY_SLOT", "_i64", "dedup_sha1_u32", "dedup_minhash", "dedup_lsh_insert_query"]
 
 
@@ -189,6 +189,37 @@ def bootstrap_counts(packed, M: int, K: int, seed: int, r0: int, R: int, out: Op
     if R:
         _check(load_library().bl_bootstrap_counts(packed.data_ptr(), packed.shape[0], M, K, int(seed) & 0xFFFFFFFFFFFFFFFF, int(r0), R,
                                                   out.data_ptr(), _stream()), "bl_bootstrap_counts")
+    return out[:R]
+
+
+CURVE_MAX_BINS = 1024  # BL_CURVE_MAX_BINS
+CURVE_COUNTERS = 5     # det_true | det_false | full_true | full_false | false_alarm
+
+
+def bootstrap_curve_counts(packed, bins, M: int, G: int, seed: int, r0: int, R: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The threshold-curve counts of bootstrap replicates r0 .. r0 + R - 1, int32 [R, 1 + M * 5 * G]: column 0 the replicate's
+    num_buggy, then [M][5][G] the cumulative counts over bins 0 .. g of the five counters of `_curves_of_ranked` (the columns:
+    include/buglab_hip.h).  packed int32 [n] as for `bootstrap_counts`; bins int16 [M, n], each value in [0, G] (G: the sample
+    passes no threshold of that model).  The draws are those of `bootstrap_counts`.  `out`: at least R rows of a larger buffer
+    to fill (the first R are written and returned).  Exactly buglab/models/_operatingpoint.py::curve_counts_host.  No sync."""
+    _i32(packed, "packed"), _req(bins, torch.int16, "bins")
+    M, G, R = int(M), int(G), int(R)
+    if packed.dim() != 1 or packed.shape[0] < 1:
+        raise ValueError(f"bootstrap_curve_counts: packed {tuple(packed.shape)} must be [n] with n >= 1")
+    if not 1 <= M <= BOOTSTRAP_MAX_MODELS or not 1 <= G <= CURVE_MAX_BINS or R < 0 or int(r0) < 0:
+        raise ValueError(f"bootstrap_curve_counts: need 1 <= M <= {BOOTSTRAP_MAX_MODELS}, 1 <= G <= {CURVE_MAX_BINS}, R >= 0 and "
+                         f"r0 >= 0 (got M {M}, G {G}, R {R}, r0 {r0})")
+    if tuple(bins.shape) != (M, packed.shape[0]) or bins.device != packed.device:
+        raise ValueError(f"bootstrap_curve_counts: bins {tuple(bins.shape)} must be [{M}, {packed.shape[0]}] on {packed.device}")
+    C = 1 + M * CURVE_COUNTERS * G
+    if out is None:
+        out = torch.empty((R, C), dtype=torch.int32, device=packed.device)
+    elif _i32(out, "out").dim() != 2 or out.shape[0] < R or out.shape[1] != C or out.device != packed.device:
+        raise ValueError(f"bootstrap_curve_counts: out {tuple(out.shape)} must be [>= {R}, {C}] on {packed.device}")
+    if R:
+        _check(load_library().bl_bootstrap_curve_counts(packed.data_ptr(), bins.data_ptr(), packed.shape[0], M, G,
+                                                        int(seed) & 0xFFFFFFFFFFFFFFFF, int(r0), R, out.data_ptr(), _stream()),
+               "bl_bootstrap_curve_counts")
     return out[:R]
 
 

@@ -12,6 +12,8 @@ Options:
     --only-incorrect           Print only snippets where the model has predicted something wrong.
     --order-by-confidence      Order by probability of the predicted action.
     --show-only-top-k=<num>    Show only the top-k. If k is zero, then show all. [default: 0]
+    --min-confidence=<p>       Show only warnings (a location is predicted) whose probability is at least p.
+    --at-operating-point       The same, at the checkpoint's warning operating point (buglab/models/operatingpoint.py).
     --report-json=<path>       Also write the report as data (the contexts the page is rendered from).
     --restore-path=<path>      Accepted for command-line compatibility (unused by the reference's run()).
     --quiet                    Accepted for command-line compatibility.
@@ -62,6 +64,8 @@ class Report(NamedTuple):
     selected: np.ndarray            # [len(snippets)] their indices among the scanned samples
     is_wrong: np.ndarray            # [n] bool, every scanned sample
     prediction_logprob: np.ndarray  # [n] float64, every scanned sample
+    warned: Optional[np.ndarray] = None  # [n] bool, every scanned sample: a location was predicted, not NO_BUG
+    confidence: Optional[np.ndarray] = None  # [n] float64: the predicted location's log-probability, what `evaluate` thresholds
 
     @property
     def num_scanned(self) -> int:
@@ -182,15 +186,57 @@ def _build_snippets(chunks: List[_Chunk], starts: List[int], order: np.ndarray, 
     return snippets
 
 
+def warning_threshold(model, min_confidence: Optional[float] = None, at_operating_point: bool = False) -> Optional[float]:
+    """The log-probability a warning must reach to be shown, or None (no filter): log(min_confidence), the checkpoint's
+    operating point, or the larger of the two."""
+    found = []
+    if min_confidence is not None:
+        if not 0 <= min_confidence <= 1:
+            raise ValueError(f"--min-confidence takes a probability in [0, 1] (got {min_confidence})")
+        found.append(float(np.log(min_confidence)) if min_confidence > 0 else -np.inf)
+    if at_operating_point:
+        point = getattr(model, "warning_operating_point", None)
+        if point is None:
+            raise ValueError("--at-operating-point: the checkpoint carries no warning operating point; fit one with "
+                             "python -m buglab.models.operatingpoint")
+        found.append(float(point.threshold_logprob))
+    return max(found) if found else None
+
+
+def _location_confidence(src, loc_idx, loc_off, pred_loc):
+    """The confidence `evaluate` thresholds, float64 [B]: the log-probability of each sample's predicted LOCATION (NO_BUG is the
+    last one) -- not `prediction_logprob`, which adds the best rewrite's.  NumPy arrays or tensors of one device alike; a sample
+    without a location entry gets NaN."""
+    if isinstance(src, np.ndarray):
+        first, end = loc_off[:-1].astype(np.int64), loc_off[1:].astype(np.int64)
+        at = np.clip(np.minimum(first + pred_loc, end - 1), 0, max(loc_idx.shape[0] - 1, 0))
+        if loc_idx.shape[0] == 0:
+            return np.full(first.shape[0], np.nan)
+        return np.where(end > first, src[loc_idx[at]].astype(np.float64), np.nan)
+    import torch
+
+    first, end = loc_off[:-1].long(), loc_off[1:].long()
+    if loc_idx.shape[0] == 0:
+        return torch.full((first.shape[0],), float("nan"), dtype=torch.float64, device=src.device)
+    at = torch.minimum(first + pred_loc.long(), end - 1).clamp_(0, loc_idx.shape[0] - 1)
+    value = src[loc_idx[at].long()].double()
+    return torch.where(end > first, value, torch.full_like(value, float("nan")))
+
+
 def _finish_host(chunks: List[_Chunk], parts_i: List[np.ndarray], parts_d: List[np.ndarray], only_incorrect: bool,
-                 order_by_confidence: bool, show_top_k: int) -> Report:
+                 order_by_confidence: bool, show_top_k: int, min_logprob: Optional[float] = None) -> Report:
     n_per = [len(c.datapoints) for c in chunks]
     starts = np.concatenate([[0], np.cumsum(n_per)]).astype(np.int64).tolist()
     sample_i = np.concatenate(parts_i, axis=1) if parts_i else np.zeros((3, 0), np.int32)
     sample_d = np.concatenate(parts_d, axis=1) if parts_d else np.zeros((2, 0), np.float64)
+    confidence = np.concatenate([_location_confidence(np.asarray(c.src), np.asarray(c.ix.loc_idx), np.asarray(c.ix.loc_off), si[0])
+                                 for c, si in zip(chunks, parts_i)]) if parts_i else np.zeros(0, np.float64)
     keep = sample_i[2] if only_incorrect else np.ones(sample_i.shape[1], np.int32)
+    if min_logprob is not None:
+        keep = ((keep != 0) & (sample_i[1] == 0) & (confidence >= min_logprob)).astype(np.int32)
     order = R.order_host(sample_d[0], keep, order_by_confidence, show_top_k)
-    return Report(_build_snippets(chunks, starts, order, sample_i, sample_d), order, sample_i[2] != 0, sample_d[0].copy())
+    return Report(_build_snippets(chunks, starts, order, sample_i, sample_d), order, sample_i[2] != 0, sample_d[0].copy(),
+                  sample_i[1] == 0, confidence)
 
 
 def triples_indices(triples: Sequence[Tuple[Any, Dict[int, float], List[float]]]
@@ -220,10 +266,10 @@ def triples_indices(triples: Sequence[Tuple[Any, Dict[int, float], List[float]]]
 
 
 def predictions_to_report(predictions: Iterable[Tuple[Any, Dict[int, float], List[float]]], only_show_incorrect_predictions: bool = False,
-                          order_results_by_confidence: bool = False, show_top_k: int = 0) -> Report:
+                          order_results_by_confidence: bool = False, show_top_k: int = 0, min_logprob: Optional[float] = None) -> Report:
     """The report of `predict` triples that already exist (the model explorer's use), through the NumPy twins of the two
     kernels.  The location order of a sample is the key order of its dict; NO_BUG (-1) must be its last key, as every
-    `predict` here yields it."""
+    `predict` here yields it.  `min_logprob`: keep only the warnings whose predicted location has at least that log-probability."""
     chunks, parts_i, parts_d = [], [], []
     it = iter(predictions)
     while True:
@@ -234,19 +280,23 @@ def predictions_to_report(predictions: Iterable[Tuple[Any, Dict[int, float], Lis
         best_rw, best_range, si, sd = R.summarize_host(flat, ix)
         chunks.append(_Chunk([t[0] for t in triples], ix, groups, keys, flat, best_rw, best_range))
         parts_i.append(si), parts_d.append(sd)
-    return _finish_host(chunks, parts_i, parts_d, only_show_incorrect_predictions, order_results_by_confidence, int(show_top_k))
+    return _finish_host(chunks, parts_i, parts_d, only_show_incorrect_predictions, order_results_by_confidence, int(show_top_k),
+                        min_logprob)
 
 
 def scan(model, nn, data: Iterable[Any], device, *, parallelize: bool = False, only_incorrect: bool = False,
-         order_by_confidence: bool = False, show_top_k: int = 0) -> Report:
+         order_by_confidence: bool = False, show_top_k: int = 0, min_confidence: Optional[float] = None,
+         at_operating_point: bool = False) -> Report:
     """Run `model` over `data` (datapoints) and report: which samples are shown, in which order, and their contexts.  The
-    samples the model's `tensorize` rejects are skipped, as `predict` skips them."""
+    samples the model's `tensorize` rejects are skipped, as `predict` skips them.  `min_confidence` (a probability) and
+    `at_operating_point` (the model's `warning_operating_point`) keep only the warnings at or above that confidence."""
     import torch
 
     from buglab.controllers import _batching as Bt
     from buglab.models import hip_ops
 
     Bt.require_single_model(model, "scan")
+    min_logprob = warning_threshold(model, min_confidence, at_operating_point)
     device = torch.device(device)
     on_gpu = device.type == "cuda"
 
@@ -257,7 +307,7 @@ def scan(model, nn, data: Iterable[Any], device, *, parallelize: bool = False, o
             out["device"] = dict(zip(hip_ops.REPORT_INDEX_FIELDS, Bt.to_device_i32([getattr(ix, f) for f in hip_ops.REPORT_INDEX_FIELDS], dev)))
         return out
 
-    chunks, parts_i, parts_d = [], [], []
+    chunks, parts_i, parts_d, parts_c = [], [], [], []
     nn.eval()
     with torch.no_grad(), model._tensorize_all_location_rewrites():
         for mb, _tags in Bt.prediction_minibatches(model, ((d, None) for d in data), device, parallelize, extend, lambda tag: None,
@@ -266,21 +316,26 @@ def scan(model, nn, data: Iterable[Any], device, *, parallelize: bool = False, o
             points, ix, groups, keys = mb["selfsup"]["host"]
             if on_gpu:
                 best_rw, best_range, si, sd = hip_ops.report_summarize(flat, mb["selfsup"]["device"])
+                parts_c.append(_location_confidence(flat, mb["selfsup"]["device"]["loc_idx"], mb["selfsup"]["device"]["loc_off"], si[0]))
             else:
                 flat = flat.numpy()
                 best_rw, best_range, si, sd = R.summarize_host(flat, ix)
             chunks.append(_Chunk(points, ix, groups, keys, flat, best_rw, best_range))
             parts_i.append(si), parts_d.append(sd)
     if not on_gpu:
-        return _finish_host(chunks, parts_i, parts_d, only_incorrect, order_by_confidence, int(show_top_k))
+        return _finish_host(chunks, parts_i, parts_d, only_incorrect, order_by_confidence, int(show_top_k), min_logprob)
     starts = np.concatenate([[0], np.cumsum([len(c.datapoints) for c in chunks])]).astype(np.int64).tolist()
     if not chunks:
-        return Report([], np.zeros(0, np.int32), np.zeros(0, bool), np.zeros(0, np.float64))
+        return Report([], np.zeros(0, np.int32), np.zeros(0, bool), np.zeros(0, np.float64), np.zeros(0, bool), np.zeros(0, np.float64))
     sample_i, sample_d = torch.cat(parts_i, dim=1).contiguous(), torch.cat(parts_d, dim=1).contiguous()  # the growing buffers
+    confidence = torch.cat(parts_c)
     keep = sample_i[2] if only_incorrect else torch.ones_like(sample_i[2])
+    if min_logprob is not None:
+        keep = ((keep != 0) & (sample_i[1] == 0) & (confidence >= min_logprob)).to(torch.int32)
     order = hip_ops.report_order(sample_d[0], keep, by_confidence=order_by_confidence, k=int(show_top_k)).cpu().numpy()
     sample_i, sample_d = sample_i.cpu().numpy(), sample_d.cpu().numpy()  # the verdicts: 3 int32 and 2 doubles per sample
-    return Report(_build_snippets(chunks, starts, order, sample_i, sample_d), order, sample_i[2] != 0, sample_d[0].copy())
+    return Report(_build_snippets(chunks, starts, order, sample_i, sample_d), order, sample_i[2] != 0, sample_d[0].copy(),
+                  sample_i[1] == 0, confidence.cpu().numpy())
 
 
 # ------------------------------------------------------------------------------------------------
@@ -394,6 +449,8 @@ def parse_args(argv=None) -> argparse.Namespace:
     p.add_argument("--only-incorrect", action="store_true")
     p.add_argument("--order-by-confidence", action="store_true")
     p.add_argument("--show-only-top-k", type=int, default=0)
+    p.add_argument("--min-confidence", type=float, default=None)
+    p.add_argument("--at-operating-point", action="store_true")
     p.add_argument("--report-json", default=None)
     p.add_argument("--restore-path", default=None)
     p.add_argument("--quiet", action="store_true")
@@ -421,7 +478,8 @@ def run(args: argparse.Namespace) -> Report:
         data = (d for d in data if d["target_fix_action_idx"] is None)
     model, nn = AbstractNeuralModel.restore_model(Path(args.MODEL_FILENAME), device)
     report = scan(model, nn, data, device, parallelize=not args.sequential, only_incorrect=args.only_incorrect,
-                  order_by_confidence=args.order_by_confidence, show_top_k=args.show_only_top_k)
+                  order_by_confidence=args.order_by_confidence, show_top_k=args.show_only_top_k, min_confidence=args.min_confidence,
+                  at_operating_point=args.at_operating_point)
     with open(args.OUT_HTML, "w", encoding="utf-8") as f:
         f.write(report_to_html(report.snippets))
     if args.report_json is not None:
