@@ -827,6 +827,49 @@ int bl_eval_judge(const float* src, int64_t n_src, const int32_t* loc_idx, const
                   int64_t capacity, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Ranked suggestions (buglab/models/suggest.py, buglab/models/evaluate.py --top-k), in csrc/bl_suggest.hip.  BEYOND THE
+ * REFERENCE: its evaluate.py:60-140 and visualize.py:75-144 reduce a sample to one answer (the first-maximum location, then the
+ * best rewrite there); nothing there ranks a sample's fixes.  Same conventions as the evaluation: src = a model's flat fp32
+ * output (n_src floats), int32 indices, DOUBLE log-probabilities, no atomics, bit-identical from run to run, an index outside
+ * [0, n_src) reads as NaN.
+ *
+ * bl_rank_suggestions, one launch per predict minibatch of B samples, no synchronisation.  Sample b has
+ * n_b = rw_off[b + 1] - rw_off[b] candidate rewrites and n_b + 1 ENTRIES: entry i < n_b is rewrite i (original index), entry n_b
+ * is NO_BUG.  It owns
+ *   rw_idx [rw_off[b] : rw_off[b + 1]]     its rewrites by original index (as PredictionLayout); alongside rw_loc_idx: the flat
+ *                                          index of the location entry of the rewrite's reference node, -1 where that node has no
+ *                                          location key; and rw_node: the dense id of that node (as bl_eval_judge);
+ *   nobug_idx[b]                           NO_BUG's location entry in src;
+ *   tgt_rw[b]                              target_fix_action_idx (an index within the sample's rewrites), negative without a bug;
+ *   loc_idx[loc_off[b] : loc_off[b + 1]]   its location entries in the key order of the dict `predict` yields, NO_BUG last, and
+ *                                          key_node alongside (as bl_eval_judge: -1 for NO_BUG).
+ * The VALUE of entry i < n_b is (double)src[rw_idx[i]] + (double)src[rw_loc_idx[i]], one fp64 addition (the g_i of
+ * bl_selector_sample; NaN where rw_loc_idx is -1); of NO_BUG, (double)src[nobug_idx[b]].  With skip_nobug != 0 the NO_BUG entry
+ * does not take part; values are not renormalised (a common shift changes no rank).  An entry whose value is NaN or not strictly
+ * above -inf is NOT RANKABLE: it precedes nothing and is never listed.  TOTAL ORDER: a precedes b iff v_a > v_b, or v_a == v_b
+ * and a < b.  The RANK of an entry is the number of rankable entries that precede it.
+ * Results go to sample offset + b of buffers the caller keeps for the whole run (capacity samples; offset + B <= capacity):
+ *   out_entry   [capacity, K] int32   the first min(K, #rankable) entries in that order, then -1;
+ *   out_logprob [capacity, K] double  their values, then -inf;
+ *   out_rank    [2, capacity] int32   row 0, the joint rank of the TRUTH entry: tgt_rw[b], or NO_BUG's entry without a bug;
+ *                                     -1 if that entry is not rankable, if tgt_rw[b] >= n_b, or if it is NO_BUG under skip_nobug.
+ *                                     Row 1, the location rank: the same order and rule over the values src[loc_idx[.]] of the
+ *                                     sample's location entries (all but the last under skip_nobug); the truth is the first entry
+ *                                     whose key_node equals rw_node[tgt_rw[b]], or the last entry (NO_BUG) without a bug; -1 if
+ *                                     there is no such entry or it is not rankable.
+ * No exp or log is taken: one addition, compares and integer counts, so buglab/models/_suggest.py::rank_host gives the same bits.
+ * Joint rank 0 is NOT bl_eval_judge's `repaired`: that takes the best rewrite at the first-maximum location, this ranks the sums.
+ * A segment of at most 4096 entries is staged in LDS; a longer one is recomputed from src in every round (no length is refused).
+ * BL_EINVAL: K < 1, null pointers, negative sizes, offset + B > capacity.  BL_ERANGE: K > BL_SUGGEST_MAX_K, or n_src, total_loc
+ * or total_rw + 1 beyond int32. */
+#define BL_SUGGEST_MAX_K 32
+int bl_rank_suggestions(const float* src, int64_t n_src, const int32_t* rw_idx, const int32_t* rw_loc_idx, const int32_t* rw_off,
+                        int64_t total_rw, const int32_t* nobug_idx, const int32_t* tgt_rw, const int32_t* loc_idx,
+                        const int32_t* loc_off, const int32_t* key_node, int64_t total_loc, const int32_t* rw_node, int32_t B, int32_t K,
+                        int32_t skip_nobug, int32_t* out_entry, double* out_logprob, int32_t* out_rank, int64_t offset,
+                        int64_t capacity, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Paired bootstrap of the evaluation counts (buglab/models/compare.py), in csrc/bl_bootstrap.hip.  BEYOND THE REFERENCE: it
  * has no counterpart -- its evaluate.py prints point estimates only.  What is resampled are the counts of
  * buglab/models/evaluate.py:139-173 (the numerators and denominators of every metric and of the per-scout tables): each

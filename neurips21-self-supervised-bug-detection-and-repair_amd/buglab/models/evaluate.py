@@ -10,6 +10,11 @@ Options:
     --sequential               Do not parallelize data loading. Makes debugging easier.
     --on-device                Judge every predict minibatch on the device (single models only; same report).
     --report-json=<path>       Also write the report as data: summary, per-scout tables and curves.
+    --top-k=<K>                After the report, a block on ranked suggestions (buglab/models/suggest.py): the share of samples
+                               whose true fix, and whose true location, is within the model's top 1..K, and the mean reciprocal
+                               ranks.  The fix is ranked among the sample's rewrites and NO_BUG by JOINT probability (location
+                               times rewrite), so its top-1 is not the "Accuracy" above, which takes the best rewrite at the
+                               most probable location.  1 <= K <= 32.
     --at-operating-point       After the report, what the checkpoint's warning operating point gives on this data
                                (buglab/models/operatingpoint.py): warnings raised, precisions and recalls at that threshold.
     --minibatch-size=<size>    Accepted for command-line compatibility (the reference parses and ignores it too).
@@ -30,6 +35,10 @@ Two paths give the same report.  The default one walks the `(datapoint, location
 output on the device, judges each predict minibatch there in one launch (hip_ops.eval_judge, csrc/bl_evaluate.hip, through the
 index arrays of buglab/models/_evaluate.py), keeps the outcome columns on the device for the whole run and copies them back once;
 the counts and curves are then the same NumPy code on columns (`ColumnarEvaluationReport`).
+
+`--top-k K` adds, on both paths, the ranks of the true fix and of the true location (buglab/models/_suggest.py: the host path
+ranks each triple with `suggestions_of_prediction`, the device path launches hip_ops.rank_suggestions next to the judge) and
+prints `top_k_summary` of the two rank columns after the report.  Without the flag nothing of this is allocated or launched.
 """
 import argparse
 import json
@@ -127,8 +136,16 @@ class EvaluationReport:
     """Aggregates SampleOutcomes; `summary()` = the scalar metrics, `curves()` = the threshold curves, `format()` =
     the text the reference prints."""
 
+    top_k: Optional[Dict[str, Any]] = None  # `_suggest.top_k_summary` of the run, when it was asked for (--top-k)
+
     def __init__(self, outcomes: Iterable[SampleOutcome], eval_only_no_bug: bool = False):
         self.outcomes: List[SampleOutcome] = [o for o in outcomes if not (eval_only_no_bug and o.has_bug)]
+
+    def format_top_k(self) -> str:
+        """The ranked-suggestions block printed after `format()`; empty when the run did not rank."""
+        from buglab.models._suggest import format_top_k
+
+        return "" if self.top_k is None else format_top_k(self.top_k)
 
     # ---- counts ---------------------------------------------------------------------------------
     def _count(self, pred) -> int:
@@ -216,15 +233,39 @@ class EvaluationReport:
         return "\n".join(lines) + "\n"
 
 
-def evaluate_predictions(predictions, assume_buggy: bool = False, eval_only_no_bug: bool = False) -> EvaluationReport:
+def evaluate_predictions(predictions, assume_buggy: bool = False, eval_only_no_bug: bool = False, top_k: Optional[int] = None
+                         ) -> EvaluationReport:
     """`predictions` = what `model.predict` yields.  With `eval_only_no_bug` the buggy samples are skipped before
-    anything is computed for them (:69-70)."""
-    outcomes = []
+    anything is computed for them (:69-70).  With `top_k` every judged sample is also ranked (`suggestions_of_prediction`) and
+    the report carries `top_k_summary` of the ranks."""
+    from buglab.models import _suggest as S
+
+    if top_k is not None:
+        top_k = _checked_top_k(top_k)
+    outcomes, ranks = [], []
     for datapoint, location_logprobs, rewrite_logprobs in predictions:
         if eval_only_no_bug and datapoint["target_fix_action_idx"] is not None:
             continue
         outcomes.append(judge_sample(datapoint, location_logprobs, rewrite_logprobs, assume_buggy))
-    return EvaluationReport(outcomes)
+        if top_k is not None:  # the ranks do not depend on how many entries are listed
+            ranked = S.suggestions_of_prediction(datapoint, location_logprobs, rewrite_logprobs, 1, assume_buggy)
+            ranks.append((ranked.truth_rank, ranked.truth_location_rank))
+    report = EvaluationReport(outcomes)
+    if top_k is not None:
+        names = ["NoBug"] + sorted({o.scout for o in outcomes} - {"NoBug"})
+        ids = {name: i for i, name in enumerate(names)}
+        columns = np.asarray(ranks, dtype=np.int32).reshape(-1, 2)
+        report.top_k = S.top_k_summary(columns[:, 0], columns[:, 1], [o.has_bug for o in outcomes], [ids[o.scout] for o in outcomes],
+                                       names, top_k)
+    return report
+
+
+def _checked_top_k(top_k) -> int:
+    from buglab.models._suggest import MAX_K
+
+    if not 1 <= int(top_k) <= MAX_K:
+        raise ValueError(f"--top-k must be in [1, {MAX_K}] (got {top_k})")
+    return int(top_k)
 
 
 class ColumnarEvaluationReport(EvaluationReport):
@@ -315,7 +356,8 @@ class ColumnarEvaluationReport(EvaluationReport):
 
 
 def evaluate_on_device(model, nn, data: Iterable[Any], device, *, assume_buggy: bool = False, eval_only_no_bug: bool = False,
-                       parallelize: bool = True, positions_out: Optional[list] = None) -> ColumnarEvaluationReport:
+                       parallelize: bool = True, positions_out: Optional[list] = None, top_k: Optional[int] = None
+                       ) -> ColumnarEvaluationReport:
     """`evaluate_predictions(model.predict(data, nn, device, parallelize), ...)` without the per-sample host work: the
     minibatches `predict` forms (same `tensorize`, same 50 samples), the same forward, and one hip_ops.eval_judge launch per
     minibatch that writes the verdicts into outcome buffers kept on the device until the end (24 bytes per sample, one copy
@@ -323,32 +365,43 @@ def evaluate_on_device(model, nn, data: Iterable[Any], device, *, assume_buggy: 
     `predict`, so that a sequence model's minibatches -- and with them its fp32 values -- are those of the host path; the buggy
     samples are left out of the report.  Single models only: an ensemble keeps the host path.  `positions_out`, when given,
     receives the position in `data` of every judged sample, in the order of the outcome columns before `eval_only_no_bug`
-    (a datapoint `tensorize` rejects has none): what buglab/models/compare.py pairs two models' samples by."""
+    (a datapoint `tensorize` rejects has none): what buglab/models/compare.py pairs two models' samples by.  With `top_k` one
+    hip_ops.rank_suggestions launch follows each judge launch, on index arrays that extend the judge's by two, and writes the
+    ranks of the true fix and the true location into buffers kept next to the outcome buffers (the ranks do not depend on how
+    many entries are listed, so one is); they are copied back after the outcomes and the report carries `top_k_summary`."""
     from buglab.controllers import _batching as Bt
     from buglab.models import _evaluate as E
+    from buglab.models import _suggest as S
     from buglab.models import hip_ops
 
     Bt.require_single_model(model, "evaluate_on_device")
+    if top_k is not None:
+        top_k = _checked_top_k(top_k)
+    index_fields = hip_ops.EVAL_INDEX_FIELDS if top_k is None else hip_ops.SUGGEST_INDEX_FIELDS  # (the second holds the first)
     device = torch.device(device)
     names, ids = ["NoBug"], {"NoBug": 0}
     has_bug: List[bool] = []
     scout: List[int] = []
 
     def extend(layout, points, dev, mb):
-        ix = E.eval_indices(layout, points, mb.get("node_mappings"))
+        ix = (E.eval_indices if top_k is None else S.suggest_indices)(layout, points, mb.get("node_mappings"))
         if assume_buggy:
             E.check_assume_buggy(ix)
         targets = [p["target_fix_action_idx"] for p in points]
         scouts = ["NoBug" if t is None else p["candidate_rewrite_metadata"][t][0] for p, t in zip(points, targets)]
-        return {"ix": dict(zip(hip_ops.EVAL_INDEX_FIELDS, Bt.to_device_i32([getattr(ix, f) for f in hip_ops.EVAL_INDEX_FIELDS], dev))),
-                "scouts": scouts}
+        return {"ix": dict(zip(index_fields, Bt.to_device_i32([getattr(ix, f) for f in index_fields], dev))), "scouts": scouts}
 
     def buffers(capacity):  # [confidence | the four verdict rows] in one allocation: one copy back
         blob = torch.empty(3 * capacity, dtype=torch.float64, device=device)
         return blob, blob[:capacity], blob[capacity:].view(torch.int32).view(4, capacity)
 
+    def rank_buffers(capacity):  # [the two rank rows | one listed entry | its log-probability]
+        return (torch.empty((2, capacity), dtype=torch.int32, device=device), torch.empty((capacity, 1), dtype=torch.int32, device=device),
+                torch.empty((capacity, 1), dtype=torch.float64, device=device))
+
     capacity = max(len(data), 1) if hasattr(data, "__len__") else 1 << 14
     blob, conf, verdict = buffers(capacity)
+    ranks = rank_buffers(capacity) if top_k is not None else None
     n = 0
     nn.eval()
     with torch.no_grad(), model._tensorize_all_location_rewrites():
@@ -364,7 +417,13 @@ def evaluate_on_device(model, nn, data: Iterable[Any], device, *, assume_buggy: 
                 _, new_conf, new_verdict = grown = buffers(capacity)
                 new_conf[:n].copy_(conf[:n]), new_verdict[:, :n].copy_(verdict[:, :n])
                 blob, conf, verdict = grown
+                if ranks is not None:
+                    new_ranks = rank_buffers(capacity)
+                    new_ranks[0][:, :n].copy_(ranks[0][:, :n])
+                    ranks = new_ranks
             hip_ops.eval_judge(flat, mb["selfsup"]["ix"], conf, verdict, n, assume_buggy=assume_buggy)
+            if ranks is not None:
+                hip_ops.rank_suggestions(flat, mb["selfsup"]["ix"], *ranks, n, k=1, skip_nobug=assume_buggy)
             for name in mb["selfsup"]["scouts"]:
                 has_bug.append(name != "NoBug")
                 scout.append(ids.setdefault(name, len(ids)))
@@ -373,8 +432,13 @@ def evaluate_on_device(model, nn, data: Iterable[Any], device, *, assume_buggy: 
             n += B
     host = blob.cpu()  # the one copy (and the one synchronisation) of the run
     conf, verdict = host[:capacity][:n].numpy(), host[capacity:].view(torch.int32).view(4, capacity)[:, :n].numpy()
-    return ColumnarEvaluationReport(conf, has_bug, verdict[0] != 0, verdict[1] != 0, verdict[2], verdict[3] != 0, scout, names,
-                                    eval_only_no_bug)
+    report = ColumnarEvaluationReport(conf, has_bug, verdict[0] != 0, verdict[1] != 0, verdict[2], verdict[3] != 0, scout, names,
+                                      eval_only_no_bug)
+    if ranks is not None:
+        columns = ranks[0][:, :n].cpu().numpy()
+        keep = ~np.asarray(has_bug, dtype=bool) if eval_only_no_bug else np.ones(n, dtype=bool)
+        report.top_k = S.top_k_summary(columns[0][keep], columns[1][keep], report.has_bug, report.scout, names, top_k)
+    return report
 
 
 def at_operating_point(report: EvaluationReport, point) -> Dict[str, Any]:
@@ -416,6 +480,8 @@ def report_to_json(report: EvaluationReport, at: Optional[Dict[str, Any]] = None
     blob = {"summary": report.summary(), "per_scout": report.per_scout(), "curves": {k: v.tolist() for k, v in report.curves().items()}}
     if at is not None:
         blob["at_operating_point"] = at
+    if report.top_k is not None:
+        blob["top_k"] = report.top_k
     return json.dumps(blob, indent=1, sort_keys=True) + "\n"
 
 
@@ -427,13 +493,16 @@ def run(arguments):
         raise RuntimeError("evaluate.py: no ROCm GPU visible; the BugLab hot path has no CPU fallback")
     device = torch.device("cuda")
     model, nn = GnnBugLabModel.restore_model(Path(arguments["MODEL_FILENAME"]), device)
+    top_k = None if arguments.get("--top-k") is None else _checked_top_k(arguments["--top-k"])
     if arguments.get("--on-device"):
         report = evaluate_on_device(model, nn, data, device, assume_buggy=arguments["--assume-buggy"],
-                                    eval_only_no_bug=arguments["--eval-only-no-bug"], parallelize=not arguments["--sequential"])
+                                    eval_only_no_bug=arguments["--eval-only-no-bug"], parallelize=not arguments["--sequential"],
+                                    top_k=top_k)
     else:
         predictions = model.predict(data, nn, device, parallelize=not arguments["--sequential"])
-        report = evaluate_predictions(predictions, arguments["--assume-buggy"], arguments["--eval-only-no-bug"])
+        report = evaluate_predictions(predictions, arguments["--assume-buggy"], arguments["--eval-only-no-bug"], top_k)
     sys.stdout.write(report.format())
+    sys.stdout.write(report.format_top_k())
     at = None
     if arguments.get("--at-operating-point"):
         if getattr(model, "warning_operating_point", None) is None:
@@ -458,6 +527,7 @@ if __name__ == "__main__":
     p.add_argument("--on-device", action="store_true")
     p.add_argument("--report-json", default=None)
     p.add_argument("--at-operating-point", action="store_true")
+    p.add_argument("--top-k", default=None, type=int)
     p.add_argument("--minibatch-size", default=300)
     p.add_argument("--restore-path", default=None)
     p.add_argument("--quiet", action="store_true")
@@ -465,4 +535,5 @@ if __name__ == "__main__":
     ns = p.parse_args()
     run({"MODEL_FILENAME": ns.MODEL_FILENAME, "TEST_DATA_PATH": ns.TEST_DATA_PATH, "--assume-buggy": ns.assume_buggy,
          "--eval-only-no-bug": ns.eval_only_no_bug, "--limit-num-elements": ns.limit_num_elements, "--sequential": ns.sequential,
-         "--on-device": ns.on_device, "--report-json": ns.report_json, "--at-operating-point": ns.at_operating_point})
+         "--on-device": ns.on_device, "--report-json": ns.report_json, "--at-operating-point": ns.at_operating_point,
+         "--top-k": ns.top_k})

@@ -196,6 +196,9 @@ _SIGNATURES = {
     "bl_report_order": ([c_void_p, c_void_p, c_int64, c_int64, c_int32, c_void_p, c_void_p, c_void_p], ctypes.c_int),
     "bl_eval_judge": ([c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int32,
                        c_int32, c_void_p, c_void_p, c_int64, c_int64, c_void_p], ctypes.c_int),
+    "bl_rank_suggestions": ([c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                             c_int64, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p],
+                            ctypes.c_int),
     "bl_bootstrap_counts": ([c_void_p, c_int64, c_int32, c_int32, c_uint64, c_int64, c_int64, c_void_p, c_void_p], ctypes.c_int),
     "bl_bootstrap_curve_counts": ([c_void_p, c_void_p, c_int64, c_int32, c_int32, c_uint64, c_int64, c_int64, c_void_p, c_void_p],
                                   ctypes.c_int),

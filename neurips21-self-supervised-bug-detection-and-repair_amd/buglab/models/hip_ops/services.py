@@ -10,6 +10,7 @@ from ._cabi import _check, _f32, _i32, load_library, _p, _req, _stream
 
 __all__ = ["ENSEMBLE_KINDS", "ENSEMBLE_MAX_MEMBERS", "ensemble_combine", "SELECTOR_MAX_K", "_f64", "score_targets",
            "selector_sample", "REPORT_MAX_SAMPLES", "REPORT_INDEX_FIELDS", "report_summarize", "report_order", "EVAL_INDEX_FIELDS", "eval_judge",
+           "SUGGEST_MAX_K", "SUGGEST_INDEX_FIELDS", "rank_suggestions",
            "BOOTSTRAP_MAX_MODELS", "BOOTSTRAP_MAX_SCOUTS", "bootstrap_counts", "CURVE_MAX_BINS", "CURVE_COUNTERS", "bootstrap_curve_counts", "conf_loc_stats", "conf_group_stats", "conf_apply", "DEDUP_MAX_PERM",
            "DEDUP_EMPTY_SLOT", "_i64", "dedup_sha1_u32", "dedup_minhash", "dedup_lsh_insert_query"]
 
@@ -161,6 +162,44 @@ def eval_judge(src, ix, out_conf, out_verdict, offset: int, *, assume_buggy: boo
     _check(load_library().bl_eval_judge(src.data_ptr(), src.numel(), p("loc_idx"), p("loc_off"), p("key_node"), total_loc, p("rw_idx"),
                                         p("rw_off"), p("rw_node"), total_rw, p("tgt_rw"), B, int(bool(assume_buggy)),
                                         out_conf.data_ptr(), out_verdict.data_ptr(), offset, N, _stream()), "bl_eval_judge")
+
+
+# ------------------------------------------------------------------------------------------------
+# ranked suggestions (csrc/bl_suggest.hip; include/buglab_hip.h::bl_rank_suggestions)
+SUGGEST_MAX_K = 32  # BL_SUGGEST_MAX_K
+SUGGEST_INDEX_FIELDS = ("rw_idx", "rw_loc_idx", "rw_off", "nobug_idx", "tgt_rw", "loc_idx", "loc_off", "key_node", "rw_node")
+
+
+def rank_suggestions(src, ix, out_rank, out_entry, out_logprob, offset: int, *, k: int, skip_nobug: bool = False) -> None:
+    """The k most probable fixes of every sample of one predict minibatch of B samples from a model's flat fp32 output `src`, and
+    the ranks of the true fix and the true location, written to samples offset .. offset + B - 1 of the run-long buffers out_rank
+    (int32 [2, N] = joint rank | location rank, -1: none), out_entry (int32 [N, k]: entries in rank order, the sample's rewrite
+    count = NO_BUG, -1 padded) and out_logprob (float64 [N, k], -inf padded).  `ix`: a mapping with the int32 tensors of
+    SUGGEST_INDEX_FIELDS (buglab/models/_suggest.py::suggest_indices).  Exactly buglab/models/_suggest.py::rank_host.  No sync."""
+    _f32(src, "src"), _i32(out_rank, "out_rank"), _i32(out_entry, "out_entry"), _f64(out_logprob, "out_logprob")
+    t = {name: _i32(ix[name], name) for name in SUGGEST_INDEX_FIELDS}
+    k = int(k)
+    B, total_loc, total_rw = t["tgt_rw"].shape[0], t["loc_idx"].shape[0], t["rw_idx"].shape[0]
+    sizes = {"rw_idx": total_rw, "rw_loc_idx": total_rw, "rw_off": B + 1, "nobug_idx": B, "tgt_rw": B, "loc_idx": total_loc,
+             "loc_off": B + 1, "key_node": total_loc, "rw_node": total_rw}
+    bad = {name: tuple(t[name].shape) for name, n in sizes.items() if t[name].dim() != 1 or t[name].shape[0] != n}
+    if bad:
+        raise ValueError(f"rank_suggestions: inconsistent shapes (B {B}, total_loc {total_loc}, total_rw {total_rw}): {bad}")
+    if not 1 <= k <= SUGGEST_MAX_K:
+        raise ValueError(f"rank_suggestions: k must be in [1, {SUGGEST_MAX_K}] (got {k})")
+    N = out_rank.shape[1] if out_rank.dim() == 2 else -1
+    if tuple(out_rank.shape) != (2, N) or tuple(out_entry.shape) != (N, k) or tuple(out_logprob.shape) != (N, k) \
+            or any(o.device != src.device for o in (out_rank, out_entry, out_logprob)):
+        raise ValueError(f"rank_suggestions: out_rank {tuple(out_rank.shape)} must be [2, N], out_entry {tuple(out_entry.shape)} and "
+                         f"out_logprob {tuple(out_logprob.shape)} [N, {k}], all on {src.device}")
+    offset = int(offset)
+    if not 0 <= offset <= N - B:
+        raise ValueError(f"rank_suggestions: samples {offset} .. {offset + B} do not fit the result buffers of {N} samples")
+    p = lambda name: t[name].data_ptr()
+    _check(load_library().bl_rank_suggestions(src.data_ptr(), src.numel(), p("rw_idx"), p("rw_loc_idx"), p("rw_off"), total_rw,
+                                              p("nobug_idx"), p("tgt_rw"), p("loc_idx"), p("loc_off"), p("key_node"), total_loc,
+                                              p("rw_node"), B, k, int(bool(skip_nobug)), out_entry.data_ptr(), out_logprob.data_ptr(),
+                                              out_rank.data_ptr(), offset, N, _stream()), "bl_rank_suggestions")
 
 
 # ------------------------------------------------------------------------------------------------
