@@ -725,6 +725,48 @@ int bl_ensemble_combine(const float* src, int64_t n_src, const int32_t* loc_idx,
                         const int32_t* rw_idx, const int32_t* rw_off, int64_t total_rw, int32_t M, int32_t B, int32_t kind,
                         double* out_loc, double* out_rw, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Fitted ensembles (buglab/models/ensemble/fit.py, the `weighted` kind), in csrc/bl_ensemble_fit.hip.  BEYOND THE REFERENCE: it
+ * has no counterpart -- its ensembles weigh every present member 1 / M' (buglab/models/ensemble/wrapper.py:33-89, whose
+ * canonical per-sample layout is the one used here: np.unique(reference_nodes) ascending then NO_BUG, rewrites by original
+ * index).  One weight per member for each head and one inverse temperature per member for the location distribution; per
+ * sample, with P the present members and l_m member m's fp32 log-probabilities:
+ *   locations  z_m = beta_m l_m;  s_m = z_m - LSE z_m (beta_m == 1 exactly: s_m = l_m, the member's values as they are);
+ *              a_m = theta_m - LSE_{k in P} theta_k;  out_i = LSE_{m in P} (a_m + s_m[i]);
+ *   rewrites   b_m = phi_m - LSE_{k in P} phi_k;      out_r = LSE_{m in P} (b_m + l_m[r]).
+ * fp64 throughout, compiled without fused multiply-adds; buglab/models/ensemble/_weights.py is the same arithmetic in NumPy.  In
+ * the statistics every LSE subtracts its first maximum and takes log1p of the sum without it, and entries that are not above
+ * -inf are skipped (they enter no maximum and no sum).  theta, beta, phi: M doubles each ON THE HOST, read before the launch.
+ *
+ * bl_ens_loc_stats: a POOL of S location segments; member m's values of segment s are vals[m * total + seg_off[s] .. seg_off[s + 1]]
+ *   (offsets clamped to [0, total]), present[m * S + s] != 0 where member m predicts the sample, the target at place tgt[s].
+ *   With F = -sum_s out_s[tgt[s]], r_m = exp(a_m + s_m[tgt] + F_s) and pi = softmax of theta over P:
+ *   out[0] = F, out[1 + m] = dF/dtheta_m = -sum_s (r_m - pi_m), out[1 + M + m] = dF/dbeta_m = -sum_s r_m (l_m[tgt] - E_m[l]),
+ *   E_m[l] = sum_i exp(s_m[i]) l_m[i].  A segment without a present member contributes 0; one where a present member has
+ *   nothing above -inf, the target lies outside, or no present member gives the target a probability contributes NaN.
+ *   One wave per segment (any length); the segments' terms go to partials ([1 + 2M, S] doubles, the caller's) and a second
+ *   kernel sums each column in an order fixed by S alone: no atomics, bit-identical from launch to launch.
+ * bl_ens_rw_stats: the same mixture over S buggy samples' truth entries vals[m * S + s]:  out[0] = F_rw,
+ *   out[1 + m] = dF_rw/dphi_m; partials [1 + M, S].
+ * bl_ensemble_combine_weighted: bl_ensemble_combine's arguments without the kind; out_loc / out_rw as there (DOUBLE), the present
+ *   members folded in member order with numpy's logaddexp; an entry without a probability keeps its value under any beta.  A
+ *   sample no member predicts gets NaN.  At theta = phi = 0, beta = 1 this is BL_ENSEMBLE_AVG up to the rounding of log(M').
+ * S == 0 / B == 0: nothing is launched and nothing written.  No synchronisation.
+ * BL_EINVAL: null pointers, M < 1, negative sizes, a theta / phi that is not finite or outside [-BL_ENS_WEIGHT_BOX,
+ * BL_ENS_WEIGHT_BOX], a beta outside [BL_ENS_BETA_MIN, BL_ENS_BETA_MAX].  BL_ERANGE: M > BL_ENSEMBLE_MAX_MEMBERS, an index space
+ * beyond int32. */
+#define BL_ENS_WEIGHT_BOX 20.0
+#define BL_ENS_BETA_MIN 0.015625
+#define BL_ENS_BETA_MAX 64.0
+int bl_ens_loc_stats(const float* vals, int64_t total, const int32_t* present, const int32_t* seg_off, const int32_t* tgt, int32_t M,
+                     int32_t S, const double* theta, const double* beta, double* partials, double* out, void* stream);
+int bl_ens_rw_stats(const float* vals, const int32_t* present, int32_t M, int32_t S, const double* phi, double* partials, double* out,
+                    void* stream);
+int bl_ensemble_combine_weighted(const float* src, int64_t n_src, const int32_t* loc_idx, const int32_t* loc_off, int64_t total_loc,
+                                 const int32_t* rw_idx, const int32_t* rw_off, int64_t total_rw, int32_t M, int32_t B,
+                                 const double* theta, const double* beta, const double* phi, double* out_loc, double* out_rw,
+                                 void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Self-supervision services (buglab/controllers/bugselectorserver.py:22-28, 120-150 and
  * buglab/controllers/detectordatascoringworker.py:118-130), in csrc/bl_selfsup.hip.  Both read a model's flat fp32 output

@@ -18,6 +18,10 @@ Where this can differ from the reference: the arg-max of a member under `consens
 order (nodes ascending, NO_BUG last), which is the reference's dict order for graph members.  A sequence member's own dict is
 ordered token by token (basemodel.py:320-335), so when EXACT ties between different nodes decide a sequence member's arg-max,
 the reference may pick another of the tied nodes than this port.  The returned location dicts are in the canonical order.
+
+Beyond the reference: a third kind, `weighted`, carries fitted per-member weights and location temperatures
+(`EnsembleWeights`, buglab/models/ensemble/_weights.py has the arithmetic, fit.py the fit) and is combined by
+hip_ops.ensemble_combine_weighted (csrc/bl_ensemble_fit.hip).  With the identity weights it is `avg`.
 """
 from __future__ import annotations
 
@@ -34,6 +38,7 @@ from torch import nn
 from buglab.data.collate import to_device
 from buglab.models import hip_ops
 from buglab.models.basemodel import PredictionLayout, prediction_layout
+from buglab.models.ensemble._weights import EnsembleWeights
 from buglab.runtime.module import ModuleWithMetrics
 from buglab.runtime.neuralmodel import COLLATE_WORKERS, ordered_map
 
@@ -72,7 +77,7 @@ class _EnsembleMinibatch(NamedTuple):
 
 
 class EnsembleWrapper:
-    def __init__(self, models: List[Any], kind: Literal["avg", "consensus"]):
+    def __init__(self, models: List[Any], kind: Literal["avg", "consensus", "weighted"], weights: Optional[EnsembleWeights] = None):
         models = list(models)
         if not models:
             raise ValueError("An ensemble needs at least one member.")
@@ -83,16 +88,35 @@ class EnsembleWrapper:
         if any(isinstance(m, GreatVarMisuse) for m in models):  # its predict yields a VarMisusePrediction per record
             raise ValueError("The GREAT var-misuse model's predict does not yield the location / rewrite log-probabilities an "
                              "ensemble combines.")
-        if kind not in ("avg", "consensus"):
-            raise ValueError(f"Unrecognized ensemble kind `{kind}`: expected `avg` or `consensus`.")
+        if kind not in ("avg", "consensus", "weighted"):
+            raise ValueError(f"Unrecognized ensemble kind `{kind}`: expected `avg`, `consensus` or `weighted`.")
+        if weights is not None and kind != "weighted":
+            raise ValueError(f"Ensemble weights belong to the `weighted` kind, not to `{kind}`.")
         if len(models) > hip_ops.ENSEMBLE_MAX_MEMBERS:
             raise ValueError(f"At most {hip_ops.ENSEMBLE_MAX_MEMBERS} ensemble members are supported (got {len(models)}).")
         self._models = models
         self._kind = kind
+        self._weights: Optional[EnsembleWeights] = None
+        if kind == "weighted":
+            self.ensemble_weights = weights if weights is not None else EnsembleWeights.identity(len(models))
 
     @property
     def kind(self) -> str:
         return self._kind
+
+    @property
+    def ensemble_weights(self) -> Optional[EnsembleWeights]:
+        """The fitted weights of a `weighted` ensemble; None for the other kinds (and for a file written before there were any)."""
+        return getattr(self, "_weights", None)
+
+    @ensemble_weights.setter
+    def ensemble_weights(self, weights: EnsembleWeights) -> None:
+        if self._kind != "weighted":
+            raise ValueError(f"Ensemble weights belong to the `weighted` kind, not to `{self._kind}`.")
+        M = len(self._models)
+        if not all(len(p) == M for p in (weights.theta, weights.beta, weights.phi)):
+            raise ValueError(f"Ensemble weights for {len(weights.theta)} members do not fit an ensemble of {M}.")
+        self._weights = weights
 
     @property
     def models(self) -> List[Any]:
@@ -216,8 +240,12 @@ class EnsembleWrapper:
         M, total_loc, total_rw, B = emb.sizes
         a, c = M * total_loc, M * total_loc + M * total_rw
         ix = emb.index
-        out = hip_ops.ensemble_combine(src.contiguous(), ix[:a].view(M, total_loc), ix[c:c + B + 1], ix[a:c].view(M, total_rw),
-                                       ix[c + B + 1:], self._kind)
+        gather = (src.contiguous(), ix[:a].view(M, total_loc), ix[c:c + B + 1], ix[a:c].view(M, total_rw), ix[c + B + 1:])
+        if self._kind == "weighted":
+            w = self.ensemble_weights
+            out = hip_ops.ensemble_combine_weighted(*gather, w.theta, w.beta, w.phi)
+        else:
+            out = hip_ops.ensemble_combine(*gather, self._kind)
         values = out.cpu().numpy()  # the one device->host copy of the minibatch
         loc_all, rw_all = values[:total_loc].tolist(), values[total_loc:].tolist()
         for b, point in enumerate(emb.originals):
@@ -239,7 +267,11 @@ class EnsembleWrapper:
         if not getattr(self, "_calibration_notice_given", False) and any(
                 getattr(m, "confidence_calibration", None) is not None for m in self._models):
             self._calibration_notice_given = True  # once per wrapper
-            LOGGER.info("Ensemble members carry a confidence calibration; the ensemble combines their uncalibrated values.")
+            if self._kind == "weighted":
+                LOGGER.info("Ensemble members carry a confidence calibration; the ensemble combines their uncalibrated values, and its "
+                            "fitted per-member temperatures take the calibration's place.")
+            else:
+                LOGGER.info("Ensemble members carry a confidence calibration; the ensemble combines their uncalibrated values.")
         with torch.no_grad(), ExitStack() as stack:
             for m in self._models:
                 stack.enter_context(m._tensorize_all_location_rewrites())

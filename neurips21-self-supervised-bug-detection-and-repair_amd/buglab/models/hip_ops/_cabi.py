@@ -187,6 +187,11 @@ _SIGNATURES = {
     "bl_varmisuse_predict": ([POINTER(bl_varmisuse_head_t), c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p], ctypes.c_int),
     "bl_ensemble_combine": ([c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int32, c_int32, c_int32, c_void_p,
                              c_void_p, c_void_p], ctypes.c_int),
+    "bl_ens_loc_stats": ([c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
+                         ctypes.c_int),
+    "bl_ens_rw_stats": ([c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p], ctypes.c_int),
+    "bl_ensemble_combine_weighted": ([c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int32, c_int32, c_void_p,
+                                      c_void_p, c_void_p, c_void_p, c_void_p, c_void_p], ctypes.c_int),
     "bl_score_targets": ([c_void_p, c_int64, c_void_p, c_void_p, c_int32, c_void_p, c_void_p], ctypes.c_int),
     "bl_selector_sample": ([c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int32, c_void_p, c_void_p, c_double,
                             c_double, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p], ctypes.c_int),

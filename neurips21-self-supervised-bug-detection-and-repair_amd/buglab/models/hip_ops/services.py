@@ -8,7 +8,8 @@ import torch
 
 from ._cabi import _check, _f32, _i32, load_library, _p, _req, _stream
 
-__all__ = ["ENSEMBLE_KINDS", "ENSEMBLE_MAX_MEMBERS", "ensemble_combine", "SELECTOR_MAX_K", "_f64", "score_targets",
+__all__ = ["ENSEMBLE_KINDS", "ENSEMBLE_MAX_MEMBERS", "ensemble_combine", "ens_loc_stats", "ens_rw_stats", "ensemble_combine_weighted",
+           "SELECTOR_MAX_K", "_f64", "score_targets",
            "selector_sample", "REPORT_MAX_SAMPLES", "REPORT_INDEX_FIELDS", "report_summarize", "report_order", "EVAL_INDEX_FIELDS", "eval_judge",
            "SUGGEST_MAX_K", "SUGGEST_INDEX_FIELDS", "rank_suggestions",
            "BOOTSTRAP_MAX_MODELS", "BOOTSTRAP_MAX_SCOUTS", "bootstrap_counts", "CURVE_MAX_BINS", "CURVE_COUNTERS", "bootstrap_curve_counts", "conf_loc_stats", "conf_group_stats", "conf_apply", "DEDUP_MAX_PERM",
@@ -37,6 +38,73 @@ def ensemble_combine(src, loc_idx, loc_off, rw_idx, rw_off, kind: str) -> torch.
                                               rw_idx.data_ptr(), rw_off.data_ptr(), total_rw, M, loc_off.shape[0] - 1,
                                               ENSEMBLE_KINDS[kind], out.data_ptr(), out.data_ptr() + 8 * total_loc, _stream()),
            "bl_ensemble_combine")
+    return out
+
+
+# ------------------------------------------------------------------------------------------------
+# fitted ensembles (csrc/bl_ensemble_fit.hip; include/buglab_hip.h::bl_ens_loc_stats, bl_ens_rw_stats,
+# bl_ensemble_combine_weighted).  The parameters travel as M host doubles each: the launcher reads them before the launch.
+def _member_params(values, M: int, name: str):
+    import ctypes
+
+    values = [float(v) for v in values]
+    if len(values) != M:
+        raise ValueError(f"{name}: {len(values)} values for {M} ensemble members")
+    return (ctypes.c_double * M)(*values)
+
+
+def ens_loc_stats(vals, present, seg_off, tgt, theta, beta) -> torch.Tensor:
+    """The weighted ensemble's location loss over a pool of S segments and its gradient, float64 [1 + 2M] = F | dF/dtheta [M] |
+    dF/dbeta [M].  vals float32 [M, total]: every member's log-probabilities in the canonical layout, segment s =
+    vals[m, seg_off[s] : seg_off[s + 1]], NO_BUG last; present int32 [M, S]; seg_off int32 [S + 1]; tgt int32 [S]: the target's
+    place within its segment; theta, beta: M floats each.  Exactly buglab/models/ensemble/_weights.py::loc_stats.  No sync."""
+    _f32(vals, "vals"), _i32(present, "present"), _i32(seg_off, "seg_off"), _i32(tgt, "tgt")
+    S = tgt.shape[0]
+    if vals.dim() != 2 or present.dim() != 2 or tgt.dim() != 1 or tuple(present.shape) != (vals.shape[0], S) or seg_off.dim() != 1 \
+            or seg_off.shape[0] != S + 1:
+        raise ValueError(f"ens_loc_stats: vals {tuple(vals.shape)} must be [M, total], present {tuple(present.shape)} [M, S], tgt "
+                         f"{tuple(tgt.shape)} [S] and seg_off {tuple(seg_off.shape)} [S + 1]")
+    M, total = vals.shape
+    cols = 1 + 2 * M
+    work = (torch.empty if S else torch.zeros)(cols * (S + 1), dtype=torch.float64, device=vals.device)  # [the result | partials]
+    _check(load_library().bl_ens_loc_stats(vals.data_ptr(), total, present.data_ptr(), seg_off.data_ptr(), tgt.data_ptr(), M, S,
+                                           _member_params(theta, M, "theta"), _member_params(beta, M, "beta"),
+                                           work.data_ptr() + 8 * cols, work.data_ptr(), _stream()), "bl_ens_loc_stats")
+    return work[:cols]
+
+
+def ens_rw_stats(vals, present, phi) -> torch.Tensor:
+    """The weighted ensemble's rewrite loss over S buggy samples and its gradient, float64 [1 + M] = F | dF/dphi [M].  vals float32
+    [M, S]: every member's log-probability of the sample's true rewrite; present int32 [M, S]; phi: M floats.  Exactly
+    buglab/models/ensemble/_weights.py::rw_stats.  No sync."""
+    _f32(vals, "vals"), _i32(present, "present")
+    if vals.dim() != 2 or vals.shape != present.shape:
+        raise ValueError(f"ens_rw_stats: vals {tuple(vals.shape)} and present {tuple(present.shape)} must both be [M, S]")
+    M, S = vals.shape
+    cols = 1 + M
+    work = (torch.empty if S else torch.zeros)(cols * (S + 1), dtype=torch.float64, device=vals.device)
+    _check(load_library().bl_ens_rw_stats(vals.data_ptr(), present.data_ptr(), M, S, _member_params(phi, M, "phi"),
+                                          work.data_ptr() + 8 * cols, work.data_ptr(), _stream()), "bl_ens_rw_stats")
+    return work[:cols]
+
+
+def ensemble_combine_weighted(src, loc_idx, loc_off, rw_idx, rw_off, theta, beta, phi) -> torch.Tensor:
+    """`ensemble_combine` for the `weighted` kind: the same arguments without the kind, and the members' location weights theta,
+    inverse temperatures beta and rewrite weights phi (M floats each) -> float64 [total_loc + total_rw].  Exactly
+    buglab/models/ensemble/_weights.py::combine_weighted.  No sync."""
+    _f32(src, "src")
+    _i32(loc_idx, "loc_idx"), _i32(rw_idx, "rw_idx"), _i32(loc_off, "loc_off"), _i32(rw_off, "rw_off")
+    if loc_idx.dim() != 2 or rw_idx.dim() != 2 or rw_idx.shape[0] != loc_idx.shape[0] or loc_off.dim() != 1 or loc_off.shape[0] < 1 \
+            or loc_off.shape != rw_off.shape:
+        raise ValueError(f"ensemble_combine_weighted: loc_idx {tuple(loc_idx.shape)} must be [M, total_loc], rw_idx {tuple(rw_idx.shape)} "
+                         f"[M, total_rw], loc_off {tuple(loc_off.shape)} and rw_off {tuple(rw_off.shape)} both [B + 1]")
+    M, total_loc = loc_idx.shape
+    total_rw = rw_idx.shape[1]
+    out = torch.empty(total_loc + total_rw, dtype=torch.float64, device=src.device)
+    _check(load_library().bl_ensemble_combine_weighted(
+        src.data_ptr(), src.numel(), loc_idx.data_ptr(), loc_off.data_ptr(), total_loc, rw_idx.data_ptr(), rw_off.data_ptr(), total_rw,
+        M, loc_off.shape[0] - 1, _member_params(theta, M, "theta"), _member_params(beta, M, "beta"), _member_params(phi, M, "phi"),
+        out.data_ptr(), out.data_ptr() + 8 * total_loc, _stream()), "bl_ensemble_combine_weighted")
     return out
 
 
