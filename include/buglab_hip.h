@@ -912,6 +912,41 @@ int bl_rank_suggestions(const float* src, int64_t n_src, const int32_t* rw_idx, 
                         int64_t capacity, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Explanations: node attributions of a predicted fix (buglab/models/explain.py), in csrc/bl_explain.hip.  BEYOND THE REFERENCE:
+ * it has no counterpart -- its visualize.py shows what was flagged, nothing says why.  The backward pass (existing kernels)
+ * gives G [N, D], the gradient of the explained log-probability with respect to the node embedder's output x [N, D]; these two
+ * reduce it.  fp64, fixed trees, no atomics, compiled without fused multiply-adds, bit-identical from run to run and equal bit
+ * for bit to buglab/models/_explain.py::node_scores_host / topk_host.  No synchronisation, no allocation.
+ *
+ * bl_attr_node_scores: score[n] = t or score[n] + t (accumulate != 0: the steps of an integrated-gradients path), with
+ *   t = w * dot_n (one rounded product, then one rounded addition) and dot_n = sum_d x[n, d] * g[n, d].  x, g: fp32, row strides
+ *   ldx, ldg in ELEMENTS (>= D); score: double [N].  One wave per node.  COLUMN OWNERSHIP: columns go in quads, quad q = columns
+ *   4q .. 4q + 3 (the last one may be partial); lane l owns the quads with q % 64 == l and adds the products of its columns, each
+ *   exact in fp64 (24 + 24 significand bits), to its own fp64 sum (initially +0.0) in ascending column order.  The 64 lane sums
+ *   are then added by the xor butterfly, strides 32 .. 1, and lane 0's value is dot_n.  The ownership is the same for every D,
+ *   stride and alignment: with x, g 16-byte aligned and both strides multiples of 4 a quad is one 16-byte load per operand,
+ *   otherwise the same columns are loaded one by one.  Any D >= 1; N == 0 is a no-op.  Bandwidth bound: 2 N D 4 bytes.
+ *   BL_EINVAL: D < 1, N < 0, a stride below D, null pointers.  BL_ERANGE: N beyond int32.
+ *
+ * bl_attr_topk: one workgroup per graph b of B over the nodes [node_off[b], node_off[b + 1]) of score (int32 offsets, clamped
+ *   to [0, N]); results go to row offset + b of buffers the caller keeps for the whole run (capacity graphs):
+ *   out_sums  [2, capacity] double   sum a | sum |a| over the graph's nodes: thread t of 256 adds nodes t, t + 256, .. in that
+ *                                    order, then the xor butterfly in each wave and the four waves' sums in wave order.  A NaN
+ *                                    score makes both NaN.
+ *   out_node  [capacity, k] int32    the first min(k, #non-NaN) nodes, as indices WITHIN the graph, in the order "greater key
+ *                                    first, the lower index among equals", key = |a| (by_abs != 0) or a; then -1.  k rounds, each
+ *                                    the first maximum among the nodes strictly after the previous pick in that order (nothing is
+ *                                    marked).  A node whose score is NaN is never listed.
+ *   out_score [capacity, k] double   a of the listed nodes (signed, whatever the key); then 0.0.
+ *   Nothing outside rows offset .. offset + B - 1 is written.  BL_EINVAL: k < 1, negative sizes, null pointers, offset + B >
+ *   capacity.  BL_ERANGE: k > BL_EXPLAIN_MAX_K, N beyond int32. */
+#define BL_EXPLAIN_MAX_K 32
+int bl_attr_node_scores(const float* x, int64_t ldx, const float* g, int64_t ldg, int64_t N, int32_t D, double w, int32_t accumulate,
+                        double* score, void* stream);
+int bl_attr_topk(const double* score, const int32_t* node_off, int32_t B, int64_t N, int32_t k, int32_t by_abs, int32_t* out_node,
+                 double* out_score, double* out_sums, int64_t offset, int64_t capacity, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Paired bootstrap of the evaluation counts (buglab/models/compare.py), in csrc/bl_bootstrap.hip.  BEYOND THE REFERENCE: it
  * has no counterpart -- its evaluate.py prints point estimates only.  What is resampled are the counts of
  * buglab/models/evaluate.py:139-173 (the numerators and denominators of every metric and of the per-scout tables): each

@@ -11,7 +11,7 @@ from ._cabi import _check, _f32, _i32, load_library, _p, _req, _stream
 __all__ = ["ENSEMBLE_KINDS", "ENSEMBLE_MAX_MEMBERS", "ensemble_combine", "ens_loc_stats", "ens_rw_stats", "ensemble_combine_weighted",
            "SELECTOR_MAX_K", "_f64", "score_targets",
            "selector_sample", "REPORT_MAX_SAMPLES", "REPORT_INDEX_FIELDS", "report_summarize", "report_order", "EVAL_INDEX_FIELDS", "eval_judge",
-           "SUGGEST_MAX_K", "SUGGEST_INDEX_FIELDS", "rank_suggestions",
+           "SUGGEST_MAX_K", "SUGGEST_INDEX_FIELDS", "rank_suggestions", "EXPLAIN_MAX_K", "attribute_node_scores", "attribute_topk",
            "BOOTSTRAP_MAX_MODELS", "BOOTSTRAP_MAX_SCOUTS", "bootstrap_counts", "CURVE_MAX_BINS", "CURVE_COUNTERS", "bootstrap_curve_counts", "conf_loc_stats", "conf_group_stats", "conf_apply", "DEDUP_MAX_PERM",
            "DEDUP_EMPTY_SLOT", "_i64", "dedup_sha1_u32", "dedup_minhash", "dedup_lsh_insert_query"]
 
@@ -268,6 +268,65 @@ def rank_suggestions(src, ix, out_rank, out_entry, out_logprob, offset: int, *, 
                                               p("nobug_idx"), p("tgt_rw"), p("loc_idx"), p("loc_off"), p("key_node"), total_loc,
                                               p("rw_node"), B, k, int(bool(skip_nobug)), out_entry.data_ptr(), out_logprob.data_ptr(),
                                               out_rank.data_ptr(), offset, N, _stream()), "bl_rank_suggestions")
+
+
+# ------------------------------------------------------------------------------------------------
+# explanations (csrc/bl_explain.hip; include/buglab_hip.h::bl_attr_node_scores, bl_attr_topk)
+EXPLAIN_MAX_K = 32  # BL_EXPLAIN_MAX_K
+
+
+def _rows_f32(t, name: str, what: str):
+    """an fp32 [N, D] operand whose rows are contiguous and at least D apart (a view with a larger row stride, or an unaligned
+    base, is taken as it is)"""
+    if not t.is_cuda:
+        raise ValueError(f"{what}: {name} is on {t.device}; the kernel only runs on a ROCm GPU")
+    if t.dtype != torch.float32 or t.dim() != 2 or t.shape[1] < 1 or (t.shape[0] > 1 and t.stride(0) < t.shape[1]) \
+            or (t.shape[1] > 1 and t.stride(1) != 1):
+        raise ValueError(f"{what}: {name} must be float32 [N, D >= 1] with contiguous rows (got {t.dtype} {tuple(t.shape)}, "
+                         f"strides {tuple(t.stride())})")
+    return t
+
+
+def attribute_node_scores(x, g, score, *, weight: float = 1.0, accumulate: bool = False) -> None:
+    """score[n] = weight * sum_d x[n, d] * g[n, d] in fp64, or that added to score[n] with `accumulate` (the steps of an
+    integrated-gradients path).  x, g float32 [N, D] (row strides above D and unaligned bases are fine), score float64 [N].
+    Exactly buglab/models/_explain.py::node_scores_host.  No sync."""
+    what = "attribute_node_scores"
+    _rows_f32(x, "x", what), _rows_f32(g, "g", what)
+    if x.shape != g.shape or score.dtype != torch.float64 or tuple(score.shape) != (x.shape[0],) or not score.is_contiguous() \
+            or score.device != x.device or g.device != x.device:
+        raise ValueError(f"{what}: inconsistent shapes (x {tuple(x.shape)}, g {tuple(g.shape)}, score {score.dtype} {tuple(score.shape)} "
+                         f"must be float64 [N], all on {x.device})")
+    N, D = x.shape
+    ld = lambda t: t.stride(0) if N > 1 else max(t.stride(0), D)
+    _check(load_library().bl_attr_node_scores(x.data_ptr(), ld(x), g.data_ptr(), ld(g), N, D, float(weight), int(bool(accumulate)),
+                                              score.data_ptr(), _stream()), "bl_attr_node_scores")
+
+
+def attribute_topk(score, node_off, out_node, out_score, out_sums, offset: int, *, k: int, by_abs: bool = True) -> None:
+    """Per graph of one minibatch of B graphs: its k first nodes by |score| (by score when not `by_abs`), the lower index first
+    among equals, NaNs never listed, and the sums of score and |score| over its nodes, written to graphs offset .. offset + B - 1
+    of the run-long buffers out_node (int32 [C, k]: indices within the graph, -1 padded), out_score (float64 [C, k], 0.0 padded)
+    and out_sums (float64 [2, C]).  score float64 [N]; node_off int32 [B + 1].  Exactly buglab/models/_explain.py::topk_host.
+    No sync."""
+    _f64(score, "score"), _i32(node_off, "node_off"), _i32(out_node, "out_node"), _f64(out_score, "out_score"), _f64(out_sums, "out_sums")
+    k = int(k)
+    if score.dim() != 1 or node_off.dim() != 1 or node_off.shape[0] < 1:
+        raise ValueError(f"attribute_topk: inconsistent shapes (score {tuple(score.shape)} must be [N], node_off {tuple(node_off.shape)} "
+                         "[B + 1])")
+    if not 1 <= k <= EXPLAIN_MAX_K:
+        raise ValueError(f"attribute_topk: k must be in [1, {EXPLAIN_MAX_K}] (got {k})")
+    B, N = node_off.shape[0] - 1, score.shape[0]
+    C = out_sums.shape[1] if out_sums.dim() == 2 else -1
+    if tuple(out_sums.shape) != (2, C) or tuple(out_node.shape) != (C, k) or tuple(out_score.shape) != (C, k) \
+            or any(t.device != score.device for t in (node_off, out_node, out_score, out_sums)):
+        raise ValueError(f"attribute_topk: inconsistent shapes (out_sums {tuple(out_sums.shape)} must be [2, C], out_node "
+                         f"{tuple(out_node.shape)} and out_score {tuple(out_score.shape)} [C, {k}], all on {score.device})")
+    offset = int(offset)
+    if not 0 <= offset <= C - B:
+        raise ValueError(f"attribute_topk: graphs {offset} .. {offset + B} do not fit the result buffers of {C} graphs")
+    _check(load_library().bl_attr_topk(score.data_ptr(), node_off.data_ptr(), B, N, k, int(bool(by_abs)), out_node.data_ptr(),
+                                       out_score.data_ptr(), out_sums.data_ptr(), offset, C, _stream()), "bl_attr_topk")
 
 
 # ------------------------------------------------------------------------------------------------

@@ -208,7 +208,9 @@ class GraphNeuralNetwork(nn.Module):
     def forward(self, *, token_ids, token_lens, msg_src, msg_tgt, type_ptr, tgt_ptr, tgt_msgs, src_ptr, src_msgs,
                 node_to_graph, reference_node_ids, reference_node_graph_idx, num_graphs, num_nodes, num_messages,
                 return_all_states: bool = False, dropout_seed: Optional[int] = None, tok_occ=None, tok_chunk_ptr=None,
-                tok_chunk_id=None, node_order=None, num_hub_nodes: int = -1, msg_feat=None, **_unused) -> GnnOutput:
+                tok_chunk_id=None, node_order=None, num_hub_nodes: int = -1, msg_feat=None, input_transform=None, **_unused) -> GnnOutput:
+        """input_transform: applied to the embedder's output before the first layer (buglab/models/explain.py scales and
+        re-leafs it there); None, as every other caller leaves it, changes nothing."""
         graph = GraphIndex(msg_src, msg_tgt, type_ptr, tgt_ptr, tgt_msgs, src_ptr, src_msgs, int(num_nodes),
                            int(num_messages), int(type_ptr.shape[0]) - 1, node_order, int(num_hub_nodes))
         training = self.training and dropout_seed is not None
@@ -216,6 +218,8 @@ class GraphNeuralNetwork(nn.Module):
         mk = lambda rate, stream: Dropout(rate if training else 0.0, seed, stream)
         tok_csr = (tok_occ, tok_chunk_ptr, tok_chunk_id) if tok_occ is not None else None
         h0 = self.embed(token_ids, token_lens, mk(self.embed.dropout_rate, 0), tok_csr)
+        if input_transform is not None:
+            h0 = input_transform(h0)
         edge_features = None
         if self.edge_embed is not None:
             if msg_feat is None:

@@ -14,6 +14,7 @@ Options:
     --show-only-top-k=<num>    Show only the top-k. If k is zero, then show all. [default: 0]
     --min-confidence=<p>       Show only warnings (a location is predicted) whose probability is at least p.
     --at-operating-point       The same, at the checkpoint's warning operating point (buglab/models/operatingpoint.py).
+    --explain=<K>              Under each shown snippet, the K graph nodes its first suggestion rests on most (explain.py; graph models).
     --report-json=<path>       Also write the report as data (the contexts the page is rendered from).
     --restore-path=<path>      Accepted for command-line compatibility (unused by the reference's run()).
     --quiet                    Accepted for command-line compatibility.
@@ -286,10 +287,12 @@ def predictions_to_report(predictions: Iterable[Tuple[Any, Dict[int, float], Lis
 
 def scan(model, nn, data: Iterable[Any], device, *, parallelize: bool = False, only_incorrect: bool = False,
          order_by_confidence: bool = False, show_top_k: int = 0, min_confidence: Optional[float] = None,
-         at_operating_point: bool = False) -> Report:
+         at_operating_point: bool = False, explain: int = 0) -> Report:
     """Run `model` over `data` (datapoints) and report: which samples are shown, in which order, and their contexts.  The
     samples the model's `tensorize` rejects are skipped, as `predict` skips them.  `min_confidence` (a probability) and
-    `at_operating_point` (the model's `warning_operating_point`) keep only the warnings at or above that confidence."""
+    `at_operating_point` (the model's `warning_operating_point`) keep only the warnings at or above that confidence.
+    `explain` = K > 0: a second pass over the shown samples only (buglab/models/explain.py, graph models) gives each shown
+    snippet's context an "influences" list: the K nodes the model's log-probability of its first suggestion rests on most."""
     import torch
 
     from buglab.controllers import _batching as Bt
@@ -334,8 +337,22 @@ def scan(model, nn, data: Iterable[Any], device, *, parallelize: bool = False, o
         keep = ((keep != 0) & (sample_i[1] == 0) & (confidence >= min_logprob)).to(torch.int32)
     order = hip_ops.report_order(sample_d[0], keep, by_confidence=order_by_confidence, k=int(show_top_k)).cpu().numpy()
     sample_i, sample_d = sample_i.cpu().numpy(), sample_d.cpu().numpy()  # the verdicts: 3 int32 and 2 doubles per sample
-    return Report(_build_snippets(chunks, starts, order, sample_i, sample_d), order, sample_i[2] != 0, sample_d[0].copy(),
-                  sample_i[1] == 0, confidence.cpu().numpy())
+    snippets = _build_snippets(chunks, starts, order, sample_i, sample_d)
+    if explain:
+        _add_influences(model, nn, chunks, starts, order, snippets, device, int(explain))
+    return Report(snippets, order, sample_i[2] != 0, sample_d[0].copy(), sample_i[1] == 0, confidence.cpu().numpy())
+
+
+def _add_influences(model, nn, chunks: List[_Chunk], starts: List[int], order: np.ndarray, snippets: List[Dict[str, Any]], device, k: int) -> None:
+    """`--explain K`: the shown samples, and only they, go through buglab/models/explain.py once more (gradient x input of the
+    first suggestion); each context gets "influences": [{"label", "kind", "share"}]."""
+    from buglab.models.explain import explain
+
+    where = np.searchsorted(np.asarray(starts[1:], dtype=np.int64), order, side="right")
+    shown = [chunks[c].datapoints[o - starts[c]] for o, c in zip(order.tolist(), where.tolist())]
+    found = {x.position: x for x in explain(model, nn, shown, device, k, parallelize=False)}
+    for position, ctx in enumerate(snippets):
+        ctx["influences"] = found[position].influences() if position in found else []
 
 
 # ------------------------------------------------------------------------------------------------
@@ -396,6 +413,10 @@ def _snippet_html(index: int, ctx: Dict[str, Any]) -> str:
         note.append("</li>")
         notes.append("".join(note))
     out.append("".join(code) + "</pre>")
+    if "influences" in ctx:  # (--explain only)
+        out.append('<p class="influences">influenced by: '
+                   + ", ".join(f'<span class="influence {e(str(i["kind"]))}">{e(str(i["label"]))} ({i["share"]:.0%})</span>' for i in ctx["influences"])
+                   + "</p>")
     out.append('<ol class="annotations">' + "".join(notes) + "</ol>")
     out.append("</section>")
     return "\n".join(out)
@@ -451,6 +472,9 @@ def parse_args(argv=None) -> argparse.Namespace:
     p.add_argument("--show-only-top-k", type=int, default=0)
     p.add_argument("--min-confidence", type=float, default=None)
     p.add_argument("--at-operating-point", action="store_true")
+    p.add_argument("--explain", type=int, default=0, metavar="K",
+                   help="Under each shown snippet, the K graph nodes its first suggestion rests on most (graph models; a second pass "
+                        "over the shown samples only).")
     p.add_argument("--report-json", default=None)
     p.add_argument("--restore-path", default=None)
     p.add_argument("--quiet", action="store_true")
@@ -479,7 +503,7 @@ def run(args: argparse.Namespace) -> Report:
     model, nn = AbstractNeuralModel.restore_model(Path(args.MODEL_FILENAME), device)
     report = scan(model, nn, data, device, parallelize=not args.sequential, only_incorrect=args.only_incorrect,
                   order_by_confidence=args.order_by_confidence, show_top_k=args.show_only_top_k, min_confidence=args.min_confidence,
-                  at_operating_point=args.at_operating_point)
+                  at_operating_point=args.at_operating_point, explain=args.explain)
     with open(args.OUT_HTML, "w", encoding="utf-8") as f:
         f.write(report_to_html(report.snippets))
     if args.report_json is not None:
