@@ -1014,6 +1014,52 @@ int bl_bootstrap_curve_counts(const uint32_t* packed, const int16_t* bins /* [M,
                               uint64_t seed, int64_t r0, int64_t R, int32_t* out /* [R, 1 + M * 5 * G] */, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * False-discovery-controlled warnings (buglab/models/fdr.py), in csrc/bl_fdr.hip.  BEYOND THE REFERENCE: it has no counterpart.
+ * Conformal p-values against a reference set of clean samples, then the Benjamini-Hochberg (BH) step-up over a scan: if the
+ * reference is exchangeable with the clean part of the scan, the expected share of false alarms among the flagged samples is
+ * at most q, whatever the share of buggy samples.  buglab/models/_fdr.py is the same arithmetic in NumPy, equal bit for bit on
+ * every output.  Definitions:
+ *   SCORE of sample b   s = src[nobug_idx[b]]: the fp32 NO_BUG location log-probability of the model's flat output (calibrated
+ *                       where the checkpoint carries a calibration).  Lower is more suspicious.  An index outside [0, n_src)
+ *                       reads as NaN.
+ *   REFERENCE           ref[0 .. n): the scores of n >= 1 clean samples, fp32, sorted ascending, no NaN (the host drops and
+ *                       counts them at fit time), n <= BL_FDR_MAX_REFERENCE.
+ *   COUNT               c = #{ j : ref[j] <= s }, fp32 compares as IEEE makes them (-0.0 == 0.0); c = n for a NaN s.
+ *   P-VALUE             p = (c + 1) / (n + 1), formed on the host; no decision uses the float.
+ *   BH over N samples at level q:  R[c] = the number of samples with count <= c;
+ *                       c* = max{ c in [0, n] : R[c] > 0 and (double)((int64)(c + 1) * N) <= q * (double)((int64)(n + 1) * R[c]) },
+ *                       an exact integer on the left, ONE rounded fp64 product on the right (both integers are below 2^53);
+ *                       c* = -1 if there is no such c.  A sample is FLAGGED iff c <= c*.  (The textbook step-up: the largest k
+ *                       with p_(k) <= q k / N.)
+ *   Q-VALUE             qv(c) = min over c' >= c with R[c'] > 0 of min(1, (double)((int64)(c' + 1) * N) / (double)((int64)(n + 1) * R[c'])),
+ *                       each term ONE correctly rounded fp64 quotient; an fp64 minimum is exact, so any order gives the same bits.
+ * Benjamini-Yekutieli (arbitrary dependence) divides q by sum_{i <= N} 1 / i on the host; the kernels know nothing of it.
+ *
+ * bl_fdr_counts: one launch per predict minibatch of B samples, no synchronisation; one thread per sample, a binary search for
+ *   the upper bound in ref.  Writes out_score[offset + b] = s (the NaN's bits as loaded; 0x7FC00000 for an index outside src)
+ *   and out_count[offset + b] = c into buffers the caller keeps for the whole run (capacity samples); nothing else is written.
+ *   The same entry serves a bulk call over N scores with nobug_idx the identity.
+ *   BL_EINVAL: null pointers, negative sizes, n_ref < 1, offset + B > capacity.  BL_ERANGE: n_ref > BL_FDR_MAX_REFERENCE, n_src
+ *   beyond int32.
+ *
+ * bl_fdr_bh: count [N] int32 (a value outside [0, n_ref] is clamped into it) -> out_cutoff int32 [2] = { c*, R[c*] or 0 },
+ *   out_flag int32 [N] (1 = flagged), out_q double [N] = qv(count).  workspace: bl_fdr_bh_workspace_bytes(n_ref) bytes, 8-byte
+ *   aligned, may hold anything on entry; on return its first n_ref + 1 int32 hold R.  Several launches on `stream`, no
+ *   synchronisation, no allocation: the histogram of the counts is zeroed and filled (integer adds, the only atomics: to an LDS
+ *   table of the workgroup where n_ref + 1 <= 16000, to global memory beyond; the top bin c = n_ref is counted in registers and
+ *   added once per workgroup), an inclusive prefix sum in chunks of 4096 bins gives R, every bin's term and the chunk's greatest
+ *   qualifying c are formed in the same pass, a suffix minimum over the terms gives qv, and one pass over the samples writes
+ *   out_flag and out_q.  The same bytes on every call.
+ *   BL_EINVAL: null pointers, a workspace that is not 8-byte aligned, N < 1, n_ref < 1, q outside (0, 1] (NaN included).
+ *   BL_ERANGE: n_ref > BL_FDR_MAX_REFERENCE, N beyond int32.  bl_fdr_bh_workspace_bytes returns 0 for an n_ref out of range. */
+#define BL_FDR_MAX_REFERENCE (1 << 20)
+int bl_fdr_counts(const float* src, int64_t n_src, const int32_t* nobug_idx, int32_t B, const float* ref, int64_t n_ref,
+                  float* out_score, int32_t* out_count, int64_t offset, int64_t capacity, void* stream);
+int64_t bl_fdr_bh_workspace_bytes(int64_t n_ref);
+int bl_fdr_bh(const int32_t* count, int64_t N, int64_t n_ref, double q, void* workspace, int32_t* out_cutoff, int32_t* out_flag,
+              double* out_q, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Confidence calibration (buglab/models/calibrate.py), in csrc/bl_confidence.hip.  BEYOND THE REFERENCE: it has no
  * counterpart; what is calibrated is the confidence its evaluate.py:60-140 thresholds and its visualize.py ranks by.  One
  * inverse temperature beta and a NO_BUG bias rescale the localization distribution, one repair_beta the repair groups:

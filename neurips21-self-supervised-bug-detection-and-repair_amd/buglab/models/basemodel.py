@@ -72,6 +72,17 @@ class AbstractBugLabModel:
     def warning_operating_point(self, value) -> None:
         self._warning_operating_point = value
 
+    @property
+    def null_reference(self):
+        """The `NullReference` fitted by `python -m buglab.models.fdr fit` (beyond the reference), or None: the sorted NO_BUG
+        scores of clean samples that `fdr scan` ranks a scanned sample in.  Pickled with the model; a checkpoint written
+        before the field existed has none, and nothing but buglab/models/fdr.py reads it."""
+        return getattr(self, "_null_reference", None)
+
+    @null_reference.setter
+    def null_reference(self, value) -> None:
+        self._null_reference = value
+
     def _compute_rewrite_data(self, datapoint, candidate_node_idxs: Sequence[int]):
         """Same 16-tuple as reference basemodel.py:80-238.
 

@@ -204,6 +204,9 @@ _SIGNATURES = {
     "bl_rank_suggestions": ([c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                              c_int64, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p],
                             ctypes.c_int),
+    "bl_fdr_counts": ([c_void_p, c_int64, c_void_p, c_int32, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_void_p], ctypes.c_int),
+    "bl_fdr_bh_workspace_bytes": ([c_int64], c_int64),
+    "bl_fdr_bh": ([c_void_p, c_int64, c_int64, c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p], ctypes.c_int),
     "bl_attr_node_scores": ([c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int32, c_double, c_int32, c_void_p, c_void_p], ctypes.c_int),
     "bl_attr_topk": ([c_void_p, c_void_p, c_int32, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p],
                      ctypes.c_int),

@@ -11,7 +11,7 @@ from ._cabi import _check, _f32, _i32, load_library, _p, _req, _stream
 __all__ = ["ENSEMBLE_KINDS", "ENSEMBLE_MAX_MEMBERS", "ensemble_combine", "ens_loc_stats", "ens_rw_stats", "ensemble_combine_weighted",
            "SELECTOR_MAX_K", "_f64", "score_targets",
            "selector_sample", "REPORT_MAX_SAMPLES", "REPORT_INDEX_FIELDS", "report_summarize", "report_order", "EVAL_INDEX_FIELDS", "eval_judge",
-           "SUGGEST_MAX_K", "SUGGEST_INDEX_FIELDS", "rank_suggestions", "EXPLAIN_MAX_K", "attribute_node_scores", "attribute_topk",
+           "SUGGEST_MAX_K", "SUGGEST_INDEX_FIELDS", "rank_suggestions", "FDR_MAX_REFERENCE", "fdr_counts", "fdr_bh", "fdr_bh_workspace_bytes", "EXPLAIN_MAX_K", "attribute_node_scores", "attribute_topk",
            "BOOTSTRAP_MAX_MODELS", "BOOTSTRAP_MAX_SCOUTS", "bootstrap_counts", "CURVE_MAX_BINS", "CURVE_COUNTERS", "bootstrap_curve_counts", "conf_loc_stats", "conf_group_stats", "conf_apply", "DEDUP_MAX_PERM",
            "DEDUP_EMPTY_SLOT", "_i64", "dedup_sha1_u32", "dedup_minhash", "dedup_lsh_insert_query"]
 
@@ -268,6 +268,66 @@ def rank_suggestions(src, ix, out_rank, out_entry, out_logprob, offset: int, *, 
                                               p("nobug_idx"), p("tgt_rw"), p("loc_idx"), p("loc_off"), p("key_node"), total_loc,
                                               p("rw_node"), B, k, int(bool(skip_nobug)), out_entry.data_ptr(), out_logprob.data_ptr(),
                                               out_rank.data_ptr(), offset, N, _stream()), "bl_rank_suggestions")
+
+
+# ------------------------------------------------------------------------------------------------
+# false-discovery-controlled warnings (csrc/bl_fdr.hip; include/buglab_hip.h::bl_fdr_counts, bl_fdr_bh)
+FDR_MAX_REFERENCE = 1 << 20  # BL_FDR_MAX_REFERENCE
+
+
+def fdr_counts(src, nobug_idx, ref, out_score, out_count, offset: int) -> None:
+    """The scores src[nobug_idx[b]] of one predict minibatch of B samples and their counts against the sorted reference `ref`
+    (c = #{j : ref[j] <= s}, len(ref) for a NaN score), written to samples offset .. offset + B - 1 of the run-long buffers
+    out_score (float32 [N]) and out_count (int32 [N]).  src float32 [n_src], nobug_idx int32 [B] (outside src: NaN), ref float32
+    [n_ref] ascending without NaN.  Exactly buglab/models/_fdr.py::counts_host.  No sync."""
+    _f32(src, "src"), _i32(nobug_idx, "nobug_idx"), _f32(ref, "ref"), _f32(out_score, "out_score"), _i32(out_count, "out_count")
+    if src.dim() != 1 or nobug_idx.dim() != 1 or ref.dim() != 1:
+        raise ValueError(f"fdr_counts: src {tuple(src.shape)}, nobug_idx {tuple(nobug_idx.shape)} and ref {tuple(ref.shape)} must be "
+                         "one-dimensional")
+    if not 1 <= ref.shape[0] <= FDR_MAX_REFERENCE:
+        raise ValueError(f"fdr_counts: the reference must hold between 1 and {FDR_MAX_REFERENCE} scores (got {ref.shape[0]})")
+    B, N = nobug_idx.shape[0], out_score.shape[0]
+    if out_score.dim() != 1 or tuple(out_count.shape) != (N,) or any(t.device != src.device for t in (nobug_idx, ref, out_score, out_count)):
+        raise ValueError(f"fdr_counts: out_score {tuple(out_score.shape)} and out_count {tuple(out_count.shape)} must both be [N], and "
+                         f"every tensor on {src.device}")
+    offset = int(offset)
+    if not 0 <= offset <= N - B:
+        raise ValueError(f"fdr_counts: samples {offset} .. {offset + B} do not fit the result buffers of {N} samples")
+    _check(load_library().bl_fdr_counts(src.data_ptr(), src.numel(), nobug_idx.data_ptr(), B, ref.data_ptr(), ref.shape[0],
+                                        out_score.data_ptr(), out_count.data_ptr(), offset, N, _stream()), "bl_fdr_counts")
+
+
+def fdr_bh(count, n_ref: int, q: float, workspace: Optional[torch.Tensor] = None
+           ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Benjamini-Hochberg at level q over the counts of N scanned samples against a reference of n_ref scores -> (cutoff int32
+    [2] = c* | R[c*] or 0, flag int32 [N], q_value float64 [N], R int32 [n_ref + 1]: a view of the workspace).  count int32 [N],
+    values clamped into [0, n_ref].  `workspace`: a uint8 tensor of at least `fdr_bh_workspace_bytes(n_ref)` bytes to reuse (its
+    contents do not matter); allocated when None.  Exactly buglab/models/_fdr.py::bh_host.  No sync."""
+    _i32(count, "count")
+    n_ref, q = int(n_ref), float(q)
+    if count.dim() != 1 or count.shape[0] < 1:
+        raise ValueError(f"fdr_bh: count {tuple(count.shape)} must be [N] with N >= 1")
+    if not 1 <= n_ref <= FDR_MAX_REFERENCE:
+        raise ValueError(f"fdr_bh: n_ref must be in [1, {FDR_MAX_REFERENCE}] (got {n_ref})")
+    if not 0.0 < q <= 1.0:
+        raise ValueError(f"fdr_bh: the level q must be in (0, 1] (got {q})")
+    need = fdr_bh_workspace_bytes(n_ref)
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.uint8, device=count.device)
+    elif _req(workspace, torch.uint8, "workspace").dim() != 1 or workspace.shape[0] < need or workspace.device != count.device:
+        raise ValueError(f"fdr_bh: workspace {tuple(workspace.shape)} must be uint8 [>= {need}] on {count.device}")
+    N = count.shape[0]
+    cutoff = torch.empty(2, dtype=torch.int32, device=count.device)
+    flag = torch.empty(N, dtype=torch.int32, device=count.device)
+    q_value = torch.empty(N, dtype=torch.float64, device=count.device)
+    _check(load_library().bl_fdr_bh(count.data_ptr(), N, n_ref, q, workspace.data_ptr(), cutoff.data_ptr(), flag.data_ptr(),
+                                    q_value.data_ptr(), _stream()), "bl_fdr_bh")
+    return cutoff, flag, q_value, workspace[:4 * (n_ref + 1)].view(torch.int32)
+
+
+def fdr_bh_workspace_bytes(n_ref: int) -> int:
+    """Bytes of workspace `fdr_bh` needs for a reference of n_ref scores (host arithmetic; no GPU)."""
+    return int(load_library().bl_fdr_bh_workspace_bytes(int(n_ref)))
 
 
 # ------------------------------------------------------------------------------------------------
