@@ -1060,6 +1060,67 @@ int bl_fdr_bh(const int32_t* count, int64_t N, int64_t n_ref, double q, void* wo
               double* out_q, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Similar-bug search (buglab/models/similar.py), in csrc/bl_similar.hip.  BEYOND THE REFERENCE: it has no counterpart.
+ *
+ * A SITE is one candidate location of one sample; its embedding is the row of the head input h behind that candidate.  An index
+ * of such rows is searched in two stages: an exact top-C search on the int8 images with v_mfma_i32_16x16x64_i8, and an fp64
+ * re-score of those C.  buglab/models/_similar.py is the same arithmetic in NumPy, equal bit for bit on every output.  The
+ * kernels sit on bl_segment_f64.h's contract and are compiled without fused multiply-adds; no exp, no sqrt, no atomics.
+ * Dp = D rounded up to a multiple of 64.
+ *
+ *   centre     c_d = (float)((double)x_d - (double)mean_d)
+ *   row        amax = max_d |c_d|; sumsq = sum_d c_d c_d in fp64 with bl_attr_node_scores' column ownership and butterfly.
+ *              A row is INVALID if a c_d is not finite or amax == 0: q = 0, sumsq = 0, r = 0; never a candidate, and as a query
+ *              it has no neighbours.
+ *   quantise   q_d = (int8)rint((double)c_d * (127.0 / (double)amax)), half to even; columns D .. Dp - 1 zero;
+ *              r = ((double)amax * (double)amax) / sumsq
+ *   key        idot = sum_d qx_d qy_d, exact in int32; key = (double)((int64)idot * |idot|) * r_y: apart from quantisation
+ *              error monotone in the cosine
+ *   search     per valid query the C valid index rows that come first in "greater key, or the same key at the lower index",
+ *              -1 (key 0.0) padded: the exact top C under a total order, whatever the tiles, the slices and the geometry
+ *   re-score   dot = sum_d cx_d cy_d in fp64 in the order of sumsq; key2 = (dot * |dot|) / sumsq_y; the k <= C first candidates
+ *              by (greater key2, lower index, earlier place in the list), -1 (dot 0.0) padded.  A candidate outside [0, N), with
+ *              sumsq_y <= 0 or with a NaN key2 is absent.  The host forms the cosine dot / sqrt(sumsq_x sumsq_y).
+ *
+ * bl_sim_embed_sites: one launch per predict minibatch of B samples, one wave per sample.  flat [n_flat]: the model's flat
+ *   output, whose first n_cand entries are the candidates' location log-probabilities; loc_idx / loc_off: the PredictionLayout's
+ *   location entries (a sample's candidates in canonical order, NO_BUG last; offsets clamped into [0, total_loc]); cand_rows
+ *   [n_cand]: the row of h behind each candidate; h [n_rows, D], row stride ldh.  mode BL_SIM_SITE_PREDICTED: the site is the
+ *   first maximum of the sample's entries (NaN and indices outside flat never enter; skip_nobug leaves NO_BUG out); a NO_BUG
+ *   that wins means no site.  BL_SIM_SITE_TRUTH: truth [B] is the site's place within the segment, -1 for none.  Written at
+ *   offset + b of the run-long buffers: out_rows [capacity, D] (zeros without a site), out_place (-1 without), out_logprob (the
+ *   fp32 entry as it is; 0 without).  Any index out of range means "no site", never an out-of-bounds read.
+ *   BL_EINVAL: null pointers, negative sizes, ldh < D, unknown mode, offset + B > capacity.  BL_ERANGE: D > BL_SIM_MAX_D, index
+ *   spaces beyond int32.
+ * bl_sim_quantize: x [N, D] (row stride ldx, any alignment), mean [D] -> c [N, D] (row stride ldc; c == x with ldc == ldx is
+ *   allowed), q int8 [N, Dp] (contiguous, 16-byte aligned), sumsq and r double [N].  One wave per row.
+ * bl_sim_search_i8: qx [Q, Dp] / rx [Q] the queries, qy [N, Dp] / ry [N] the index (r <= 0 marks an invalid row) -> out_idx
+ *   int32 [Q, C], out_key double [Q, C].  slices in [1, BL_SIM_MAX_SLICES]: the index is cut into that many parts, searched by
+ *   separate workgroups and merged; the result does not depend on it.  workspace: bl_sim_search_workspace_bytes(Q, slices)
+ *   bytes, 8-byte aligned, contents irrelevant.  BL_EINVAL: Dp not a multiple of 64, C outside [1, BL_SIM_MAX_CANDIDATES], slices
+ *   out of range, a workspace too small, images not 16-byte aligned.  BL_ERANGE: Dp > BL_SIM_MAX_D, N beyond int32.
+ * bl_sim_rescore: cx [Q, D], cy [N, D] (row strides, any alignment), sumsq_y [N], cand int32 [Q, C] -> out_idx int32 [Q, k],
+ *   out_dot double [Q, k].  BL_EINVAL: k outside [1, C], C outside [1, BL_SIM_MAX_CANDIDATES].
+ * No call synchronises. */
+#define BL_SIM_MAX_D 512
+#define BL_SIM_MAX_CANDIDATES 16
+#define BL_SIM_MAX_SLICES 64
+#define BL_SIM_SITE_PREDICTED 0
+#define BL_SIM_SITE_TRUTH 1
+int bl_sim_embed_sites(const float* flat, int64_t n_flat, const int32_t* loc_idx, const int32_t* loc_off, int64_t total_loc, int32_t B,
+                       const int32_t* cand_rows, int64_t n_cand, const float* h, int64_t ldh, int64_t n_rows, int32_t D,
+                       const int32_t* truth, int32_t skip_nobug, int32_t mode, float* out_rows, int32_t* out_place,
+                       float* out_logprob, int64_t offset, int64_t capacity, void* stream);
+int bl_sim_quantize(const float* x, int64_t ldx, const float* mean, int64_t N, int32_t D, float* c, int64_t ldc, int8_t* q,
+                    double* sumsq, double* r, void* stream);
+int64_t bl_sim_search_workspace_bytes(int64_t Q, int32_t slices);
+int bl_sim_search_i8(const int8_t* qx, const double* rx, int64_t Q, const int8_t* qy, const double* ry, int64_t N, int32_t Dp,
+                     int32_t C, int32_t slices, void* workspace, int64_t workspace_bytes, int32_t* out_idx, double* out_key,
+                     void* stream);
+int bl_sim_rescore(const float* cx, int64_t ldx, int64_t Q, const float* cy, int64_t ldy, const double* sumsq_y, int64_t N, int32_t D,
+                   const int32_t* cand, int32_t C, int32_t k, int32_t* out_idx, double* out_dot, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Confidence calibration (buglab/models/calibrate.py), in csrc/bl_confidence.hip.  BEYOND THE REFERENCE: it has no
  * counterpart; what is calibrated is the confidence its evaluate.py:60-140 thresholds and its visualize.py ranks by.  One
  * inverse temperature beta and a NO_BUG bias rescale the localization distribution, one repair_beta the repair groups:

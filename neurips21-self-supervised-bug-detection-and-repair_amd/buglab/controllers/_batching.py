@@ -110,9 +110,10 @@ def prediction_minibatches(model, tagged: Iterable[Tuple[Any, Any]], device, par
                                         finalize=finalize)
 
 
-def flat_prediction_output(trained_nn, mb_data) -> torch.Tensor:
-    """The forward of the model's own `predict` (gnn.py / seqmodel.py) -> its flat fp32 output [loc | text | var | swap],
-    left on the device; calibrated there (hip_ops.conf_apply) when the model carries a `confidence_calibration`."""
+def flat_prediction_output_and_encoding(trained_nn, mb_data) -> Tuple[torch.Tensor, Any]:
+    """The forward of the model's own `predict` (gnn.py / seqmodel.py) -> (its flat fp32 output [loc | text | var | swap], left
+    on the device and calibrated there (hip_ops.conf_apply) when the model carries a `confidence_calibration`; the encoder
+    output both heads read, for a service that needs the head input as well: `trained_nn._head_inputs`)."""
     _, loc_lp, enc_out, _ = trained_nn.compute_localization_logprobs(mb_data["graph_data"])
     swap_lp, text_lp, var_lp, _ = trained_nn._compute_repair_logprobs(
         enc_out, mb_data["target_rewrites"], mb_data["rewrite_to_location_group"], mb_data["candidate_symbol_to_location_group"],
@@ -123,7 +124,12 @@ def flat_prediction_output(trained_nn, mb_data) -> torch.Tensor:
         from buglab.models._calibrate import apply_to_flat
 
         apply_to_flat(mb_data["confidence_calibration"], flat, mb_data)
-    return flat
+    return flat, enc_out
+
+
+def flat_prediction_output(trained_nn, mb_data) -> torch.Tensor:
+    """The flat output of `flat_prediction_output_and_encoding` alone."""
+    return flat_prediction_output_and_encoding(trained_nn, mb_data)[0]
 
 
 class InOrder:

@@ -207,6 +207,14 @@ _SIGNATURES = {
     "bl_fdr_counts": ([c_void_p, c_int64, c_void_p, c_int32, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_void_p], ctypes.c_int),
     "bl_fdr_bh_workspace_bytes": ([c_int64], c_int64),
     "bl_fdr_bh": ([c_void_p, c_int64, c_int64, c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p], ctypes.c_int),
+    "bl_sim_embed_sites": ([c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int32,
+                            c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p], ctypes.c_int),
+    "bl_sim_quantize": ([c_void_p, c_int64, c_void_p, c_int64, c_int32, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p], ctypes.c_int),
+    "bl_sim_search_workspace_bytes": ([c_int64, c_int32], c_int64),
+    "bl_sim_search_i8": ([c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int32, c_int32, c_int32, c_void_p, c_int64, c_void_p,
+                          c_void_p, c_void_p], ctypes.c_int),
+    "bl_sim_rescore": ([c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int32, c_void_p, c_int32, c_int32, c_void_p,
+                        c_void_p, c_void_p], ctypes.c_int),
     "bl_attr_node_scores": ([c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int32, c_double, c_int32, c_void_p, c_void_p], ctypes.c_int),
     "bl_attr_topk": ([c_void_p, c_void_p, c_int32, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p],
                      ctypes.c_int),

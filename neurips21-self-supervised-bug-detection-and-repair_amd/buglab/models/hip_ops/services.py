@@ -12,6 +12,7 @@ __all__ = ["ENSEMBLE_KINDS", "ENSEMBLE_MAX_MEMBERS", "ensemble_combine", "ens_lo
            "SELECTOR_MAX_K", "_f64", "score_targets",
            "selector_sample", "REPORT_MAX_SAMPLES", "REPORT_INDEX_FIELDS", "report_summarize", "report_order", "EVAL_INDEX_FIELDS", "eval_judge",
            "SUGGEST_MAX_K", "SUGGEST_INDEX_FIELDS", "rank_suggestions", "FDR_MAX_REFERENCE", "fdr_counts", "fdr_bh", "fdr_bh_workspace_bytes", "EXPLAIN_MAX_K", "attribute_node_scores", "attribute_topk",
+           "SIM_MAX_D", "SIM_MAX_CANDIDATES", "SIM_MAX_SLICES", "SIM_SITE_MODES", "similar_embed_sites", "similar_quantize", "similar_search", "similar_search_slices", "similar_rescore",
            "BOOTSTRAP_MAX_MODELS", "BOOTSTRAP_MAX_SCOUTS", "bootstrap_counts", "CURVE_MAX_BINS", "CURVE_COUNTERS", "bootstrap_curve_counts", "conf_loc_stats", "conf_group_stats", "conf_apply", "DEDUP_MAX_PERM",
            "DEDUP_EMPTY_SLOT", "_i64", "dedup_sha1_u32", "dedup_minhash", "dedup_lsh_insert_query"]
 
@@ -387,6 +388,145 @@ def attribute_topk(score, node_off, out_node, out_score, out_sums, offset: int, 
         raise ValueError(f"attribute_topk: graphs {offset} .. {offset + B} do not fit the result buffers of {C} graphs")
     _check(load_library().bl_attr_topk(score.data_ptr(), node_off.data_ptr(), B, N, k, int(bool(by_abs)), out_node.data_ptr(),
                                        out_score.data_ptr(), out_sums.data_ptr(), offset, C, _stream()), "bl_attr_topk")
+
+
+# ------------------------------------------------------------------------------------------------
+# similar-bug search (csrc/bl_similar.hip; include/buglab_hip.h::bl_sim_embed_sites, bl_sim_quantize, bl_sim_search_i8,
+# bl_sim_rescore).  Shapes and ranges are checked first (plain ValueErrors, also without a GPU), devices after.
+SIM_MAX_D = 512           # BL_SIM_MAX_D
+SIM_MAX_CANDIDATES = 16   # BL_SIM_MAX_CANDIDATES
+SIM_MAX_SLICES = 64       # BL_SIM_MAX_SLICES
+SIM_SITE_MODES = {"predicted": 0, "truth": 1}  # BL_SIM_SITE_PREDICTED, BL_SIM_SITE_TRUTH
+
+
+def _sim_dim(D: int, what: str) -> int:
+    if not 1 <= int(D) <= SIM_MAX_D:
+        raise ValueError(f"{what}: the embedding size D must be in [1, {SIM_MAX_D}] (got {D})")
+    return int(D)
+
+
+def _ld(t, D: int) -> int:
+    return t.stride(0) if t.shape[0] > 1 else max(t.stride(0), D)
+
+
+def similar_embed_sites(flat, loc_idx, loc_off, cand_rows, h, out_rows, out_place, out_logprob, offset: int, *, mode: str = "predicted",
+                        truth=None, skip_nobug: bool = False) -> None:
+    """The site of each of the B samples of one predict minibatch and the row of `h` behind it, written to samples offset ..
+    offset + B - 1 of the run-long buffers out_rows (float32 [N, D]; zeros without a site), out_place (int32 [N]: the site's place
+    among the sample's location entries, -1 without) and out_logprob (float32 [N]).  flat float32 [n_flat]; loc_idx / loc_off
+    int32: the PredictionLayout's; cand_rows int32 [n_cand]: the forward's own refs["candidate_nodes"]; h float32 [n_rows, D]
+    (any row stride); mode "predicted" (the first maximum; `skip_nobug` leaves NO_BUG out; a winning NO_BUG is no site) or
+    "truth" (`truth` int32 [B]: the place, -1 for none).  Exactly buglab/models/_similar.py::embed_sites_host.  No sync."""
+    what = "similar_embed_sites"
+    if mode not in SIM_SITE_MODES:
+        raise ValueError(f"{what}: mode must be one of {sorted(SIM_SITE_MODES)} (got {mode!r})")
+    if h.dim() != 2 or loc_off.dim() != 1 or loc_off.shape[0] < 1 or out_rows.dim() != 2:
+        raise ValueError(f"{what}: h {tuple(h.shape)} must be [n_rows, D], loc_off {tuple(loc_off.shape)} [B + 1], out_rows "
+                         f"{tuple(out_rows.shape)} [N, D]")
+    D, B, N = _sim_dim(h.shape[1], what), loc_off.shape[0] - 1, out_rows.shape[0]
+    if (mode == "truth") != (truth is not None):
+        raise ValueError(f"{what}: `truth` goes with mode 'truth' and with no other")
+    if out_rows.shape[1] != D or tuple(out_place.shape) != (N,) or tuple(out_logprob.shape) != (N,) \
+            or (truth is not None and tuple(truth.shape) != (B,)):
+        raise ValueError(f"{what}: inconsistent shapes (out_rows {tuple(out_rows.shape)} must be [N, {D}], out_place "
+                         f"{tuple(out_place.shape)} and out_logprob {tuple(out_logprob.shape)} [N], truth [{B}])")
+    offset = int(offset)
+    if not 0 <= offset <= N - B:
+        raise ValueError(f"{what}: samples {offset} .. {offset + B} do not fit the result buffers of {N} samples")
+    _f32(flat, "flat"), _i32(loc_idx, "loc_idx"), _i32(loc_off, "loc_off"), _i32(cand_rows, "cand_rows"), _rows_f32(h, "h", what)
+    _f32(out_rows, "out_rows"), _i32(out_place, "out_place"), _f32(out_logprob, "out_logprob")
+    if truth is not None:
+        _i32(truth, "truth")
+    _check(load_library().bl_sim_embed_sites(flat.data_ptr(), flat.numel(), loc_idx.data_ptr(), loc_off.data_ptr(), loc_idx.numel(), B,
+                                             cand_rows.data_ptr(), cand_rows.numel(), h.data_ptr(), _ld(h, D), h.shape[0], D, _p(truth),
+                                             int(bool(skip_nobug)), SIM_SITE_MODES[mode], out_rows.data_ptr(), out_place.data_ptr(),
+                                             out_logprob.data_ptr(), offset, N, _stream()), "bl_sim_embed_sites")
+
+
+def similar_quantize(x, mean, out_c=None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """x float32 [N, D] (any row stride and alignment), mean float32 [D] -> (c float32 [N, D] = x - mean, q int8 [N, Dp], sumsq
+    float64 [N], r float64 [N]); Dp = D rounded up to a multiple of 64.  `out_c`: where to write c (x itself centres in place; a
+    new contiguous tensor when None).  An invalid row (not finite, or all zero after centring) has q = 0, sumsq = 0, r = 0.
+    Exactly buglab/models/_similar.py::quantize_host.  No sync."""
+    what = "similar_quantize"
+    if x.dim() != 2 or mean.dim() != 1 or mean.shape[0] != x.shape[1]:
+        raise ValueError(f"{what}: x {tuple(x.shape)} must be [N, D] and mean {tuple(mean.shape)} [D]")
+    N, D = x.shape[0], _sim_dim(x.shape[1], what)
+    if out_c is not None and tuple(out_c.shape) != (N, D):
+        raise ValueError(f"{what}: out_c {tuple(out_c.shape)} must be [{N}, {D}]")
+    _rows_f32(x, "x", what), _f32(mean, "mean")
+    c = torch.empty((N, D), dtype=torch.float32, device=x.device) if out_c is None else _rows_f32(out_c, "out_c", what)
+    Dp = (D + 63) // 64 * 64
+    q = torch.empty((N, Dp), dtype=torch.int8, device=x.device)
+    stats = torch.empty((2, N), dtype=torch.float64, device=x.device)
+    _check(load_library().bl_sim_quantize(x.data_ptr(), _ld(x, D), mean.data_ptr(), N, D, c.data_ptr(), _ld(c, D), q.data_ptr(),
+                                          stats[0].data_ptr(), stats[1].data_ptr(), _stream()), "bl_sim_quantize")
+    return c, q, stats[0], stats[1]
+
+
+def similar_search_slices(Q: int, N: int) -> int:
+    """The number of index slices `similar_search` takes by default.  A search workgroup (16 queries x one slice) holds 48 KB of
+    LDS and 230 VGPRs, so two are resident per compute unit, 512 on the chip: the grid ceil(Q / 16) x S stays within that one
+    round (measured: at Q = 1000 the search takes 0.71 ms with S = 8, 504 workgroups, and 1.26 ms with S = 9, 567: DESIGN.md).
+    Each slice ends in a ranking whose cost does not depend on its length, about that of searching 10^4 rows, so no slice is
+    shorter than 1024 rows.  The result of a search does not depend on S."""
+    tiles_q = max((int(Q) + 15) // 16, 1)
+    return max(1, min(SIM_MAX_SLICES, 512 // tiles_q, int(N) // 1024))
+
+
+def similar_search(qx, rx, qy, ry, candidates: int = SIM_MAX_CANDIDATES, slices: Optional[int] = None
+                   ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The exact top `candidates` of every query under the coarse key -> (index int32 [Q, C], -1 padded; key float64 [Q, C], 0.0
+    padded), in order: greater key first, the lower index among equals.  qx int8 [Q, Dp] / rx float64 [Q]: the queries; qy int8
+    [N, Dp] / ry float64 [N]: the index (`similar_quantize`'s q and r).  `slices`: into how many parts the index is cut (for
+    tests and tuning; `similar_search_slices` when None) -- the result does not depend on it.  Exactly
+    buglab/models/_similar.py::search_host.  No sync."""
+    what = "similar_search"
+    C = int(candidates)
+    if not 1 <= C <= SIM_MAX_CANDIDATES:
+        raise ValueError(f"{what}: candidates must be in [1, {SIM_MAX_CANDIDATES}] (got {candidates})")
+    if qx.dim() != 2 or qy.dim() != 2 or qx.shape[1] != qy.shape[1] or qx.shape[1] % 64 or not 64 <= qx.shape[1] <= SIM_MAX_D:
+        raise ValueError(f"{what}: qx {tuple(qx.shape)} and qy {tuple(qy.shape)} must be [Q, Dp] and [N, Dp], Dp a multiple of 64 up to "
+                         f"{SIM_MAX_D}")
+    Q, N, Dp = qx.shape[0], qy.shape[0], qx.shape[1]
+    if tuple(rx.shape) != (Q,) or tuple(ry.shape) != (N,):
+        raise ValueError(f"{what}: rx {tuple(rx.shape)} must be [{Q}] and ry {tuple(ry.shape)} [{N}]")
+    S = similar_search_slices(Q, N) if slices is None else int(slices)
+    if not 1 <= S <= SIM_MAX_SLICES:
+        raise ValueError(f"{what}: slices must be in [1, {SIM_MAX_SLICES}] (got {slices})")
+    _req(qx, torch.int8, "qx"), _req(qy, torch.int8, "qy"), _f64(rx, "rx"), _f64(ry, "ry")
+    lib = load_library()
+    need = int(lib.bl_sim_search_workspace_bytes(Q, S))
+    workspace = torch.empty(max(need // 8, 1), dtype=torch.float64, device=qx.device)
+    out_idx = torch.empty((Q, C), dtype=torch.int32, device=qx.device)
+    out_key = torch.empty((Q, C), dtype=torch.float64, device=qx.device)
+    _check(lib.bl_sim_search_i8(qx.data_ptr(), rx.data_ptr(), Q, qy.data_ptr(), ry.data_ptr(), N, Dp, C, S, workspace.data_ptr(), need,
+                                out_idx.data_ptr(), out_key.data_ptr(), _stream()), "bl_sim_search_i8")
+    return out_idx, out_key
+
+
+def similar_rescore(cx, cy, sumsq_y, cand, k: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The candidates of every query re-scored in fp64 -> (index int32 [Q, k], -1 padded; dot float64 [Q, k], 0.0 padded): the k
+    first by key2 = dot |dot| / sumsq_y, the lower index among equals.  cx float32 [Q, D], cy float32 [N, D] (any row stride and
+    alignment), sumsq_y float64 [N], cand int32 [Q, C] (-1: none).  Exactly buglab/models/_similar.py::rescore_host.  No sync."""
+    what = "similar_rescore"
+    if cx.dim() != 2 or cy.dim() != 2 or cx.shape[1] != cy.shape[1] or cand.dim() != 2 or cand.shape[0] != cx.shape[0]:
+        raise ValueError(f"{what}: cx {tuple(cx.shape)} must be [Q, D], cy {tuple(cy.shape)} [N, D] and cand {tuple(cand.shape)} [Q, C]")
+    Q, N, D, C, k = cx.shape[0], cy.shape[0], _sim_dim(cx.shape[1], what), cand.shape[1], int(k)
+    if not 1 <= C <= SIM_MAX_CANDIDATES:
+        raise ValueError(f"{what}: the number of candidates must be in [1, {SIM_MAX_CANDIDATES}] (got {C})")
+    if not 1 <= k <= C:
+        raise ValueError(f"{what}: k must be in [1, C = {C}] (got {k})")
+    if tuple(sumsq_y.shape) != (N,):
+        raise ValueError(f"{what}: sumsq_y {tuple(sumsq_y.shape)} must be [{N}]")
+    _rows_f32(cx, "cx", what), _f64(sumsq_y, "sumsq_y"), _i32(cand, "cand")
+    if N:
+        _rows_f32(cy, "cy", what)
+    out_idx = torch.empty((Q, k), dtype=torch.int32, device=cx.device)
+    out_dot = torch.empty((Q, k), dtype=torch.float64, device=cx.device)
+    _check(load_library().bl_sim_rescore(cx.data_ptr(), _ld(cx, D), Q, cy.data_ptr(), _ld(cy, D), sumsq_y.data_ptr(), N, D, cand.data_ptr(),
+                                         C, k, out_idx.data_ptr(), out_dot.data_ptr(), _stream()), "bl_sim_rescore")
+    return out_idx, out_dot
 
 
 # ------------------------------------------------------------------------------------------------

@@ -11,13 +11,14 @@
 // never in a search.  Compiled without fused multiply-adds: score[n] + w * dot is a rounded product and a rounded sum, as NumPy
 // forms it.  The NumPy twin (buglab/models/_explain.py::node_scores_host, topk_host) is equal bit for bit.
 //
-// COLUMN OWNERSHIP of bl_attr_node_scores (restated in include/buglab_hip.h and by the twin): columns go in quads, quad q =
+// COLUMN OWNERSHIP of bl_attr_node_scores (bl_lane_dot_f64.h; restated in include/buglab_hip.h and by the twin): columns go in quads, quad q =
 // columns 4q .. 4q + 3; lane l of the node's wave owns the quads q with q % 64 == l and adds the products of its columns to its
 // own fp64 sum, which starts at +0.0, in ascending column order.  That holds for every D, row stride and alignment: where both
 // rows are 16-byte aligned a whole quad is one 16-byte load per operand, elsewhere (and for the last, partial quad) the same
 // columns are loaded one by one -- the loads differ, the order of the additions does not.  A product of two fp32 values is exact
 // in fp64 (24 + 24 significand bits), so only the additions round.  The 64 lane sums then go through bl_wave_sum_f64.
 #include "bl_common.h"
+#include "bl_lane_dot_f64.h"
 #include "bl_segment_f64.h"
 
 #pragma clang fp contract(off)
@@ -25,32 +26,6 @@
 namespace {
 constexpr int AT_THREADS = 256;
 constexpr int AT_WAVES = AT_THREADS / BL_WAVE;
-
-template <bool VEC>
-__device__ __forceinline__ double at_lane_dot(const float* __restrict__ xr, const float* __restrict__ gr, int D, int lane) {
-  double acc = 0.0;
-  const int full = D / 4;  // whole quads
-  for (int q = lane; q < full; q += BL_WAVE) {
-    float xv[4], gv[4];
-    if (VEC) {
-      const float4 a = *reinterpret_cast<const float4*>(xr + 4 * q);
-      const float4 b = *reinterpret_cast<const float4*>(gr + 4 * q);
-      xv[0] = a.x, xv[1] = a.y, xv[2] = a.z, xv[3] = a.w;
-      gv[0] = b.x, gv[1] = b.y, gv[2] = b.z, gv[3] = b.w;
-    } else {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        xv[j] = xr[4 * q + j];
-        gv[j] = gr[4 * q + j];
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc += (double)xv[j] * (double)gv[j];
-  }
-  if (full % BL_WAVE == lane)  // the last, partial quad belongs to the lane that would own it whole (it comes after all of its others)
-    for (int c = 4 * full; c < D; ++c) acc += (double)xr[c] * (double)gr[c];
-  return acc;
-}
 
 __global__ __launch_bounds__(AT_THREADS) void attr_node_scores_kernel(const float* __restrict__ x, int64_t ldx, const float* __restrict__ g,
                                                                       int64_t ldg, int64_t N, int D, double w, int accumulate, int vec,
@@ -60,7 +35,7 @@ __global__ __launch_bounds__(AT_THREADS) void attr_node_scores_kernel(const floa
   if (n >= N) return;  // the whole wave leaves: the shuffles below are among the lanes of one wave
   const float* xr = x + n * ldx;
   const float* gr = g + n * ldg;
-  const double dot = bl_wave_sum_f64(vec ? at_lane_dot<true>(xr, gr, D, lane) : at_lane_dot<false>(xr, gr, D, lane));
+  const double dot = bl_wave_sum_f64(vec ? bl_lane_dot_f64<true>(xr, gr, D, lane) : bl_lane_dot_f64<false>(xr, gr, D, lane));
   if (lane == 0) {
     const double t = w * dot;
     score[n] = accumulate ? score[n] + t : t;
