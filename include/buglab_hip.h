@@ -647,7 +647,12 @@ typedef struct {
  * (arg-max hits, count) for text / var / swap rewrites, loss, repair loss (times w_buggy), buggy graphs, 1, 0. */
 int bl_bug_loss_fwd(const bl_bug_loss_t* d, float* loc_logprobs, float* repair_logprobs, float* group_max, float* loss,
                     float* stats, void* stream);
-/* g_loss: device scalar; scratch: C + B + Rt + Rv + Rs floats; writes every entry of g_loc_scores [C] and g_repair_logits */
+/* Both calls walk the values through the two CSRs: loc_group_items names every item 0 .. C + B - 1 exactly once and
+ * repair_group_items every logit 0 .. Rt + Rv + Rs - 1 exactly once (the collator's CSR of cat(logit_group): every logit has
+ * a location group).  An item no group names would get no log-probability and no gradient.  An empty location group is fine:
+ * its group_max is -inf.  For the same inputs the outputs of both calls are the same bits on every run.
+ * g_loss: device scalar; scratch: C + B + Rt + Rv + Rs floats; under the condition above bwd writes every entry of
+ * g_loc_scores [C] and g_repair_logits [Rt + Rv + Rs]: the caller need not clear them */
 int bl_bug_loss_bwd(const bl_bug_loss_t* d, const float* loc_logprobs, const float* repair_logprobs, const float* g_loss,
                     float* scratch, float* g_loc_scores, float* g_repair_logits, void* stream);
 
