@@ -1126,6 +1126,67 @@ int bl_sim_rescore(const float* cx, int64_t ldx, int64_t Q, const float* cy, int
                    const int32_t* cand, int32_t C, int32_t k, int32_t* out_idx, double* out_dot, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Drift detection (buglab/models/drift.py), in csrc/bl_drift.hip.  BEYOND THE REFERENCE: it has no counterpart.  A two-sample
+ * permutation test of the kernel maximum mean discrepancy (MMD) between the site embeddings of a reference (a SiteIndex) and
+ * those of the data about to be scanned.  buglab/models/_drift.py is the twin: the subsets bit for bit, the sums in fp64.
+ *
+ *   pooled rows  Z = [X_ref ; X_new], fp32 [N, D], N = n + m, n, m >= 2: the index's centred embeddings, then the scanned
+ *                sites' embeddings centred with the index's mean.
+ *   bandwidth    s = scale * (1 / N^2) sum_ij |z_i - z_j|^2 = scale * 2 (mean_i |z_i|^2 - |mean_i z_i|^2), in fp64 from column
+ *                sums.  NO SPREAD: when the bracket is at most 2^-40 of mean_i |z_i|^2 (all rows equal up to fp64 rounding of
+ *                the sums), s = 0; the sums then take every kernel value as 1 and the report says statistic 0, p-value 1.
+ *   kernel       k(x, y) = exp(-max(|x|^2 + |y|^2 - 2 x.y, 0) / s); the row norms are the fp32 roundings of fp64 sums.
+ *   subsets      a_0[i] = 1 iff i < n.  For r = 1 .. R, row i has the key mix(base + (r << 32) + i), uint64 and wrapping, with
+ *                bl_bootstrap_counts' mix and base = mix(seed * 0x9E3779B97F4A7C15 + 0x9E3779B97F4A7C15): it depends on
+ *                (seed, r, i) alone.  a_r[i] = 1 iff fewer than n rows precede (key_i, i) in lexicographic order, so equal keys
+ *                go to the lower row.  Integer work: device and twin agree bit for bit.
+ *   the mask     uint8 [R + 2, ldm], ldm = bl_drift_mask_ld(N) = N rounded up to a multiple of 32: row r <= R is a_r, row
+ *                R + 1 is all ones (it yields rho = K 1 and S); bytes N .. ldm - 1 of every row are 0.
+ *   sums         with U = K A (A the [N, R + 2] matrix whose columns are the mask's rows):
+ *                A_r = sum_i a_r[i] U[i, r];  B_r = sum_i U[i, r] = a_r^T K 1;  S = 1^T K 1;
+ *                MMD2_r = A_r / n^2 + (S - 2 B_r + A_r) / m^2 - 2 (B_r - A_r) / (n m)   (the biased V-statistic)
+ *                The MMD weights sum to zero, so the device works on K - c for a caller-chosen constant c in [0, 1] (`shift`;
+ *                drift.py passes exp(-1 / scale), the kernel value at the mean squared distance) and adds c n^2, c n N, c N^2,
+ *                c n and c N back in fp64: every output is of K itself.
+ *   p-value      (1 + #{r >= 1 : MMD2_r >= MMD2_0}) / (R + 1), on the host in fp64.
+ *   witness      for a scanned row i >= n: f_i = U[i, 0] / n - (rho_i - U[i, 0]) / m, rho = K 1; the most negative are the
+ *                samples least like the reference.
+ *
+ * Arithmetic of bl_drift_permutation_sums.  Z_j Z_i^T on v_mfma_f32_16x16x4_f32: exact fp32 products, fp32 accumulation (gfx950
+ * has no xf32; embeddings are unbounded, which rules the clamped f16x3 images out).  The kernel tile in registers: n_i + n_j - 2 G,
+ * clamp at 0, expf, minus c.  Then K ALONE is cut into three bf16 planes by truncation, hi + mid + lo == the fp32 value exactly,
+ * and each plane is one v_mfma_f32_16x16x32_bf16 against the mask, which is exact in bf16: an fp32-class second product in three
+ * terms.  The first product's accumulator tiles are the second's B operand as they lie.  Nothing of size N x N or N x R reaches
+ * memory beyond the byte mask and, per 16 rows, one fp64 partial of A_r and B_r; a second kernel adds those in row order in fp64.
+ * No atomics: equal bits on every run and for every col_tiles.  Rows beyond N, mask rows beyond R + 1 and the padding of D (to a
+ * multiple of 64, as the similar-bug search pads) contribute exactly nothing.
+ *
+ * bl_drift_ok: 1 <= D <= BL_DRIFT_MAX_D and 1 <= R <= BL_DRIFT_MAX_PERMUTATIONS.
+ * bl_drift_bandwidth: z [N, D] (row stride ldz, any alignment) -> out_rownorm float [N], out_bandwidth double [1] = s.
+ *   workspace: bl_drift_bandwidth_workspace_bytes(N, D) bytes, 8-byte aligned.
+ * bl_drift_subsets: -> out_mask uint8 [R + 2, ldm], ldm == bl_drift_mask_ld(N), 4-byte aligned.  One workgroup per row; the n-th
+ *   smallest key by 8-bit radix selection over recomputed keys, no sort and no key in memory.
+ * bl_drift_permutation_sums: -> out_sums double [2 (R + 1) + 1] = A_0 .. A_R | B_0 .. B_R | S; out_u0 double [N] = U[:, 0];
+ *   out_rho double [N] = K 1.  bandwidth: the DEVICE double bl_drift_bandwidth wrote (no synchronisation in between).
+ *   col_tiles: 16-row groups of the mask per workgroup, 4, 8 or 16, 0 = the default; for tests and tuning, the result does not
+ *   depend on it.  workspace: bl_drift_sums_workspace_bytes(N, R) bytes, 8-byte aligned.
+ * BL_EINVAL: null pointers, n < 2 or N - n < 2, R < 1, ldz < D, a wrong ldm, misaligned buffers, a workspace too small, shift
+ *   outside [0, 1], col_tiles not in {0, 4, 8, 16}.  BL_ERANGE: D > BL_DRIFT_MAX_D, R > BL_DRIFT_MAX_PERMUTATIONS, N beyond int32.
+ * No call synchronises. */
+#define BL_DRIFT_MAX_D 512
+#define BL_DRIFT_MAX_PERMUTATIONS 65533
+int32_t bl_drift_ok(int32_t D, int64_t R);
+int64_t bl_drift_mask_ld(int64_t N);
+int64_t bl_drift_bandwidth_workspace_bytes(int64_t N, int32_t D);
+int bl_drift_bandwidth(const float* z, int64_t ldz, int64_t N, int32_t D, double scale, void* workspace, int64_t workspace_bytes,
+                       float* out_rownorm, double* out_bandwidth, void* stream);
+int bl_drift_subsets(int64_t N, int64_t n, int64_t R, uint64_t seed, uint8_t* out_mask, int64_t ldm, void* stream);
+int64_t bl_drift_sums_workspace_bytes(int64_t N, int64_t R);
+int bl_drift_permutation_sums(const float* z, int64_t ldz, int64_t N, int64_t n, int32_t D, const float* rownorm, const uint8_t* mask,
+                              int64_t ldm, int64_t R, const double* bandwidth, double shift, int32_t col_tiles, void* workspace,
+                              int64_t workspace_bytes, double* out_sums, double* out_u0, double* out_rho, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Confidence calibration (buglab/models/calibrate.py), in csrc/bl_confidence.hip.  BEYOND THE REFERENCE: it has no
  * counterpart; what is calibrated is the confidence its evaluate.py:60-140 thresholds and its visualize.py ranks by.  One
  * inverse temperature beta and a NO_BUG bias rescale the localization distribution, one repair_beta the repair groups:

@@ -215,6 +215,14 @@ _SIGNATURES = {
                           c_void_p, c_void_p], ctypes.c_int),
     "bl_sim_rescore": ([c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int32, c_void_p, c_int32, c_int32, c_void_p,
                         c_void_p, c_void_p], ctypes.c_int),
+    "bl_drift_ok": ([c_int32, c_int64], c_int32),
+    "bl_drift_mask_ld": ([c_int64], c_int64),
+    "bl_drift_bandwidth_workspace_bytes": ([c_int64, c_int32], c_int64),
+    "bl_drift_bandwidth": ([c_void_p, c_int64, c_int64, c_int32, c_double, c_void_p, c_int64, c_void_p, c_void_p, c_void_p], ctypes.c_int),
+    "bl_drift_subsets": ([c_int64, c_int64, c_int64, c_uint64, c_void_p, c_int64, c_void_p], ctypes.c_int),
+    "bl_drift_sums_workspace_bytes": ([c_int64, c_int64], c_int64),
+    "bl_drift_permutation_sums": ([c_void_p, c_int64, c_int64, c_int64, c_int32, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_double,
+                                   c_int32, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p], ctypes.c_int),
     "bl_attr_node_scores": ([c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int32, c_double, c_int32, c_void_p, c_void_p], ctypes.c_int),
     "bl_attr_topk": ([c_void_p, c_void_p, c_int32, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p],
                      ctypes.c_int),

@@ -1,5 +1,5 @@
 """Forward-only device services: ensemble combine, self-supervision scoring / sampling, bug reports, evaluation, confidence
-calibration, near-duplicate detection."""
+calibration, near-duplicate detection, drift detection."""
 from __future__ import annotations
 
 from typing import Optional, Tuple
@@ -13,6 +13,7 @@ __all__ = ["ENSEMBLE_KINDS", "ENSEMBLE_MAX_MEMBERS", "ensemble_combine", "ens_lo
            "selector_sample", "REPORT_MAX_SAMPLES", "REPORT_INDEX_FIELDS", "report_summarize", "report_order", "EVAL_INDEX_FIELDS", "eval_judge",
            "SUGGEST_MAX_K", "SUGGEST_INDEX_FIELDS", "rank_suggestions", "FDR_MAX_REFERENCE", "fdr_counts", "fdr_bh", "fdr_bh_workspace_bytes", "EXPLAIN_MAX_K", "attribute_node_scores", "attribute_topk",
            "SIM_MAX_D", "SIM_MAX_CANDIDATES", "SIM_MAX_SLICES", "SIM_SITE_MODES", "similar_embed_sites", "similar_quantize", "similar_search", "similar_search_slices", "similar_rescore",
+           "DRIFT_MAX_D", "DRIFT_MAX_PERMUTATIONS", "drift_ok", "drift_mask_ld", "drift_bandwidth", "drift_subsets", "drift_permutation_sums",
            "BOOTSTRAP_MAX_MODELS", "BOOTSTRAP_MAX_SCOUTS", "bootstrap_counts", "CURVE_MAX_BINS", "CURVE_COUNTERS", "bootstrap_curve_counts", "conf_loc_stats", "conf_group_stats", "conf_apply", "DEDUP_MAX_PERM",
            "DEDUP_EMPTY_SLOT", "_i64", "dedup_sha1_u32", "dedup_minhash", "dedup_lsh_insert_query"]
 
@@ -527,6 +528,116 @@ def similar_rescore(cx, cy, sumsq_y, cand, k: int) -> Tuple[torch.Tensor, torch.
     _check(load_library().bl_sim_rescore(cx.data_ptr(), _ld(cx, D), Q, cy.data_ptr(), _ld(cy, D), sumsq_y.data_ptr(), N, D, cand.data_ptr(),
                                          C, k, out_idx.data_ptr(), out_dot.data_ptr(), _stream()), "bl_sim_rescore")
     return out_idx, out_dot
+
+
+# ------------------------------------------------------------------------------------------------
+# drift detection (csrc/bl_drift.hip; include/buglab_hip.h::bl_drift_bandwidth, bl_drift_subsets, bl_drift_permutation_sums).
+# Shapes and ranges are checked first (plain ValueErrors, also without a GPU), devices after.
+DRIFT_MAX_D = 512                # BL_DRIFT_MAX_D
+DRIFT_MAX_PERMUTATIONS = 65533   # BL_DRIFT_MAX_PERMUTATIONS
+
+
+def drift_ok(D: int, R: int) -> bool:
+    """Whether the drift kernels take embeddings of size D and R permutations (bl_drift_ok, restated: no library needed)."""
+    return 1 <= int(D) <= DRIFT_MAX_D and 1 <= int(R) <= DRIFT_MAX_PERMUTATIONS
+
+
+def drift_mask_ld(N: int) -> int:
+    """The row stride of the subset mask: N rounded up to a multiple of 32 (bl_drift_mask_ld)."""
+    return (int(N) + 31) // 32 * 32
+
+
+def _drift_sizes(what: str, N: int, n: int, D: int, R: int) -> None:
+    if not (2 <= int(n) <= int(N) - 2):
+        raise ValueError(f"{what}: both samples need at least 2 rows (got n {n} of N {N})")
+    if not drift_ok(D, R):
+        raise ValueError(f"{what}: need 1 <= D <= {DRIFT_MAX_D} and 1 <= R <= {DRIFT_MAX_PERMUTATIONS} (got D {D}, R {R})")
+
+
+def _drift_out(out, shape, dtype, device, name: str, what: str):
+    if out is None:
+        return torch.empty(shape, dtype=dtype, device=device)
+    if tuple(out.shape) != tuple(shape) or out.device != device:
+        raise ValueError(f"{what}: {name} {tuple(out.shape)} on {out.device} must be {tuple(shape)} on {device}")
+    return _req(out, dtype, name)
+
+
+def drift_bandwidth(z, scale: float = 1.0, out_rownorm=None, out_bandwidth=None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """z float32 [N, D] (any row stride and alignment) -> (bandwidth float64 [1], rownorm float32 [N]): s = scale * 2 (mean |z_i|^2
+    - |mean z_i|^2) from fp64 column sums, 0 when there is no spread, and every row's |z_i|^2 summed in fp64 and rounded once.
+    `out_*`: the caller's tensors to fill.  Twin: buglab/models/_drift.py::bandwidth_host.  No sync."""
+    what = "drift_bandwidth"
+    if z.dim() != 2 or z.shape[0] < 4 or not 1 <= z.shape[1] <= DRIFT_MAX_D:
+        raise ValueError(f"{what}: z {tuple(z.shape)} must be [N >= 4, 1 <= D <= {DRIFT_MAX_D}]")
+    scale = float(scale)
+    if not 0.0 < scale < float("inf"):
+        raise ValueError(f"{what}: the scale must be positive and finite (got {scale})")
+    _rows_f32(z, "z", what)
+    N, D = z.shape
+    rown = _drift_out(out_rownorm, (N,), torch.float32, z.device, "out_rownorm", what)
+    bw = _drift_out(out_bandwidth, (1,), torch.float64, z.device, "out_bandwidth", what)
+    lib = load_library()
+    need = int(lib.bl_drift_bandwidth_workspace_bytes(N, D))
+    workspace = torch.empty(max(need // 8, 1), dtype=torch.float64, device=z.device)
+    _check(lib.bl_drift_bandwidth(z.data_ptr(), _ld(z, D), N, D, scale, workspace.data_ptr(), need, rown.data_ptr(), bw.data_ptr(),
+                                  _stream()), "bl_drift_bandwidth")
+    return bw, rown
+
+
+def drift_subsets(N: int, n: int, R: int, seed: int, device=None, out=None) -> torch.Tensor:
+    """The subset mask uint8 [R + 2, drift_mask_ld(N)]: row 0 the observed split (i < n), rows 1 .. R seeded n-subsets of the N
+    rows, row R + 1 all ones; bytes beyond N are 0.  `out`: the caller's tensor to fill (then `device` is its own).  Rows 0 .. R
+    equal buglab/models/_drift.py::subsets_host bit for bit.  No sync."""
+    what = "drift_subsets"
+    N, n, R = int(N), int(n), int(R)
+    _drift_sizes(what, N, n, 1, R)
+    if N > 0x7FFFFFFF:
+        raise ValueError(f"{what}: N = {N} is beyond int32")
+    ldm = drift_mask_ld(N)
+    if out is None and device is None:
+        raise ValueError(f"{what}: give a device or an out tensor")
+    device = torch.device(device) if out is None else out.device
+    if device.type != "cuda":
+        raise ValueError(f"{what}: the mask is on {device}; the kernel only runs on a ROCm GPU")
+    mask = _drift_out(out, (R + 2, ldm), torch.uint8, device, "out", what)
+    _check(load_library().bl_drift_subsets(N, n, R, int(seed) & 0xFFFFFFFFFFFFFFFF, mask.data_ptr(), ldm, _stream()), "bl_drift_subsets")
+    return mask
+
+
+def drift_permutation_sums(z, rownorm, mask, n: int, bandwidth, shift: float = 0.0, *, col_tiles: Optional[int] = None, out_sums=None,
+                           out_u0=None, out_rho=None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """The fused permutation sums -> (sums float64 [2 (R + 1) + 1] = A_0 .. A_R | B_0 .. B_R | S, u0 float64 [N] = U[:, 0], rho
+    float64 [N] = K 1) of the RBF kernel matrix K of the pooled rows z float32 [N, D] (any row stride and alignment; the first n
+    are the reference), which is never formed.  rownorm float32 [N] and bandwidth float64 [1]: `drift_bandwidth`'s; mask uint8
+    [R + 2, drift_mask_ld(N)]: `drift_subsets`'.  shift in [0, 1]: the constant the kernel subtracts from K while it sums (added
+    back in fp64: the outputs are of K).  `col_tiles` (4, 8 or 16): how many 16-row groups of the mask a workgroup takes, for tests
+    and tuning -- the result does not depend on it.  `out_*`: the caller's tensors to fill.  Reference:
+    buglab/models/_drift.py::permutation_sums_host (fp64).  No sync."""
+    what = "drift_permutation_sums"
+    if z.dim() != 2 or mask.dim() != 2 or rownorm.dim() != 1 or bandwidth.numel() != 1:
+        raise ValueError(f"{what}: z {tuple(z.shape)} must be [N, D], mask {tuple(mask.shape)} [R + 2, ld], rownorm "
+                         f"{tuple(rownorm.shape)} [N] and bandwidth {tuple(bandwidth.shape)} [1]")
+    N, D, R = z.shape[0], z.shape[1], mask.shape[0] - 2
+    _drift_sizes(what, N, n, D, R)
+    if tuple(mask.shape) != (R + 2, drift_mask_ld(N)) or rownorm.shape[0] != N:
+        raise ValueError(f"{what}: mask {tuple(mask.shape)} must be [{R + 2}, {drift_mask_ld(N)}] and rownorm {tuple(rownorm.shape)} [{N}]")
+    ct = 0 if col_tiles is None else int(col_tiles)
+    if ct not in (0, 4, 8, 16):
+        raise ValueError(f"{what}: col_tiles must be 4, 8 or 16 (got {col_tiles})")
+    shift = float(shift)
+    if not 0.0 <= shift <= 1.0:
+        raise ValueError(f"{what}: the shift must be in [0, 1] (got {shift})")
+    _rows_f32(z, "z", what), _f32(rownorm, "rownorm"), _req(mask, torch.uint8, "mask"), _f64(bandwidth, "bandwidth")
+    sums = _drift_out(out_sums, (2 * (R + 1) + 1,), torch.float64, z.device, "out_sums", what)
+    u0 = _drift_out(out_u0, (N,), torch.float64, z.device, "out_u0", what)
+    rho = _drift_out(out_rho, (N,), torch.float64, z.device, "out_rho", what)
+    lib = load_library()
+    need = int(lib.bl_drift_sums_workspace_bytes(N, R))
+    workspace = torch.empty(max(need // 8, 1), dtype=torch.float64, device=z.device)
+    _check(lib.bl_drift_permutation_sums(z.data_ptr(), _ld(z, D), N, int(n), D, rownorm.data_ptr(), mask.data_ptr(), mask.shape[1], R,
+                                         bandwidth.data_ptr(), shift, ct, workspace.data_ptr(), need, sums.data_ptr(), u0.data_ptr(),
+                                         rho.data_ptr(), _stream()), "bl_drift_permutation_sums")
+    return sums, u0, rho
 
 
 # ------------------------------------------------------------------------------------------------
