@@ -32,8 +32,9 @@ def _run_hip(module, mb_np, seed=None):
 
     mb = to_device(mb_np, "cuda")
     module.zero_grad(set_to_none=True)
-    # bind every .grad to a preallocated buffer like FlatAdam does: exercises the direct
-    # accumulation of weight gradients into param.grad on the free-running side stream
+    # bind every OTHER .grad to a preallocated buffer like FlatAdam does for all of them: exercises the direct accumulation into
+    # param.grad next to gradients returned through autograd.  In gnn-mlp a layer's W and Wd are not both bound this way, so its
+    # weight gradients are joined inside the call: the free-running side stream is covered by tests/test_stream_order_gpu.py
     for i, p in enumerate(module.parameters()):
         if i % 2 == 0:
             p.grad = torch.zeros_like(p)
