@@ -1126,6 +1126,52 @@ int bl_sim_rescore(const float* cx, int64_t ldx, int64_t Q, const float* cy, int
                    const int32_t* cand, int32_t C, int32_t k, int32_t* out_idx, double* out_dot, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Warning grouping (buglab/models/group.py), in csrc/bl_group.hip.  BEYOND THE REFERENCE: it has no counterpart.  The warnings of
+ * a scan are mostly the same few patterns many times; this groups the N site embeddings into the connected components of "cosine
+ * of the centred embeddings >= S" (single linkage at S), so that a reviewer looks at a pattern once.  It is the all-pairs join of
+ * ONE set of rows with itself, an N x N / 2 integer GEMM whose result is never stored: the epilogue decides, re-scores and links
+ * in place.  buglab/models/_group.py is the same arithmetic in NumPy, equal bit for bit on every output.
+ *
+ * Inputs: bl_sim_quantize's outputs for the N rows (centred with their own column mean, or not centred): c float [N, D], q int8
+ * [N, Dp], sumsq and r double [N]; l1_i = sum_d |q_id|, int32 and exact (bl_group_row_l1); S in (0, 1].  The host forms
+ * s2 = S * S and K = ((16 * 16129^2) * s2) * (1 - 2^-40) once, in double, and passes both.
+ *
+ *   edge     for i < j with both rows valid (r > 0): dot = sum_d c_id c_jd in bl_attr_node_scores' column ownership and butterfly
+ *            -- exactly the dot of bl_sim_rescore.  (i, j) is an EDGE iff dot > 0.0 and dot * dot >= s2 * (sumsq_i * sumsq_j):
+ *            three rounded products and one compare, no sqrt and no division.  Two identical rows have dot == sumsq bit for bit,
+ *            so duplicates link at S = 1.
+ *   filter   idot = sum_d q_id q_jd, exact in int32; A = 4 idot + 2 (l1_i + l1_j) + D in int64.  (i, j) is a CANDIDATE iff
+ *            A > 0 and ((double)A * (double)A) * (r_i * r_j) >= K.  A^2 < 2^53, so the square is exact; then two rounded
+ *            products and a compare.  Only candidates are re-scored.  The filter loses no edge: with u = c * 127 / amax and
+ *            q = u + e, |e_d| <= 1/2, u_i . u_j <= idot + (l1_i + l1_j) / 2 + D / 4 = A / 4 and |u_i|^2 = 16129 / r_i, so
+ *            cos >= S implies A / 4 >= S * 16129 / sqrt(r_i r_j); the factor 1 - 2^-40 absorbs every rounding.
+ *   groups   the connected components of the edge graph.  label_i = the smallest row index of i's component; an invalid row is
+ *            its own group.  degree_i = the number of edges at i.  counters = { number of candidates, number of edges }.
+ *            All of them are functions of the input alone: the same whatever the order in which the pairs are visited.
+ *
+ * bl_group_row_l1: q [N, Dp] (contiguous, 16-byte aligned) -> l1 int32 [N].  One wave per row.
+ * bl_group_link: covers the upper triangle of 16 x 16 tiles with v_mfma_i32_16x16x64_i8.  UPDATES parent int32 [N] (the caller
+ *   sets it to the identity first), degree int32 [N] (zeroed first) and counters int64 [2] (zeroed first, 8-byte aligned) with
+ *   vector global atomics; c has row stride ldc and any alignment.  A lock-free union-find: parent[x] <= x always, a root is
+ *   hooked below a smaller root by compare-and-swap, no thread waits for another.  parent is NOT unique (it depends on the order
+ *   of the hooks); the partition it encodes is.  slices in [1, BL_GROUP_MAX_SLICES]: every tile row's range of the triangle is cut
+ *   into that many parts for separate workgroups; the result does not depend on it.
+ * bl_group_labels: parent [N] -> label int32 [N], each row's root; to be called after bl_group_link on the same stream.  An entry
+ *   of parent outside [0, row) ends the walk there, so garbage stays in bounds.
+ * A member's cosine to its group's representative: bl_sim_rescore with cand [N, 1] and k = 1.
+ * BL_EINVAL: null pointers, negative sizes, Dp not D rounded up to a multiple of 64, ldc < D, s2 outside (0, 1] or K outside
+ *   (0, 16 * 16129^2] (NaN included), slices out of range, q not 16-byte aligned, counters not 8-byte aligned.  BL_ERANGE:
+ *   D or Dp > BL_SIM_MAX_D, N > BL_GROUP_MAX_N (the work is N^2 / 2 tile products: DESIGN.md has the time at the cap).
+ * No call synchronises. */
+#define BL_GROUP_MAX_N (1 << 19)
+#define BL_GROUP_MAX_SLICES 64
+int bl_group_row_l1(const int8_t* q, int64_t N, int32_t Dp, int32_t* l1, void* stream);
+int bl_group_link(const int8_t* q, const double* r, const int32_t* l1, const float* c, int64_t ldc, const double* sumsq, int64_t N,
+                  int32_t D, int32_t Dp, double s2, double K, int32_t slices, int32_t* parent, int32_t* degree, int64_t* counters,
+                  void* stream);
+int bl_group_labels(const int32_t* parent, int64_t N, int32_t* label, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Drift detection (buglab/models/drift.py), in csrc/bl_drift.hip.  BEYOND THE REFERENCE: it has no counterpart.  A two-sample
  * permutation test of the kernel maximum mean discrepancy (MMD) between the site embeddings of a reference (a SiteIndex) and
  * those of the data about to be scanned.  buglab/models/_drift.py is the twin: the subsets bit for bit, the sums in fp64.

@@ -215,6 +215,10 @@ _SIGNATURES = {
                           c_void_p, c_void_p], ctypes.c_int),
     "bl_sim_rescore": ([c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int32, c_void_p, c_int32, c_int32, c_void_p,
                         c_void_p, c_void_p], ctypes.c_int),
+    "bl_group_row_l1": ([c_void_p, c_int64, c_int32, c_void_p, c_void_p], ctypes.c_int),
+    "bl_group_link": ([c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int32, c_int32, c_double, c_double, c_int32,
+                       c_void_p, c_void_p, c_void_p, c_void_p], ctypes.c_int),
+    "bl_group_labels": ([c_void_p, c_int64, c_void_p, c_void_p], ctypes.c_int),
     "bl_drift_ok": ([c_int32, c_int64], c_int32),
     "bl_drift_mask_ld": ([c_int64], c_int64),
     "bl_drift_bandwidth_workspace_bytes": ([c_int64, c_int32], c_int64),

@@ -1,5 +1,5 @@
 """Forward-only device services: ensemble combine, self-supervision scoring / sampling, bug reports, evaluation, confidence
-calibration, near-duplicate detection, drift detection."""
+calibration, near-duplicate detection, drift detection, warning grouping."""
 from __future__ import annotations
 
 from typing import Optional, Tuple
@@ -13,6 +13,7 @@ __all__ = ["ENSEMBLE_KINDS", "ENSEMBLE_MAX_MEMBERS", "ensemble_combine", "ens_lo
            "selector_sample", "REPORT_MAX_SAMPLES", "REPORT_INDEX_FIELDS", "report_summarize", "report_order", "EVAL_INDEX_FIELDS", "eval_judge",
            "SUGGEST_MAX_K", "SUGGEST_INDEX_FIELDS", "rank_suggestions", "FDR_MAX_REFERENCE", "fdr_counts", "fdr_bh", "fdr_bh_workspace_bytes", "EXPLAIN_MAX_K", "attribute_node_scores", "attribute_topk",
            "SIM_MAX_D", "SIM_MAX_CANDIDATES", "SIM_MAX_SLICES", "SIM_SITE_MODES", "similar_embed_sites", "similar_quantize", "similar_search", "similar_search_slices", "similar_rescore",
+           "GROUP_MAX_N", "GROUP_MAX_SLICES", "group_thresholds", "group_link_slices", "group_row_l1", "group_link", "group_labels",
            "DRIFT_MAX_D", "DRIFT_MAX_PERMUTATIONS", "drift_ok", "drift_mask_ld", "drift_bandwidth", "drift_subsets", "drift_permutation_sums",
            "BOOTSTRAP_MAX_MODELS", "BOOTSTRAP_MAX_SCOUTS", "bootstrap_counts", "CURVE_MAX_BINS", "CURVE_COUNTERS", "bootstrap_curve_counts", "conf_loc_stats", "conf_group_stats", "conf_apply", "DEDUP_MAX_PERM",
            "DEDUP_EMPTY_SLOT", "_i64", "dedup_sha1_u32", "dedup_minhash", "dedup_lsh_insert_query"]
@@ -528,6 +529,91 @@ def similar_rescore(cx, cy, sumsq_y, cand, k: int) -> Tuple[torch.Tensor, torch.
     _check(load_library().bl_sim_rescore(cx.data_ptr(), _ld(cx, D), Q, cy.data_ptr(), _ld(cy, D), sumsq_y.data_ptr(), N, D, cand.data_ptr(),
                                          C, k, out_idx.data_ptr(), out_dot.data_ptr(), _stream()), "bl_sim_rescore")
     return out_idx, out_dot
+
+
+# ------------------------------------------------------------------------------------------------
+# warning grouping (csrc/bl_group.hip; include/buglab_hip.h::bl_group_row_l1, bl_group_link, bl_group_labels).  Shapes and
+# ranges are checked first (plain ValueErrors, also without a GPU), devices after.
+GROUP_MAX_N = 1 << 19    # BL_GROUP_MAX_N
+GROUP_MAX_SLICES = 64    # BL_GROUP_MAX_SLICES
+
+
+def group_thresholds(similarity: float) -> Tuple[float, float]:
+    """(s2, K) of a similarity S in (0, 1]: s2 = S S and K = ((16 16129^2) s2) (1 - 2^-40), in double, as include/buglab_hip.h
+    states them (buglab/models/_group.py::thresholds is the twin's copy).  ValueError for any other S, NaN included."""
+    S = float(similarity)
+    if not 0.0 < S <= 1.0:
+        raise ValueError(f"group: the similarity must be in (0, 1] (got {similarity})")
+    s2 = S * S
+    return s2, ((16.0 * 16129.0 * 16129.0) * s2) * (1.0 - 2.0 ** -40)
+
+
+def group_link_slices(N: int) -> int:
+    """Into how many parts `group_link` cuts every tile row's range by default.  Two needs, the greater wins: about 8192
+    workgroups, so that the tile rows that hold a large group -- whose pairs are all re-scored -- are spread over the chip; and
+    slices of about 1500 tiles at most, because workgroups are handed out slice by slice, so those running at one time walk the
+    same part of the int8 image and find it in L2 (measured at 524 288 rows: 371 ms with 1 slice, 248 ms with 16).
+    The result does not depend on it."""
+    tiles = max((int(N) + 15) // 16, 1)
+    return max(1, min(GROUP_MAX_SLICES, max(-(-8192 // tiles), tiles // 1536)))
+
+
+def group_row_l1(q) -> torch.Tensor:
+    """q int8 [N, Dp] (`similar_quantize`'s image) -> l1 int32 [N], l1_i = sum_d |q_id|, exact.  Exactly
+    buglab/models/_group.py::row_l1_host.  No sync."""
+    what = "group_row_l1"
+    if q.dim() != 2 or q.shape[1] % 64 or not 64 <= q.shape[1] <= SIM_MAX_D:
+        raise ValueError(f"{what}: q {tuple(q.shape)} must be [N, Dp], Dp a multiple of 64 up to {SIM_MAX_D}")
+    _req(q, torch.int8, "q")
+    l1 = torch.empty(q.shape[0], dtype=torch.int32, device=q.device)
+    _check(load_library().bl_group_row_l1(q.data_ptr(), q.shape[0], q.shape[1], l1.data_ptr(), _stream()), "bl_group_row_l1")
+    return l1
+
+
+def group_link(c, q, sumsq, r, l1, similarity: float, slices: Optional[int] = None
+               ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """The single-linkage join of N rows with themselves at the cosine `similarity` -> (parent int32 [N], degree int32 [N],
+    counters int64 [2] = number of candidates, number of edges).  c float32 [N, D] (any row stride and alignment), q int8 [N, Dp],
+    sumsq / r float64 [N]: `similar_quantize`'s outputs; l1 int32 [N]: `group_row_l1`'s.  parent is a forest with parent[x] <= x
+    whose trees are the groups (`group_labels` gives every row's root, the smallest row of its group); the forest itself depends on
+    the order of the hooks, the groups, the degrees and the counters do not.  `slices`: into how many parts every tile row's range
+    is cut (for tests and tuning; `group_link_slices` when None) -- the result does not depend on it.  Labels, degrees and
+    counters are exactly buglab/models/_group.py::link_host's.  No sync."""
+    what = "group_link"
+    s2, K = group_thresholds(similarity)
+    if c.dim() != 2 or q.dim() != 2 or q.shape[0] != c.shape[0]:
+        raise ValueError(f"{what}: c {tuple(c.shape)} must be [N, D] and q {tuple(q.shape)} [N, Dp]")
+    N, D = c.shape[0], _sim_dim(c.shape[1], what)
+    Dp = (D + 63) // 64 * 64
+    if q.shape[1] != Dp:
+        raise ValueError(f"{what}: q {tuple(q.shape)} must be [{N}, {Dp}]: D = {D} rounded up to a multiple of 64")
+    if N > GROUP_MAX_N:
+        raise ValueError(f"{what}: N = {N} is above {GROUP_MAX_N} rows (the work is N^2 / 2)")
+    if tuple(sumsq.shape) != (N,) or tuple(r.shape) != (N,) or tuple(l1.shape) != (N,):
+        raise ValueError(f"{what}: sumsq {tuple(sumsq.shape)}, r {tuple(r.shape)} and l1 {tuple(l1.shape)} must be [{N}]")
+    S = group_link_slices(N) if slices is None else int(slices)
+    if not 1 <= S <= GROUP_MAX_SLICES:
+        raise ValueError(f"{what}: slices must be in [1, {GROUP_MAX_SLICES}] (got {slices})")
+    _req(q, torch.int8, "q"), _f64(sumsq, "sumsq"), _f64(r, "r"), _i32(l1, "l1")
+    if N:
+        _rows_f32(c, "c", what)
+    parent = torch.arange(N, dtype=torch.int32, device=q.device)
+    degree = torch.zeros(N, dtype=torch.int32, device=q.device)
+    counters = torch.zeros(2, dtype=torch.int64, device=q.device)
+    _check(load_library().bl_group_link(q.data_ptr(), r.data_ptr(), l1.data_ptr(), c.data_ptr(), _ld(c, D), sumsq.data_ptr(), N, D, Dp, s2, K,
+                                        S, parent.data_ptr(), degree.data_ptr(), counters.data_ptr(), _stream()), "bl_group_link")
+    return parent, degree, counters
+
+
+def group_labels(parent) -> torch.Tensor:
+    """parent int32 [N] (`group_link`'s) -> label int32 [N]: every row's root, the smallest row of its group.  Exactly
+    buglab/models/_group.py::labels_host.  No sync."""
+    if parent.dim() != 1 or parent.shape[0] > GROUP_MAX_N:
+        raise ValueError(f"group_labels: parent {tuple(parent.shape)} must be [N], N up to {GROUP_MAX_N}")
+    _i32(parent, "parent")
+    label = torch.empty_like(parent)
+    _check(load_library().bl_group_labels(parent.data_ptr(), parent.shape[0], label.data_ptr(), _stream()), "bl_group_labels")
+    return label
 
 
 # ------------------------------------------------------------------------------------------------
