@@ -1233,6 +1233,49 @@ int bl_drift_permutation_sums(const float* z, int64_t ldz, int64_t N, int64_t n,
                               int64_t workspace_bytes, double* out_sums, double* out_u0, double* out_rho, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Warning triage (buglab/models/triage.py), in csrc/bl_triage.hip.  BEYOND THE REFERENCE: it has no counterpart.  A ridge-
+ * regularised logistic re-ranker fitted on a reviewer's verdicts (1 = accepted, 0 = dismissed), over the site embedding and the
+ * site's location log-probability that bl_sim_embed_sites writes.  The fit is Newton's method on the host (buglab/models/
+ * _triage.py::fit_logistic); the device forms the statistics of one iteration over all N labelled rows and, once fitted, scores
+ * the rows of a scan.  buglab/models/_triage.py is the twin: the margins bit for bit, the sums in fp64.
+ *
+ *   features   P = D + 2.  phi_c = ((double)x_c - shift_c) * scale_c for c < D; phi_D = ((double)logprob - shift_D) * scale_D;
+ *              phi_{D+1} = 1, the intercept.  shift, scale double [D + 1]: the host's, computed once (a constant column has
+ *              scale 0).  w double [P].
+ *   margin     z = sum_c w_c phi_c by ONE wave: columns in quads, lane l owns the quads q with q % 64 == l (the ownership of
+ *              bl_attr_node_scores) and adds the ROUNDED products w_c * phi_c in ascending column order to its own sum, which
+ *              starts at +0.0; the 64 sums go through the xor butterfly, strides 32 .. 1.
+ *   row        e = exp(-|z|), d = 1 + e; (p, 1 - p) = (1 / d, e / d) for z >= 0 and (e / d, 1 / d) otherwise;
+ *              s = c (p (1 - p)); r = -(c (1 - p)) for y != 0 and c p otherwise; loss = c (softplus(z) - y z), formed as
+ *              c (max(u, 0) + log1p(e)) with u = -z for y != 0 and z otherwise: the same number without the difference of two
+ *              large ones.  Nothing overflows: at |z| = 800 the loss is finite and s is exactly 0.
+ *   sums       L = sum loss + (lambda / 2) sum_{c <= D} w_c^2;  g = sum_n r_n phi_n + lambda w~;
+ *              H = sum_n (s_n phi_n) phi_n^T + lambda I~  (w~, I~: the intercept left out).
+ *   skipped    a row with a non-finite entry in x or logprob is in no sum; it is counted.
+ *
+ * bl_triage_newton_stats: x float [N, D] (row stride ldx; 16-byte alignment with ldx % 4 == 0 only buys wider loads), logprob
+ *   float [N], y uint8 [N], c double [N] >= 0 or NULL for all ones, lambda > 0 -> H double [P, P], both triangles and H == H^T bit
+ *   for bit; g double [P]; scalars double [4] = L, sum of c over the rows used, rows used, rows skipped.  The Gram matrix runs on
+ *   v_mfma_f64_16x16x4_f64 over the 16 x 16 tiles of the lower triangle, the embeddings widened in registers.  The rows are cut
+ *   into S = min(BL_TRIAGE_MAX_SLICES, max(1, ceil(N / 128))) slices of ceil(N / S) rows rounded up to a multiple of 4; every
+ *   slice's partial H and g go to the workspace and a last kernel adds them in slice order.  No atomics: the same bits on every
+ *   run.  workspace: bl_triage_workspace_bytes(N, D) bytes (-1 for sizes the kernels do not take), 8-byte aligned, contents
+ *   irrelevant.  Four launches, no synchronisation.  N == 0: BL_OK, zeros in the outputs that are not NULL, nothing launched.
+ * bl_triage_score: the same rows and w -> margin double [N], prob double [N] = p; NaN in both for a skipped row.  One wave per
+ *   row, the dot product above.
+ * BL_EINVAL: null pointers, negative sizes, ldx < D, doubles not 8-byte or floats not 4-byte aligned, lambda <= 0, NaN or
+ *   infinite, a workspace too small (the text names the size needed).  BL_ERANGE: D > BL_TRIAGE_MAX_D, N > 2^36.  All of it is
+ *   checked before the first HIP call. */
+#define BL_TRIAGE_MAX_D 512
+#define BL_TRIAGE_MAX_SLICES 64
+int64_t bl_triage_workspace_bytes(int64_t N, int32_t D);
+int bl_triage_newton_stats(const float* x, int64_t ldx, const float* logprob, const double* shift, const double* scale, const double* w,
+                           const uint8_t* y, const double* c, int64_t N, int32_t D, double lambda, void* workspace,
+                           int64_t workspace_bytes, double* H, double* g, double* scalars, void* stream);
+int bl_triage_score(const float* x, int64_t ldx, const float* logprob, const double* shift, const double* scale, const double* w,
+                    int64_t N, int32_t D, double* margin, double* prob, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Confidence calibration (buglab/models/calibrate.py), in csrc/bl_confidence.hip.  BEYOND THE REFERENCE: it has no
  * counterpart; what is calibrated is the confidence its evaluate.py:60-140 thresholds and its visualize.py ranks by.  One
  * inverse temperature beta and a NO_BUG bias rescale the localization distribution, one repair_beta the repair groups:

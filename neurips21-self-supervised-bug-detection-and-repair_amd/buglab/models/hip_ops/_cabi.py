@@ -227,6 +227,11 @@ _SIGNATURES = {
     "bl_drift_sums_workspace_bytes": ([c_int64, c_int64], c_int64),
     "bl_drift_permutation_sums": ([c_void_p, c_int64, c_int64, c_int64, c_int32, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_double,
                                    c_int32, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p], ctypes.c_int),
+    "bl_triage_workspace_bytes": ([c_int64, c_int32], c_int64),
+    "bl_triage_newton_stats": ([c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_double,
+                                c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p], ctypes.c_int),
+    "bl_triage_score": ([c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_void_p],
+                        ctypes.c_int),
     "bl_attr_node_scores": ([c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int32, c_double, c_int32, c_void_p, c_void_p], ctypes.c_int),
     "bl_attr_topk": ([c_void_p, c_void_p, c_int32, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p],
                      ctypes.c_int),

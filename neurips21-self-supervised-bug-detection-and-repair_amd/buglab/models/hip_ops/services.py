@@ -1,5 +1,5 @@
 """Forward-only device services: ensemble combine, self-supervision scoring / sampling, bug reports, evaluation, confidence
-calibration, near-duplicate detection, drift detection, warning grouping."""
+calibration, near-duplicate detection, drift detection, warning grouping, warning triage."""
 from __future__ import annotations
 
 from typing import Optional, Tuple
@@ -14,6 +14,7 @@ __all__ = ["ENSEMBLE_KINDS", "ENSEMBLE_MAX_MEMBERS", "ensemble_combine", "ens_lo
            "SUGGEST_MAX_K", "SUGGEST_INDEX_FIELDS", "rank_suggestions", "FDR_MAX_REFERENCE", "fdr_counts", "fdr_bh", "fdr_bh_workspace_bytes", "EXPLAIN_MAX_K", "attribute_node_scores", "attribute_topk",
            "SIM_MAX_D", "SIM_MAX_CANDIDATES", "SIM_MAX_SLICES", "SIM_SITE_MODES", "similar_embed_sites", "similar_quantize", "similar_search", "similar_search_slices", "similar_rescore",
            "GROUP_MAX_N", "GROUP_MAX_SLICES", "group_thresholds", "group_link_slices", "group_row_l1", "group_link", "group_labels",
+           "TRIAGE_MAX_D", "TRIAGE_MAX_SLICES", "triage_slices", "triage_workspace_bytes", "triage_newton_stats", "triage_score",
            "DRIFT_MAX_D", "DRIFT_MAX_PERMUTATIONS", "drift_ok", "drift_mask_ld", "drift_bandwidth", "drift_subsets", "drift_permutation_sums",
            "BOOTSTRAP_MAX_MODELS", "BOOTSTRAP_MAX_SCOUTS", "bootstrap_counts", "CURVE_MAX_BINS", "CURVE_COUNTERS", "bootstrap_curve_counts", "conf_loc_stats", "conf_group_stats", "conf_apply", "DEDUP_MAX_PERM",
            "DEDUP_EMPTY_SLOT", "_i64", "dedup_sha1_u32", "dedup_minhash", "dedup_lsh_insert_query"]
@@ -724,6 +725,100 @@ def drift_permutation_sums(z, rownorm, mask, n: int, bandwidth, shift: float = 0
                                          bandwidth.data_ptr(), shift, ct, workspace.data_ptr(), need, sums.data_ptr(), u0.data_ptr(),
                                          rho.data_ptr(), _stream()), "bl_drift_permutation_sums")
     return sums, u0, rho
+
+
+# ------------------------------------------------------------------------------------------------
+# warning triage (csrc/bl_triage.hip; include/buglab_hip.h::bl_triage_newton_stats, bl_triage_score).  Shapes and ranges are
+# checked first (plain ValueErrors, also without a GPU), devices after.
+TRIAGE_MAX_D = 512       # BL_TRIAGE_MAX_D
+TRIAGE_MAX_SLICES = 64   # BL_TRIAGE_MAX_SLICES
+
+
+def triage_slices(N: int) -> Tuple[int, int]:
+    """(number of row slices, rows per slice) of `triage_newton_stats` over N rows, as include/buglab_hip.h states them
+    (restated: no library needed).  A function of N alone; the last slice is the ragged one."""
+    N = int(N)
+    S = max(1, min(TRIAGE_MAX_SLICES, -(-N // 128)))
+    return S, (-(-N // S) + 3) // 4 * 4
+
+
+def triage_workspace_bytes(N: int, D: int) -> int:
+    """The bytes of workspace `triage_newton_stats` needs for N rows of size D (bl_triage_workspace_bytes)."""
+    if int(N) < 0 or not 1 <= int(D) <= TRIAGE_MAX_D:
+        raise ValueError(f"triage_workspace_bytes: need N >= 0 and 1 <= D <= {TRIAGE_MAX_D} (got N {N}, D {D})")
+    return int(load_library().bl_triage_workspace_bytes(int(N), int(D)))
+
+
+def _triage_rows(what: str, x, logprob, shift, scale, w) -> Tuple[int, int]:
+    if x.dim() != 2 or not 1 <= x.shape[1] <= TRIAGE_MAX_D:
+        raise ValueError(f"{what}: x {tuple(x.shape)} must be [N, 1 <= D <= {TRIAGE_MAX_D}]")
+    N, D = x.shape
+    if tuple(logprob.shape) != (N,) or tuple(shift.shape) != (D + 1,) or tuple(scale.shape) != (D + 1,) or tuple(w.shape) != (D + 2,):
+        raise ValueError(f"{what}: logprob {tuple(logprob.shape)} must be [{N}], shift {tuple(shift.shape)} and scale "
+                         f"{tuple(scale.shape)} [{D + 1}] and w {tuple(w.shape)} [{D + 2}]")
+    return N, D
+
+
+def _triage_on_device(what: str, x, logprob, shift, scale, w) -> None:
+    if x.shape[0]:
+        _rows_f32(x, "x", what)
+    _f32(logprob, "logprob"), _f64(shift, "shift"), _f64(scale, "scale"), _f64(w, "w")
+
+
+def triage_newton_stats(x, logprob, shift, scale, w, y, c, l2: float, *, workspace=None, out=None) -> torch.Tensor:
+    """The Newton statistics of the ridge-regularised logistic loss at w over N labelled rows -> ONE float64 buffer [P P + P + 4],
+    P = D + 2: H [P, P] | g [P] | L, sum of c over the rows used, rows used, rows skipped -- one device->host copy for the
+    caller.  x float32 [N, D] (any row stride and alignment), logprob float32 [N], shift / scale float64 [D + 1], w float64 [P],
+    y uint8 [N], c float64 [N] >= 0 or None for all ones, l2 > 0.  `workspace`: a float64 tensor of at least
+    triage_workspace_bytes(N, D) bytes to reuse across calls; `out`: the caller's buffer to fill.  H == H^T bit for bit and every
+    number has the same bits on every run.  Twin: buglab/models/_triage.py::newton_stats_host (margins bit for bit).  No sync."""
+    what = "triage_newton_stats"
+    N, D = _triage_rows(what, x, logprob, shift, scale, w)
+    P = D + 2
+    l2 = float(l2)
+    if not 0.0 < l2 < float("inf"):
+        raise ValueError(f"{what}: l2 must be positive and finite (got {l2})")
+    if tuple(y.shape) != (N,) or (c is not None and tuple(c.shape) != (N,)):
+        raise ValueError(f"{what}: y {tuple(y.shape)} and c must be [{N}]")
+    _triage_on_device(what, x, logprob, shift, scale, w)
+    _req(y, torch.uint8, "y")
+    if c is not None:
+        _f64(c, "c")
+    if out is None:
+        out = torch.empty(P * P + P + 4, dtype=torch.float64, device=x.device)
+    elif tuple(out.shape) != (P * P + P + 4,):
+        raise ValueError(f"{what}: out {tuple(out.shape)} must be [{P * P + P + 4}]")
+    _f64(out, "out")
+    if N == 0:
+        return out.zero_()
+    lib = load_library()
+    need = int(lib.bl_triage_workspace_bytes(N, D))
+    if workspace is None:
+        workspace = torch.empty(need // 8, dtype=torch.float64, device=x.device)
+    _f64(workspace, "workspace")
+    base = out.data_ptr()
+    _check(lib.bl_triage_newton_stats(x.data_ptr(), _ld(x, D), logprob.data_ptr(), shift.data_ptr(), scale.data_ptr(), w.data_ptr(),
+                                      y.data_ptr(), _p(c), N, D, l2, workspace.data_ptr(), workspace.numel() * 8, base, base + 8 * P * P,
+                                      base + 8 * (P * P + P), _stream()), "bl_triage_newton_stats")
+    return out
+
+
+def triage_score(x, logprob, shift, scale, w, out=None) -> torch.Tensor:
+    """The margins and probabilities of N rows under w -> float64 [2, N]: row 0 the margin z, row 1 p = sigmoid(z); NaN in both
+    for a row with a non-finite entry.  Operands as `triage_newton_stats`.  The margins are exactly
+    buglab/models/_triage.py::score_host's.  No sync."""
+    what = "triage_score"
+    N, D = _triage_rows(what, x, logprob, shift, scale, w)
+    _triage_on_device(what, x, logprob, shift, scale, w)
+    if out is None:
+        out = torch.empty((2, N), dtype=torch.float64, device=x.device)
+    elif tuple(out.shape) != (2, N):
+        raise ValueError(f"{what}: out {tuple(out.shape)} must be [2, {N}]")
+    _f64(out, "out")
+    if N:
+        _check(load_library().bl_triage_score(x.data_ptr(), _ld(x, D), logprob.data_ptr(), shift.data_ptr(), scale.data_ptr(), w.data_ptr(),
+                                              N, D, out.data_ptr(), out.data_ptr() + 8 * N, _stream()), "bl_triage_score")
+    return out
 
 
 # ------------------------------------------------------------------------------------------------
