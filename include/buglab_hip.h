@@ -1276,6 +1276,73 @@ int bl_triage_score(const float* x, int64_t ldx, const float* logprob, const dou
                     int64_t N, int32_t D, double* margin, double* prob, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Review queue (buglab/models/review.py), in csrc/bl_review.hip.  BEYOND THE REFERENCE: it has no counterpart.  Given a budget
+ * of B reviews and what was reviewed already, pick the B warnings that cover the scan best: each pick is the warning least like
+ * everything reviewed or queued so far.  This is k-center greedy, or farthest-point selection (Gonzalez 1985; the core-set
+ * selection of Sener & Savarese 2018).  buglab/models/_review.py is the same arithmetic in NumPy, equal bit for bit on every
+ * output: picks, pick affinities, final best and near.
+ *
+ * All M rows live in ONE row space: first the L reviewed rows, then the N candidate rows.  The rows are bl_sim_quantize's int8
+ * images q [M, Dp] (Dp = D rounded up to a multiple of 64, padding columns zero) with their r; r_i > 0 means the row is valid.
+ * Selection runs on the images, where dot products are exact integers.
+ *
+ *   norm       n_i = sum_d q_id^2, int32 and exact, at most 512 * 127^2 = 8 258 048.  0 for an invalid row (its image is zero); a
+ *              valid row has an entry +-127, so n_i >= 16129.
+ *   affinity   a(i, j) = (double)(idot * |idot|) / (double)(n_i * n_j), idot = sum_d q_id q_jd.  Both products are formed in
+ *              int64 and stay below 2^53, so both conversions are exact; the result is ONE IEEE quotient.  It is the signed
+ *              squared cosine of the images, and a(i, i) == 1.0.  The affinity is monotone in the angle, and min, max and argmin
+ *              commute with monotone maps: the picks are those of farthest-point selection on the angular metric.  No sqrt and
+ *              no exp runs on the device.
+ *   cover      per row: best_i double, -2.0 meaning "no centre yet"; near_i int32, -1 meaning none.  Applying a centre j to a
+ *              valid row i: if a(i, j) > best_i, then best_i = a(i, j) and near_i = j.  For a SET of centres the result is
+ *              (greater affinity, then lower centre index), and bl_review_cover_i8 combines with the caller's state in that same
+ *              total order; an invalid centre covers nothing, an invalid row is left as it is.  A queued pick never displaces
+ *              an equal earlier centre, because the comparison is strict.
+ *   pick       among the rows with eligible_i != 0, n_i > 0 and best_i < stop, the one with the lowest best_i; ties go to the
+ *              lowest index.  stop = S * S for a greatest similarity S in (0, 1].  If there is no such row the queue has ENDED:
+ *              this pick and all later ones are -1 (affinity 0.0) and the state is left as it is.  Otherwise (s, best_s) is
+ *              recorded and centre s applied to every valid row; row s itself gets best = 1.0, near = s by that same rule
+ *              (best_s < stop <= 1 == a(s, s)), so it cannot be picked again.
+ * Nothing in the arithmetic depends on a launch geometry.
+ *
+ * Image operands have a row stride (ldq, ldc): a multiple of 16, at least Dp, the base 16-byte aligned.
+ * bl_review_norms: q -> n int32 [M].  One wave per row, the packed int8 dot.
+ * bl_review_cover_i8: applies the L centres qc / nc (centre j has the index first_id + j) to the M rows q / n and UPDATES best
+ *   double [M] and near int32 [M].  An M x L int8 GEMM on v_mfma_i32_16x16x64_i8 that is never stored: the epilogue turns each
+ *   accumulator into an affinity in registers and keeps a running (best, near) per row.  slices in [1, BL_REVIEW_MAX_SLICES]:
+ *   the centres are cut into that many parts for separate workgroups; the result does not depend on it.  Calling it twice over
+ *   two parts of the centres equals calling it once with all of them.  No atomics.  workspace:
+ *   bl_review_cover_workspace_bytes(M, slices) bytes (-1 for sizes the kernels do not take), 8-byte aligned, contents irrelevant.
+ *   Two launches.
+ * bl_review_greedy: B picks from the state (best, near), which it UPDATES -> picks int32 [B], pick_aff double [B] and pick_near
+ *   int32 [B]: (best_s, near_s) at the time of the pick, the nearest earlier item (0.0 and -1 for no pick; -2.0 and -1 for a pick
+ *   that no centre covered).  eligible uint8 [M] or NULL for all.  ONE call enqueues the whole chain, B + 1 launches of one step kernel,
+ *   with no host synchronisation and no communication between workgroups inside a launch: every workgroup reduces the per-
+ *   workgroup partials (best, index) of the launch before, all arrive at the same winner, each updates its own rows and writes its
+ *   own partial into the other of two buffers.  blocks: the number of workgroups, 0 for bl_review_blocks(M) =
+ *   min(BL_REVIEW_MAX_BLOCKS, ceil(M / BL_REVIEW_ROWS_PER_BLOCK)), a function of M alone; the results are the same for every
+ *   value.  workspace: bl_review_workspace_bytes(M) bytes (-1 for M out of range), 8-byte aligned, contents irrelevant.
+ * BL_EINVAL: null pointers, negative sizes, Dp not a multiple of 64, a row stride below Dp or not a multiple of 16, images not
+ *   16-byte aligned, doubles not 8-byte aligned, stop outside (0, 1] (NaN included), slices or blocks out of range, a workspace too
+ *   small.  BL_ERANGE: Dp > BL_SIM_MAX_D, M or L > BL_REVIEW_MAX_ROWS, B > BL_REVIEW_MAX_BUDGET.  All of it is checked before the
+ *   first launch.  No call synchronises. */
+#define BL_REVIEW_MAX_ROWS (1 << 20)
+#define BL_REVIEW_MAX_BUDGET 16384
+#define BL_REVIEW_MAX_SLICES 64
+#define BL_REVIEW_MAX_BLOCKS 1024
+#define BL_REVIEW_ROWS_PER_BLOCK 64
+int bl_review_norms(const int8_t* q, int64_t ldq, int64_t M, int32_t Dp, int32_t* n, void* stream);
+int64_t bl_review_cover_workspace_bytes(int64_t M, int32_t slices);
+int bl_review_cover_i8(const int8_t* q, int64_t ldq, const int32_t* n, int64_t M, const int8_t* qc, int64_t ldc, const int32_t* nc,
+                       int64_t L, int32_t first_id, int32_t Dp, int32_t slices, void* workspace, int64_t workspace_bytes, double* best,
+                       int32_t* near, void* stream);
+int32_t bl_review_blocks(int64_t M);
+int64_t bl_review_workspace_bytes(int64_t M);
+int bl_review_greedy(const int8_t* q, int64_t ldq, const int32_t* n, const uint8_t* eligible, int64_t M, int32_t Dp, int32_t B,
+                     double stop, int32_t blocks, void* workspace, int64_t workspace_bytes, double* best, int32_t* near,
+                     int32_t* picks, double* pick_aff, int32_t* pick_near, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Confidence calibration (buglab/models/calibrate.py), in csrc/bl_confidence.hip.  BEYOND THE REFERENCE: it has no
  * counterpart; what is calibrated is the confidence its evaluate.py:60-140 thresholds and its visualize.py ranks by.  One
  * inverse temperature beta and a NO_BUG bias rescale the localization distribution, one repair_beta the repair groups:

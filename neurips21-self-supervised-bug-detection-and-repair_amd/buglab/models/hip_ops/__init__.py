@@ -15,7 +15,8 @@ This file is a facade: the code lives in the modules below and callers keep usin
   gemm       raw GEMM and row-wise entry points        weights   packed / transposed weight copies
   graph      message-passing layers, notifications     linear    gathered Linear, row dot, dropout
   heads      scoring heads and losses                  seq       attention, GRU scan, one-call GREAT layer
-  services   ensemble, self-supervision, reports, evaluation, suggestions, FDR, calibration, dedup, drift, grouping, triage
+  services   ensemble, self-supervision, reports, evaluation, suggestions, FDR, calibration, dedup, drift, grouping, triage,
+             review queues
   optim      clip + Adam on flat buffers               runtime   library-wide modes
 """
 from __future__ import annotations

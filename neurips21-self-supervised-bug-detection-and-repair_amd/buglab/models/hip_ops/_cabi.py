@@ -232,6 +232,14 @@ _SIGNATURES = {
                                 c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p], ctypes.c_int),
     "bl_triage_score": ([c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_void_p],
                         ctypes.c_int),
+    "bl_review_norms": ([c_void_p, c_int64, c_int64, c_int32, c_void_p, c_void_p], ctypes.c_int),
+    "bl_review_cover_workspace_bytes": ([c_int64, c_int32], c_int64),
+    "bl_review_cover_i8": ([c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int32, c_int32, c_int32, c_void_p,
+                            c_int64, c_void_p, c_void_p, c_void_p], ctypes.c_int),
+    "bl_review_blocks": ([c_int64], c_int32),
+    "bl_review_workspace_bytes": ([c_int64], c_int64),
+    "bl_review_greedy": ([c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int32, c_int32, c_double, c_int32, c_void_p, c_int64, c_void_p,
+                          c_void_p, c_void_p, c_void_p, c_void_p, c_void_p], ctypes.c_int),
     "bl_attr_node_scores": ([c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int32, c_double, c_int32, c_void_p, c_void_p], ctypes.c_int),
     "bl_attr_topk": ([c_void_p, c_void_p, c_int32, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p],
                      ctypes.c_int),

@@ -1,12 +1,12 @@
 """Forward-only device services: ensemble combine, self-supervision scoring / sampling, bug reports, evaluation, confidence
-calibration, near-duplicate detection, drift detection, warning grouping, warning triage."""
+calibration, near-duplicate detection, drift detection, warning grouping, warning triage, review queues."""
 from __future__ import annotations
 
 from typing import Optional, Tuple
 
 import torch
 
-from ._cabi import _check, _f32, _i32, load_library, _p, _req, _stream
+from ._cabi import HipOpsUnavailable, _check, _f32, _i32, load_library, _p, _req, _stream
 
 __all__ = ["ENSEMBLE_KINDS", "ENSEMBLE_MAX_MEMBERS", "ensemble_combine", "ens_loc_stats", "ens_rw_stats", "ensemble_combine_weighted",
            "SELECTOR_MAX_K", "_f64", "score_targets",
@@ -15,6 +15,8 @@ __all__ = ["ENSEMBLE_KINDS", "ENSEMBLE_MAX_MEMBERS", "ensemble_combine", "ens_lo
            "SIM_MAX_D", "SIM_MAX_CANDIDATES", "SIM_MAX_SLICES", "SIM_SITE_MODES", "similar_embed_sites", "similar_quantize", "similar_search", "similar_search_slices", "similar_rescore",
            "GROUP_MAX_N", "GROUP_MAX_SLICES", "group_thresholds", "group_link_slices", "group_row_l1", "group_link", "group_labels",
            "TRIAGE_MAX_D", "TRIAGE_MAX_SLICES", "triage_slices", "triage_workspace_bytes", "triage_newton_stats", "triage_score",
+           "REVIEW_MAX_ROWS", "REVIEW_MAX_BUDGET", "REVIEW_MAX_SLICES", "REVIEW_MAX_BLOCKS", "REVIEW_ROWS_PER_BLOCK", "review_blocks",
+           "review_workspace_bytes", "review_cover_slices", "review_norms", "review_cover", "review_greedy",
            "DRIFT_MAX_D", "DRIFT_MAX_PERMUTATIONS", "drift_ok", "drift_mask_ld", "drift_bandwidth", "drift_subsets", "drift_permutation_sums",
            "BOOTSTRAP_MAX_MODELS", "BOOTSTRAP_MAX_SCOUTS", "bootstrap_counts", "CURVE_MAX_BINS", "CURVE_COUNTERS", "bootstrap_curve_counts", "conf_loc_stats", "conf_group_stats", "conf_apply", "DEDUP_MAX_PERM",
            "DEDUP_EMPTY_SLOT", "_i64", "dedup_sha1_u32", "dedup_minhash", "dedup_lsh_insert_query"]
@@ -819,6 +821,157 @@ def triage_score(x, logprob, shift, scale, w, out=None) -> torch.Tensor:
         _check(load_library().bl_triage_score(x.data_ptr(), _ld(x, D), logprob.data_ptr(), shift.data_ptr(), scale.data_ptr(), w.data_ptr(),
                                               N, D, out.data_ptr(), out.data_ptr() + 8 * N, _stream()), "bl_triage_score")
     return out
+
+
+# ------------------------------------------------------------------------------------------------
+# review queues (csrc/bl_review.hip; include/buglab_hip.h::bl_review_norms, bl_review_cover_i8, bl_review_greedy).  Shapes and
+# ranges are checked first (plain ValueErrors, also without a GPU), devices after.
+REVIEW_MAX_ROWS = 1 << 20      # BL_REVIEW_MAX_ROWS
+REVIEW_MAX_BUDGET = 16384      # BL_REVIEW_MAX_BUDGET
+REVIEW_MAX_SLICES = 64         # BL_REVIEW_MAX_SLICES
+REVIEW_MAX_BLOCKS = 1024       # BL_REVIEW_MAX_BLOCKS
+REVIEW_ROWS_PER_BLOCK = 64     # BL_REVIEW_ROWS_PER_BLOCK
+
+
+def review_blocks(M: int) -> int:
+    """The number of workgroups of a `review_greedy` step over M rows by default, as include/buglab_hip.h states it (restated: no
+    library needed): one per 64 rows -- a pass of the step kernel, four lanes per row -- up to 1024, beyond which every workgroup
+    takes more passes over a contiguous part of the rows.  A function of M alone; the results do not depend on it."""
+    return max(1, min(REVIEW_MAX_BLOCKS, -(-int(M) // REVIEW_ROWS_PER_BLOCK)))
+
+
+def review_workspace_bytes(M: int) -> int:
+    """The bytes of workspace `review_greedy` needs for M rows (bl_review_workspace_bytes): a control word and two sets of
+    per-workgroup partials."""
+    if not 0 <= int(M) <= REVIEW_MAX_ROWS:
+        raise ValueError(f"review_workspace_bytes: M must be in [0, {REVIEW_MAX_ROWS}] (got {M})")
+    return int(load_library().bl_review_workspace_bytes(int(M)))
+
+
+def review_cover_slices(M: int, L: int) -> int:
+    """Into how many parts `review_cover` cuts the centres by default: enough workgroups (ceil(M / 16) x S) to fill the chip when
+    the rows are few, and no slice shorter than 1024 centres, because every slice ends in a combine whose cost does not depend
+    on its length.  The result does not depend on it."""
+    tiles = max((int(M) + 15) // 16, 1)
+    return max(1, min(REVIEW_MAX_SLICES, 2048 // tiles, int(L) // 1024))
+
+
+def _review_image(t, name: str, what: str) -> Tuple[int, int]:
+    """(rows, row stride) of an int8 image [rows, Dp]: Dp a multiple of 64 up to 512, unit column stride, a row stride that is a
+    multiple of 16"""
+    if t.dim() != 2 or t.shape[1] % 64 or not 64 <= t.shape[1] <= SIM_MAX_D:
+        raise ValueError(f"{what}: {name} {tuple(t.shape)} must be [rows, Dp], Dp a multiple of 64 up to {SIM_MAX_D}")
+    if t.shape[0] > REVIEW_MAX_ROWS:
+        raise ValueError(f"{what}: {name} has {t.shape[0]} rows, above {REVIEW_MAX_ROWS}")
+    ld = _ld(t, t.shape[1])
+    if t.dtype != torch.int8 or t.stride(1) != 1 or ld % 16 or ld < t.shape[1]:
+        raise ValueError(f"{what}: {name} must be int8 with unit column stride and a row stride that is a multiple of 16 (got {t.dtype}, "
+                         f"strides {tuple(t.stride())})")
+    if not t.is_cuda:
+        raise HipOpsUnavailable(f"{what}: {name} is on {t.device}; the BugLab hot path only runs on a ROCm GPU (no CPU fallback)")
+    return t.shape[0], ld
+
+
+def review_norms(q) -> torch.Tensor:
+    """q int8 [M, Dp] (`similar_quantize`'s image; any row stride that is a multiple of 16) -> n int32 [M], n_i = sum_d q_id^2,
+    exact; 0 marks an invalid row.  Exactly buglab/models/_review.py::norms_host.  No sync."""
+    M, ld = _review_image(q, "q", "review_norms")
+    n = torch.empty(M, dtype=torch.int32, device=q.device)
+    _check(load_library().bl_review_norms(q.data_ptr(), ld, M, q.shape[1], n.data_ptr(), _stream()), "bl_review_norms")
+    return n
+
+
+def _review_state(what: str, M: int, n, best, near, device):
+    if tuple(n.shape) != (M,):
+        raise ValueError(f"{what}: n {tuple(n.shape)} must be [{M}]")
+    if (best is None) != (near is None):
+        raise ValueError(f"{what}: best and near come together")
+    if best is None:
+        best = torch.full((M,), -2.0, dtype=torch.float64, device=device)
+        near = torch.full((M,), -1, dtype=torch.int32, device=device)
+    elif tuple(best.shape) != (M,) or tuple(near.shape) != (M,):
+        raise ValueError(f"{what}: best {tuple(best.shape)} and near {tuple(near.shape)} must be [{M}]")
+    _i32(n, "n"), _f64(best, "best"), _i32(near, "near")
+    return best, near
+
+
+def review_cover(q, n, centres_q, centres_n, best=None, near=None, *, first_id: int = 0, slices: Optional[int] = None
+                 ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Applies L centres to M rows -> (best float64 [M], near int32 [M]): per valid row the greatest affinity to a centre and that
+    centre's index, the lower index among equals; -2.0 / -1 where nothing covers.  q int8 [M, Dp] / n int32 [M]: the rows
+    (`similar_quantize`'s image, `review_norms`' norms); centres_q int8 [L, Dp] / centres_n int32 [L]: the centres, centre j
+    carrying the index first_id + j.  `best` / `near`: a state to UPDATE in place (and return) instead of a fresh one -- two
+    calls over two parts of the centres equal one call over all.  `slices`: into how many parts the centres are cut (for tests
+    and tuning; `review_cover_slices` when None) -- the result does not depend on it.  Exactly
+    buglab/models/_review.py::cover_host.  No sync."""
+    what = "review_cover"
+    if q.dim() != 2 or centres_q.dim() != 2 or q.shape[1] != centres_q.shape[1]:
+        raise ValueError(f"{what}: q {tuple(q.shape)} and centres_q {tuple(centres_q.shape)} must be [M, Dp] and [L, Dp]")
+    S = review_cover_slices(q.shape[0], centres_q.shape[0]) if slices is None else int(slices)
+    if not 1 <= S <= REVIEW_MAX_SLICES:
+        raise ValueError(f"{what}: slices must be in [1, {REVIEW_MAX_SLICES}] (got {slices})")
+    first_id = int(first_id)
+    if first_id < 0 or first_id + centres_q.shape[0] > 0x7FFFFFFF:
+        raise ValueError(f"{what}: the centre indices {first_id} .. {first_id + centres_q.shape[0]} leave int32")
+    if tuple(centres_n.shape) != (centres_q.shape[0],):
+        raise ValueError(f"{what}: centres_n {tuple(centres_n.shape)} must be [{centres_q.shape[0]}]")
+    M, ldq = _review_image(q, "q", what)
+    L, ldc = _review_image(centres_q, "centres_q", what)
+    best, near = _review_state(what, M, n, best, near, q.device)
+    _i32(centres_n, "centres_n")
+    lib = load_library()
+    need = int(lib.bl_review_cover_workspace_bytes(M, S))
+    workspace = torch.empty(max((need + 7) // 8, 1), dtype=torch.float64, device=q.device)
+    _check(lib.bl_review_cover_i8(q.data_ptr(), ldq, n.data_ptr(), M, centres_q.data_ptr(), ldc, centres_n.data_ptr(), L, first_id,
+                                  q.shape[1], S, workspace.data_ptr(), workspace.numel() * 8, best.data_ptr(), near.data_ptr(), _stream()),
+           "bl_review_cover_i8")
+    return best, near
+
+
+def review_greedy(q, n, best, near, budget: int, *, eligible=None, stop: float = 1.0, blocks: Optional[int] = None, workspace=None
+                  ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """`budget` k-center greedy picks from the cover state -> (picks int32 [B], -1 once the queue has ended; pick_affinity float64
+    [B] and pick_near int32 [B]: the pick's `best` and `near` when it was taken, its nearest earlier item; 0.0 and -1 for no
+    pick).  UPDATES best float64 [M] / near int32 [M] in place (-2.0 / -1:
+    no centre yet): every pick is applied as a centre to every valid row.  q int8 [M, Dp] / n int32 [M] as in `review_cover`;
+    eligible uint8 [M] or None for all; stop = S S for a greatest similarity S in (0, 1]: rows with best >= stop are never
+    picked.  One call enqueues budget + 1 launches and nothing else: no host synchronisation, no communication between
+    workgroups inside a launch.  `blocks`: the number of workgroups (for tests and tuning; `review_blocks(M)` when None) -- the
+    results do not depend on it.  `workspace`: a float64 tensor of at least review_workspace_bytes(M) bytes to reuse.  Exactly
+    buglab/models/_review.py::greedy_host.  No sync."""
+    what = "review_greedy"
+    B, stop = int(budget), float(stop)
+    if not 0 <= B <= REVIEW_MAX_BUDGET:
+        raise ValueError(f"{what}: the budget must be in [0, {REVIEW_MAX_BUDGET}] (got {budget})")
+    if not 0.0 < stop <= 1.0:
+        raise ValueError(f"{what}: stop must be in (0, 1]: the square of a similarity in (0, 1] (got {stop})")
+    G = 0 if blocks is None else int(blocks)
+    if blocks is not None and not 1 <= G <= REVIEW_MAX_BLOCKS:
+        raise ValueError(f"{what}: blocks must be in [1, {REVIEW_MAX_BLOCKS}] (got {blocks})")
+    if best is None or near is None:
+        raise ValueError(f"{what}: best and near are the state to update")
+    if q.dim() != 2:
+        raise ValueError(f"{what}: q {tuple(q.shape)} must be [M, Dp]")
+    if eligible is not None and tuple(eligible.shape) != (q.shape[0],):
+        raise ValueError(f"{what}: eligible {tuple(eligible.shape)} must be [{q.shape[0]}]")
+    M, ldq = _review_image(q, "q", what)
+    _review_state(what, M, n, best, near, q.device)
+    if eligible is not None:
+        _req(eligible, torch.uint8, "eligible")
+    picks = torch.empty(B, dtype=torch.int32, device=q.device)
+    pick_aff = torch.empty(B, dtype=torch.float64, device=q.device)
+    pick_near = torch.empty(B, dtype=torch.int32, device=q.device)
+    if B == 0:
+        return picks, pick_aff, pick_near
+    lib = load_library()
+    need = int(lib.bl_review_workspace_bytes(M))
+    if workspace is None:
+        workspace = torch.empty(need // 8, dtype=torch.float64, device=q.device)
+    _f64(workspace, "workspace")
+    _check(lib.bl_review_greedy(q.data_ptr(), ldq, n.data_ptr(), _p(eligible), M, q.shape[1], B, stop, G, workspace.data_ptr(),
+                                workspace.numel() * 8, best.data_ptr(), near.data_ptr(), picks.data_ptr(), pick_aff.data_ptr(),
+                                pick_near.data_ptr(), _stream()), "bl_review_greedy")
+    return picks, pick_aff, pick_near
 
 
 # ------------------------------------------------------------------------------------------------
