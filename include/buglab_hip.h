@@ -1343,6 +1343,68 @@ int bl_review_greedy(const int8_t* q, int64_t ldq, const int32_t* n, const uint8
                      int32_t* picks, double* pick_aff, int32_t* pick_near, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Warning tracking (buglab/models/track.py), in csrc/bl_track.hip.  BEYOND THE REFERENCE: it has no counterpart.  Given the
+ * warnings of an earlier scan and those of this one, find the ONE-TO-ONE assignment between them: which warnings persist (and
+ * what the reviewer said about them), which are new, which are gone.  buglab/models/_track.py is the same arithmetic in NumPy,
+ * equal bit for bit on every output, by ANOTHER algorithm (it orders the pairs; the device runs rounds).
+ *
+ *   rows        L old rows and N new rows: bl_sim_quantize's int8 images [rows, Dp] in ONE row space -- the old rows are a
+ *               SiteIndex's embeddings, already centred, the new rows are centred with the index's mean -- with bl_review_norms'
+ *               norms n (int32, 0 for an invalid row).
+ *   affinity    the review queue's: a(i, j) = (double)(idot * |idot|) / (double)(n_i * n_j), idot = sum_d q_id q_jd, both
+ *               products in int64 and below 2^53, ONE IEEE quotient.
+ *   admissible  a pair (old i, new j) with n_i > 0, n_j > 0, a(i, j) >= floor (floor = S * S for a least similarity S in
+ *               (0, 1]) and, when keys are given, key_old[i] == key_new[j].  A key is an int32 per row (the file or package,
+ *               numbered on the host over the union of both sides).
+ *   matching    repeatedly take, among the admissible pairs whose two rows are both unmatched, the FIRST in the order
+ *               (greater affinity, then lower old index, then lower new index), and match it; stop when none is left.  A
+ *               function of the input alone, and the unique stable matching under that order: no admissible pair in which each
+ *               side would come before its partner.
+ *   rounds      how the device computes it, without sorting L x N pairs.  A row is OPEN while it is unmatched.  In a round every
+ *               open old row finds its best admissible open new row (the lower new index among equals) and every open new row
+ *               its best admissible open old row (the lower old index among equals); EVERY pair that chose each other is
+ *               matched.  A round that matches nothing ends the matching.  This equals the sequential definition: the first pair
+ *               of the order is always mutual, and no pair that is mutual among the open rows can be pre-empted by an earlier
+ *               pair of the order.  `rounds`, the number of rounds that matched something, is a function of the input too.
+ * Nothing in the arithmetic depends on a launch geometry: no float atomics, no exp, no sqrt, compiled without contraction.
+ *
+ * Image operands have a row stride (a multiple of 16, at least Dp) and a 16-byte aligned base: bl_review_*'s rules.  Keys come
+ * for both sides or for neither (NULL).
+ * bl_track_best_i8: the directional best.  For each OPEN row i of the first side (open_old[i] != 0; NULL: all) the best
+ *   admissible OPEN row of the second side -> best double [L], arg int32 [L]: (affinity, index), the lower index among equals;
+ *   (-2.0, -1) for none and for a row that is not open.  The other direction is the same call with the sides exchanged.  An
+ *   L x N int8 GEMM on v_mfma_i32_16x16x64_i8 that is never stored; the open rows of either side are compacted into ascending
+ *   index lists first (a prefix sum), and each lane gathers its own row of a tile through the list.  slices in
+ *   [1, BL_TRACK_MAX_SLICES]: into how many parts the second side is cut; the result does not depend on it.  workspace:
+ *   bl_track_best_workspace_bytes(L, N, slices) bytes (-1 out of range), 8-byte aligned, contents irrelevant.  Four launches.
+ * bl_track_match: up to max_rounds rounds from a state that it UPDATES: match_old int32 [L] and match_new int32 [N] (the partner,
+ *   -1: unmatched; a fresh state is all -1) and match_aff double [N] (the affinity of a matched new row).  ONE call enqueues
+ *   1 + 6 max_rounds launches on the caller's stream with no host synchronisation and no communication between workgroups
+ *   inside a launch: the open lists of the state, then per round both directions of the best kernel with their merges, a mutual
+ *   kernel with one thread per open new row, and the compaction, which also keeps the counts and the word that says the
+ *   matching has ended.  Control words and lists are ping-pong buffered from launch to launch; once the matching has ended the
+ *   remaining launches read the word and return.  status int32 [4]: rounds run by THIS call that matched something | pairs
+ *   matched by this call | whether the matching has ended (a round of this call matched nothing) | open new rows left.  A call
+ *   from the state an earlier call left continues the matching: two calls of max_rounds = r equal one call of 2 r in the state,
+ *   and their rounds and pairs add up.  workspace: bl_track_match_workspace_bytes(L, N, slices) bytes.
+ * BL_EINVAL: null pointers, negative sizes, Dp not a multiple of 64, a row stride below Dp or not a multiple of 16, images not
+ *   16-byte aligned, doubles not 8-byte aligned, floor outside (0, 1] (NaN included), max_rounds < 1, slices out of range, keys
+ *   for one side only, a workspace too small.  BL_ERANGE: Dp > BL_SIM_MAX_D, L or N > BL_REVIEW_MAX_ROWS, max_rounds >
+ *   BL_TRACK_MAX_ROUNDS.  All of it is checked before the first launch.  No call synchronises. */
+#define BL_TRACK_MAX_SLICES 64
+#define BL_TRACK_MAX_ROUNDS 4096
+int64_t bl_track_best_workspace_bytes(int64_t L, int64_t N, int32_t slices);
+int bl_track_best_i8(const int8_t* q_old, int64_t ld_old, const int32_t* n_old, const int32_t* key_old, const uint8_t* open_old,
+                     int64_t L, const int8_t* q_new, int64_t ld_new, const int32_t* n_new, const int32_t* key_new,
+                     const uint8_t* open_new, int64_t N, int32_t Dp, double floor, int32_t slices, void* workspace,
+                     int64_t workspace_bytes, double* best, int32_t* arg, void* stream);
+int64_t bl_track_match_workspace_bytes(int64_t L, int64_t N, int32_t slices);
+int bl_track_match(const int8_t* q_old, int64_t ld_old, const int32_t* n_old, const int32_t* key_old, int64_t L, const int8_t* q_new,
+                   int64_t ld_new, const int32_t* n_new, const int32_t* key_new, int64_t N, int32_t Dp, double floor,
+                   int32_t max_rounds, int32_t slices, void* workspace, int64_t workspace_bytes, int32_t* match_old,
+                   int32_t* match_new, double* match_aff, int32_t* status, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Confidence calibration (buglab/models/calibrate.py), in csrc/bl_confidence.hip.  BEYOND THE REFERENCE: it has no
  * counterpart; what is calibrated is the confidence its evaluate.py:60-140 thresholds and its visualize.py ranks by.  One
  * inverse temperature beta and a NO_BUG bias rescale the localization distribution, one repair_beta the repair groups:

@@ -16,7 +16,7 @@ This file is a facade: the code lives in the modules below and callers keep usin
   graph      message-passing layers, notifications     linear    gathered Linear, row dot, dropout
   heads      scoring heads and losses                  seq       attention, GRU scan, one-call GREAT layer
   services   ensemble, self-supervision, reports, evaluation, suggestions, FDR, calibration, dedup, drift, grouping, triage,
-             review queues
+             review queues, warning tracking
   optim      clip + Adam on flat buffers               runtime   library-wide modes
 """
 from __future__ import annotations

@@ -240,6 +240,12 @@ _SIGNATURES = {
     "bl_review_workspace_bytes": ([c_int64], c_int64),
     "bl_review_greedy": ([c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int32, c_int32, c_double, c_int32, c_void_p, c_int64, c_void_p,
                           c_void_p, c_void_p, c_void_p, c_void_p, c_void_p], ctypes.c_int),
+    "bl_track_best_workspace_bytes": ([c_int64, c_int64, c_int32], c_int64),
+    "bl_track_best_i8": ([c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64,
+                          c_int32, c_double, c_int32, c_void_p, c_int64, c_void_p, c_void_p, c_void_p], ctypes.c_int),
+    "bl_track_match_workspace_bytes": ([c_int64, c_int64, c_int32], c_int64),
+    "bl_track_match": ([c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int32, c_double,
+                        c_int32, c_int32, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p], ctypes.c_int),
     "bl_attr_node_scores": ([c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int32, c_double, c_int32, c_void_p, c_void_p], ctypes.c_int),
     "bl_attr_topk": ([c_void_p, c_void_p, c_int32, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p],
                      ctypes.c_int),

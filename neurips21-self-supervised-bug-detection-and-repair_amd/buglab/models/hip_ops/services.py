@@ -1,5 +1,5 @@
 """Forward-only device services: ensemble combine, self-supervision scoring / sampling, bug reports, evaluation, confidence
-calibration, near-duplicate detection, drift detection, warning grouping, warning triage, review queues."""
+calibration, near-duplicate detection, drift detection, warning grouping, warning triage, review queues, warning tracking."""
 from __future__ import annotations
 
 from typing import Optional, Tuple
@@ -17,6 +17,7 @@ __all__ = ["ENSEMBLE_KINDS", "ENSEMBLE_MAX_MEMBERS", "ensemble_combine", "ens_lo
            "TRIAGE_MAX_D", "TRIAGE_MAX_SLICES", "triage_slices", "triage_workspace_bytes", "triage_newton_stats", "triage_score",
            "REVIEW_MAX_ROWS", "REVIEW_MAX_BUDGET", "REVIEW_MAX_SLICES", "REVIEW_MAX_BLOCKS", "REVIEW_ROWS_PER_BLOCK", "review_blocks",
            "review_workspace_bytes", "review_cover_slices", "review_norms", "review_cover", "review_greedy",
+           "TRACK_MAX_SLICES", "TRACK_MAX_ROUNDS", "track_slices", "track_best", "track_match",
            "DRIFT_MAX_D", "DRIFT_MAX_PERMUTATIONS", "drift_ok", "drift_mask_ld", "drift_bandwidth", "drift_subsets", "drift_permutation_sums",
            "BOOTSTRAP_MAX_MODELS", "BOOTSTRAP_MAX_SCOUTS", "bootstrap_counts", "CURVE_MAX_BINS", "CURVE_COUNTERS", "bootstrap_curve_counts", "conf_loc_stats", "conf_group_stats", "conf_apply", "DEDUP_MAX_PERM",
            "DEDUP_EMPTY_SLOT", "_i64", "dedup_sha1_u32", "dedup_minhash", "dedup_lsh_insert_query"]
@@ -972,6 +973,106 @@ def review_greedy(q, n, best, near, budget: int, *, eligible=None, stop: float =
                                 workspace.numel() * 8, best.data_ptr(), near.data_ptr(), picks.data_ptr(), pick_aff.data_ptr(),
                                 pick_near.data_ptr(), _stream()), "bl_review_greedy")
     return picks, pick_aff, pick_near
+
+
+# ------------------------------------------------------------------------------------------------
+# warning tracking (csrc/bl_track.hip; include/buglab_hip.h::bl_track_best_i8, bl_track_match).  Shapes and ranges are checked
+# first (plain ValueErrors, also without a GPU), devices after.
+TRACK_MAX_SLICES = 64      # BL_TRACK_MAX_SLICES
+TRACK_MAX_ROUNDS = 4096    # BL_TRACK_MAX_ROUNDS
+
+
+def track_slices(X: int, Y: int) -> int:
+    """Into how many parts `track_best` / `track_match` cut the other side by default: `review_cover_slices`' rule.  The result
+    does not depend on it."""
+    tiles = max((int(X) + 15) // 16, 1)
+    return max(1, min(TRACK_MAX_SLICES, 2048 // tiles, int(Y) // 1024))
+
+
+def _track_sides(what: str, q_old, n_old, q_new, n_new, key_old, key_new, floor, slices):
+    """the checks `track_best` and `track_match` share -> (L, ld_old, N, ld_new, floor, S)"""
+    if q_old.dim() != 2 or q_new.dim() != 2 or q_old.shape[1] != q_new.shape[1]:
+        raise ValueError(f"{what}: the images {tuple(q_old.shape)} and {tuple(q_new.shape)} must be [L, Dp] and [N, Dp]")
+    floor = float(floor)
+    if not 0.0 < floor <= 1.0:
+        raise ValueError(f"{what}: floor must be in (0, 1]: the square of a similarity in (0, 1] (got {floor})")
+    S = track_slices(min(q_old.shape[0], q_new.shape[0]), max(q_old.shape[0], q_new.shape[0])) if slices is None else int(slices)
+    if not 1 <= S <= TRACK_MAX_SLICES:
+        raise ValueError(f"{what}: slices must be in [1, {TRACK_MAX_SLICES}] (got {slices})")
+    if (key_old is None) != (key_new is None):
+        raise ValueError(f"{what}: the keys of both sides come together")
+    for n, q, name in ((n_old, q_old, "n_old"), (n_new, q_new, "n_new"), (key_old, q_old, "key_old"), (key_new, q_new, "key_new")):
+        if n is not None and tuple(n.shape) != (q.shape[0],):
+            raise ValueError(f"{what}: {name} {tuple(n.shape)} must be [{q.shape[0]}]")
+    L, ld_old = _review_image(q_old, "q_old", what)
+    N, ld_new = _review_image(q_new, "q_new", what)
+    for t, name in ((n_old, "n_old"), (n_new, "n_new"), (key_old, "key_old"), (key_new, "key_new")):
+        if t is not None:
+            _i32(t, name)
+    return L, ld_old, N, ld_new, floor, S
+
+
+def track_best(q_old, n_old, q_new, n_new, floor: float, *, key_old=None, key_new=None, open_old=None, open_new=None,
+               slices: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The directional best -> (best float64 [L], arg int32 [L]): for each OPEN row of the first side the best admissible OPEN row
+    of the second as (affinity, index), the lower index among equals; (-2.0, -1) for none and for a row that is not open.  A pair
+    is admissible when both norms are > 0, its affinity (review's) is >= floor and, with keys (int32 per row, both sides or
+    neither), the keys are equal.  q_* int8 [rows, Dp] / n_* int32 [rows] (`similar_quantize`'s images, `review_norms`' norms);
+    open_* uint8 [rows] or None for all.  The other direction is the same call with the sides exchanged.  `slices`: into how many
+    parts the second side is cut (for tests and tuning) -- the result does not depend on it.  Exactly
+    buglab/models/_track.py::best_host.  No sync."""
+    what = "track_best"
+    for mask, q, name in ((open_old, q_old, "open_old"), (open_new, q_new, "open_new")):
+        if mask is not None and (q.dim() != 2 or tuple(mask.shape) != (q.shape[0],)):
+            raise ValueError(f"{what}: {name} {tuple(mask.shape)} must be [{q.shape[0] if q.dim() == 2 else '?'}]")
+    L, ld_old, N, ld_new, floor, S = _track_sides(what, q_old, n_old, q_new, n_new, key_old, key_new, floor, slices)
+    for mask, name in ((open_old, "open_old"), (open_new, "open_new")):
+        if mask is not None:
+            _req(mask, torch.uint8, name)
+    best = torch.empty(L, dtype=torch.float64, device=q_old.device)
+    arg = torch.empty(L, dtype=torch.int32, device=q_old.device)
+    lib = load_library()
+    need = int(lib.bl_track_best_workspace_bytes(L, N, S))
+    workspace = torch.empty(max((need + 7) // 8, 1), dtype=torch.float64, device=q_old.device)
+    _check(lib.bl_track_best_i8(q_old.data_ptr(), ld_old, n_old.data_ptr(), _p(key_old), _p(open_old), L, q_new.data_ptr(), ld_new,
+                                n_new.data_ptr(), _p(key_new), _p(open_new), N, q_old.shape[1], floor, S, workspace.data_ptr(),
+                                workspace.numel() * 8, best.data_ptr(), arg.data_ptr(), _stream()), "bl_track_best_i8")
+    return best, arg
+
+
+def track_match(q_old, n_old, q_new, n_new, floor: float, match_old, match_new, match_aff, *, max_rounds: int = 16, key_old=None,
+                key_new=None, slices: Optional[int] = None, workspace=None, status=None) -> torch.Tensor:
+    """Up to `max_rounds` rounds of mutual best from the state it UPDATES in place: match_old int32 [L] / match_new int32 [N] (the
+    partner, -1: unmatched; a fresh state is all -1) and match_aff float64 [N] -> status int32 [4] ON THE DEVICE: rounds of this
+    call that matched something | pairs matched by this call | whether the matching has ended | open new rows left.  One call
+    enqueues every launch of its rounds and nothing else: no host synchronisation, no communication between workgroups inside a
+    launch; a call from the state an earlier call left continues the matching.  The caller copies `status` back and calls again
+    while the matching has not ended.  `workspace`: a float64 tensor to reuse.  Exactly buglab/models/_track.py::rounds_host.
+    No sync."""
+    what = "track_match"
+    R = int(max_rounds)
+    if not 1 <= R <= TRACK_MAX_ROUNDS:
+        raise ValueError(f"{what}: max_rounds must be in [1, {TRACK_MAX_ROUNDS}] (got {max_rounds})")
+    L, ld_old, N, ld_new, floor, S = _track_sides(what, q_old, n_old, q_new, n_new, key_old, key_new, floor, slices)
+    if match_old is None or match_new is None or match_aff is None:
+        raise ValueError(f"{what}: match_old, match_new and match_aff are the state to update")
+    if tuple(match_old.shape) != (L,) or tuple(match_new.shape) != (N,) or tuple(match_aff.shape) != (N,):
+        raise ValueError(f"{what}: the state {tuple(match_old.shape)}, {tuple(match_new.shape)}, {tuple(match_aff.shape)} must be "
+                         f"[{L}], [{N}], [{N}]")
+    _i32(match_old, "match_old"), _i32(match_new, "match_new"), _f64(match_aff, "match_aff")
+    if status is None:
+        status = torch.empty(4, dtype=torch.int32, device=q_old.device)
+    _i32(status, "status")
+    lib = load_library()
+    need = int(lib.bl_track_match_workspace_bytes(L, N, S))
+    if workspace is None:
+        workspace = torch.empty((need + 7) // 8, dtype=torch.float64, device=q_old.device)
+    _f64(workspace, "workspace")
+    _check(lib.bl_track_match(q_old.data_ptr(), ld_old, n_old.data_ptr(), _p(key_old), L, q_new.data_ptr(), ld_new, n_new.data_ptr(),
+                              _p(key_new), N, q_old.shape[1], floor, R, S, workspace.data_ptr(), workspace.numel() * 8,
+                              match_old.data_ptr(), match_new.data_ptr(), match_aff.data_ptr(), status.data_ptr(), _stream()),
+           "bl_track_match")
+    return status
 
 
 # ------------------------------------------------------------------------------------------------
