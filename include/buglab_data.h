@@ -97,6 +97,20 @@ typedef struct {                  /* caller-allocated outputs; N = sum of num_no
 int32_t bl_collate_graphs(const bl_graph_in_t* graphs, int32_t B, int32_t T, int32_t S, int32_t hub_degree,
                           int32_t token_chunk, bl_collated_t* out);
 
+/* Runs of a collated minibatch (buglab/data/collate.py::message_run_arrays): a run = maximal consecutive messages of one type
+ * with one target.  The backward pass of a message-passing layer (ptgnn MlpMessagePassingLayer, call site
+ * buglab/models/gnnlayerdefs.py:6-23) computes the target half of a run's gradients once; these are its index arrays over a row
+ * space of E + R rows (rows 0..E-1 the messages, E..E+R-1 the runs).  Caller-allocated for the largest case R == E:
+ *   run_ptr [E + 1]        message range of every run                         (R + 1 filled)
+ *   bwd_group_ptr [2T + 1] groups 0..T-1 = type_ptr; T..2T-1 the types over the run rows
+ *   bwd_group_w [2T]       g -> 2 g, T + g -> 2 g + 1 (W viewed as [2T, Din, Dm])
+ *   bwd_rows_tgt / bwd_rows_src [2 E]  [msg_tgt ; run target] / [msg_src ; run target]   (E + R filled)
+ *   tgt_run_ptr [N + 1], tgt_run_rows [E]  CSR node -> rows of its runs (E + run id, ascending)   (R filled)
+ * *num_runs = R.  (bl_data_version() >= 4) */
+int32_t bl_message_runs(const int32_t* msg_src, const int32_t* msg_tgt, const int32_t* type_ptr, int64_t E, int32_t T, int64_t N,
+                        int32_t* run_ptr, int32_t* bwd_group_ptr, int32_t* bwd_group_w, int32_t* bwd_rows_tgt, int32_t* bwd_rows_src,
+                        int32_t* tgt_run_ptr, int32_t* tgt_run_rows, int64_t* num_runs);
+
 /* Stable counting sort of keys in [0, K): perm[E] = item indices ordered by key (ties keep input order),
  * ptr[K + 1] = where each key's run starts.  The collator's CSRs and per-type target order
  * (reference gnn.py:463-542 builds these with Python lists; here: one pass). */

@@ -435,6 +435,22 @@ typedef struct {
                                    * message_aggregation_function values: a_v = act(sum_{e -> v} m_e (/ in-degree)), 0 for a node without
                                    * messages; msg_act must then be BL_ACT_GELU_AGG or BL_ACT_NONE; no winner table (winner_out untouched), every
                                    * message receives its target's gradient in backward (unrouted GEMMs on the matrix cores) */
+  /* Optional: the RUNS of the minibatch (maximal consecutive messages of one type with one target; the collators make these
+   * arrays, buglab/data/collate.py::message_run_arrays).  The routing masks of a run's members are disjoint and the target
+   * halves of their input and weight gradients are summed anyway, so backward computes a run's target half as ONE GEMM row with
+   * the OR of the masks: the routed f16x3 GEMMs then run over E + R rows of Din columns (rows 0..E-1 the messages' source
+   * halves, rows E..E+R-1 the runs' target halves) instead of E rows of 2 Din.  num_runs == 0 or run_ptr == NULL: none.
+   * With run arrays the routing bitmask inside `saved` has E + num_runs rows: size it with bl_mp_layer_saved_bytes(N, E +
+   * num_runs, ...) and hand the SAME arrays to forward and backward.  Taken (bl_set_run_rows) by the f16x3 mode with max
+   * aggregation, matrix-core input gradient and Din a multiple of 128; every other configuration ignores the arrays. */
+  int32_t num_runs;               /* R <= E */
+  const int32_t* run_ptr;         /* [R + 1] message range of every run */
+  const int32_t* bwd_group_ptr;   /* [2 T + 1] groups 0..T-1: the types over message rows; T..2T-1: the types over run rows (+ E) */
+  const int32_t* bwd_group_w;     /* [2 T] weight slice of a group, W viewed as [2 T, Din, Dm]: g -> 2 g, T + g -> 2 g + 1 */
+  const int32_t* bwd_rows_tgt;    /* [E + R] = [msg_tgt ; run target] */
+  const int32_t* bwd_rows_src;    /* [E + R] = [msg_src ; run target] */
+  const int32_t* tgt_run_ptr;     /* [N + 1] CSR node -> the rows of its runs ... */
+  const int32_t* tgt_run_rows;    /* [R]     ... E + run id, ascending */
 } bl_mp_layer_t;
 #define BL_AGG_MAX 0
 #define BL_AGG_SUM 1
@@ -444,7 +460,7 @@ typedef struct {
  * backward: 0 = forward call, 1 = backward call, 2 = backward call that will take the bl_routed_dgrad_nodes_rows path (Wt
  * given, shape supported, deterministic mode off): [E, Din] source-half rows instead of the [E, 2 Din] per-message gradient,
  * 3 = forward-only call (bl_mp_layer_fwd with saved == NULL: the workspace then also holds the packed input and the
- * LayerNorm output) */
+ * LayerNorm output).  E sizes the routing bitmask of `saved` and nothing else: a descriptor with run arrays passes E + num_runs. */
 int64_t bl_mp_layer_saved_bytes(int32_t N, int32_t E, int32_t Din, int32_t Dm, int32_t msg_act);
 int64_t bl_mp_layer_workspace_bytes(int32_t N, int32_t E, int32_t Din, int32_t Dm, int32_t Dout, int32_t backward);
 /* uint16 elements of the packed weights a layer call takes: bl_pack_weights_x6(W, T, 2 Din, Dm, w_is_kn = 1) for
@@ -491,6 +507,22 @@ int bl_node_update_bwd(const float* g_out, const float* h_out, int32_t nrows, in
 /* A/B switch: 1 (default) = bl_mp_layer_bwd uses bl_node_update_bwd where it applies, 0 = the three kernels it replaces.
  * Returns the previous value. */
 int32_t bl_set_fused_node_bwd(int32_t on);
+
+/* The pieces of bl_mp_layer_bwd's run-row path (bl_mp_layer_t.num_runs; backward of the per-type Linear + scatter-max of
+ * ptgnn's MlpMessagePassingLayer, buglab/models/gnnlayerdefs.py:6-23).
+ *   bl_winbits_or_runs: bits[E + r, 0:words] = OR over e in run_ptr[r] .. run_ptr[r + 1] of bits[e, 0:words], behind the E
+ *     message rows of the same buffer (rows ld_bits words apart).
+ *   bl_mp_scatter_grad_runs: bl_mp_scatter_grad / _split (g_h_hi != NULL: columns >= split go there) with both halves at
+ *     column 0 of g_a: g_h[n] = sum_{e in src CSR of n} g_a[e, 0:Din] + sum_{row in run CSR of n} g_a[row, 0:Din];
+ *     num_hub_slots as in bl_mp_layer_t.
+ *   bl_set_run_rows: A/B switch, 1 (default; BL_RUN_ROWS=0 in the environment starts with 0) = bl_mp_layer_bwd takes the
+ *     run-row path where it applies, 0 = the per-message launches on the same arrays.  Returns the previous value. */
+int bl_winbits_or_runs(uint32_t* bits, int32_t ld_bits, const int32_t* run_ptr, int32_t E, int32_t R, int32_t words, void* stream);
+int bl_mp_scatter_grad_runs(const float* g_a, int32_t ld_ga, const int32_t* src_ptr, const int32_t* src_msgs,
+                            const int32_t* tgt_run_ptr, const int32_t* tgt_run_rows, int32_t N, int32_t Din, int32_t split,
+                            float* g_h_lo, int32_t ld_lo, float* g_h_hi, int32_t ld_hi, const int32_t* node_order,
+                            int32_t num_hub_slots, void* stream);
+int32_t bl_set_run_rows(int32_t on);
 
 /* optional per-kernel timing of the launches made inside bl_mp_layer_fwd / _bwd (HIP events on the stream each
  * kernel is launched on); read after a device synchronisation.  bench.py's roofline numbers come from here. */

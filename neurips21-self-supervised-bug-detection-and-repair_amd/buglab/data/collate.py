@@ -11,6 +11,8 @@ adjacency lists:
   type_ptr         : int32[T+1] extent of each edge type in that order (the GEMM groups)
   tgt_ptr/tgt_msgs : int32[N+1]/int32[E]  CSR node -> ids of its incoming messages (ascending)
   src_ptr/src_msgs : int32[N+1]/int32[E]  CSR node -> ids of the messages it is the source of
+  run_ptr, bwd_*, tgt_run_* : the runs (consecutive messages of one type into one node) and the backward pass's row space of
+                     E + R rows built on them (`message_run_arrays`)
 
 Target-sorted CSR turns the reference's atomic `scatter_max` (torch_scatter) into
 a segmented reduction: no atomics, deterministic, ties resolve to the lowest
@@ -138,6 +140,42 @@ def token_occurrence_chunks(token_ids: np.ndarray, token_lens: np.ndarray, chunk
     return occ, chunk_ptr, np.repeat(uniq, nch).astype(I32)
 
 
+RUN_KEYS = ("run_ptr", "bwd_group_ptr", "bwd_group_w", "bwd_rows_tgt", "bwd_rows_src", "tgt_run_ptr", "tgt_run_rows")
+
+
+def message_run_arrays(msg_src: np.ndarray, msg_tgt: np.ndarray, type_ptr: np.ndarray, num_nodes: int) -> Dict[str, np.ndarray]:
+    """The runs of a minibatch and the backward row space built on them (NumPy; `buglab.data.native.message_run_arrays` is the
+    native twin and must return the same arrays).
+
+    A RUN is a maximal stretch of consecutive messages of one type with one target (messages are type-major and target-sorted
+    inside a type).  The max aggregation gives every (node, channel) to one message, so the routing masks of a run's members are
+    disjoint, and the target halves of their input and weight gradients are summed per node / per type anyway: backward computes
+    them once per run with the OR of the masks (csrc/bl_mp_layer.hip).  R runs, row space of E + R rows (0..E-1 the messages,
+    E..E+R-1 the runs):
+      run_ptr [R+1]        message range of every run
+      bwd_group_ptr [2T+1] GEMM groups: 0..T-1 the types over the message rows (= type_ptr), T..2T-1 the types over the run rows
+      bwd_group_w [2T]     weight slice of a group, W [T, 2 Din, Dm] viewed as [2T, Din, Dm]: g -> 2g, T + g -> 2g + 1
+      bwd_rows_tgt [E+R]   [msg_tgt ; run target]        bwd_rows_src [E+R]   [msg_src ; run target]
+      tgt_run_ptr [N+1], tgt_run_rows [R]  CSR node -> rows of its runs (E + run id, ascending)"""
+    msg_src, msg_tgt = np.asarray(msg_src, dtype=I32), np.asarray(msg_tgt, dtype=I32)
+    type_ptr = np.asarray(type_ptr, dtype=np.int64)
+    E, T = int(msg_tgt.shape[0]), int(type_ptr.shape[0]) - 1
+    first = np.zeros(E, dtype=bool)
+    if E:
+        first[1:] = msg_tgt[1:] != msg_tgt[:-1]
+        first[type_ptr[:-1][type_ptr[:-1] < E]] = True  # a type's first message starts a run whatever its neighbour's target
+    starts = np.flatnonzero(first)
+    R = int(starts.shape[0])
+    run_tgt = msg_tgt[starts]
+    runs_before = np.searchsorted(starts, type_ptr, side="left")  # runs that start before each type boundary
+    tgt_run_ptr, order = _csr(run_tgt, num_nodes)
+    return {"run_ptr": np.concatenate([starts, [E]]).astype(I32),
+            "bwd_group_ptr": np.concatenate([type_ptr[:-1], E + runs_before]).astype(I32),
+            "bwd_group_w": np.concatenate([2 * np.arange(T), 2 * np.arange(T) + 1]).astype(I32),
+            "bwd_rows_tgt": np.concatenate([msg_tgt, run_tgt]).astype(I32), "bwd_rows_src": np.concatenate([msg_src, run_tgt]).astype(I32),
+            "tgt_run_ptr": np.asarray(tgt_run_ptr, dtype=I32), "tgt_run_rows": (E + np.asarray(order, dtype=np.int64)).astype(I32)}
+
+
 def _collate_graph_arrays_numpy(graphs, num_edge_types: int, node_off: np.ndarray, N: int) -> Dict[str, np.ndarray]:
     """NumPy version of `buglab.data.native.collate_graph_arrays` (used when the native library is not built, and as
     its test reference)."""
@@ -201,6 +239,7 @@ def _collate_graph_arrays_numpy(graphs, num_edge_types: int, node_off: np.ndarra
            "tok_occ": tok_occ, "tok_chunk_ptr": tok_chunk_ptr, "tok_chunk_id": tok_chunk_id}
     if msg_feat is not None:
         out["msg_feat"] = msg_feat
+    out.update(message_run_arrays(msg_src, msg_tgt, out["type_ptr"], N))
     return out
 
 
@@ -283,6 +322,7 @@ def collate_graphs(graphs: Sequence[TensorizedGraphData], num_edge_types: int) -
         "tgt_msgs": tgt_msgs,
         "src_ptr": src_ptr,
         "src_msgs": src_msgs,
+        **{k: arr[k] for k in RUN_KEYS},
         "node_to_graph": node_to_graph,
         "num_nodes_per_graph": n_per_graph.astype(I32),
         "num_graphs": B,
@@ -403,8 +443,9 @@ _INT_KEYS_GD = ("loc_group_ptr", "loc_group_items", "token_ids", "token_lens", "
                 "head_gather_idx", "head_local_idx", "node_order", "msg_src", "msg_tgt", "type_ptr", "tgt_ptr", "tgt_msgs", "src_ptr", "src_msgs", "node_to_graph", "candidate_ptr")
 
 
-# present only in minibatches of the sequence models (buglab.models.seqmodel.collate_sequences) / with edge features on
-_INT_KEYS_GD_SEQ = ("seq_lens", "erow_ptr", "ekey", "ecode", "msg_feat")
+# present only in minibatches of the sequence models (buglab.models.seqmodel.collate_sequences) / with edge features on / made by
+# collate_graphs (a hand-built graph_data without the run arrays takes the per-message backward)
+_INT_KEYS_GD_SEQ = ("seq_lens", "erow_ptr", "ekey", "ecode", "msg_feat") + RUN_KEYS
 
 
 def pack_minibatch(mb: Dict[str, Any], out: Optional[np.ndarray] = None):

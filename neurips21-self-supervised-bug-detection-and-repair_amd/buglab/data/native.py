@@ -65,7 +65,10 @@ _SIGNATURES = {
     "bl_tensorize_nodes": ([c_void_p, c_int32, c_char_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p], c_int32),
     "bl_counting_sort": ([c_void_p, c_int64, c_int32, c_void_p, c_void_p], c_int32),
     "bl_collate_graphs": ([c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, POINTER(bl_collated_t)], c_int32),
+    "bl_message_runs": ([c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                         c_void_p, POINTER(c_int64)], c_int32),
 }
+RUN_KEYS = ("run_ptr", "bwd_group_ptr", "bwd_group_w", "bwd_rows_tgt", "bwd_rows_src", "tgt_run_ptr", "tgt_run_rows")
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 _lib = None
 
@@ -173,6 +176,31 @@ def collate_graph_arrays(graphs, num_edge_types: int, hub_degree: int, token_chu
     o["tok_occ"] = o["tok_occ"][: c.num_occ]
     o["tok_chunk_ptr"] = o["tok_chunk_ptr"][: c.num_chunks + 1]
     o["tok_chunk_id"] = o["tok_chunk_id"][: c.num_chunks]
+    o.update(message_run_arrays(o["msg_src"], o["msg_tgt"], o["type_ptr"], N))
+    return o
+
+
+def message_run_arrays(msg_src: np.ndarray, msg_tgt: np.ndarray, type_ptr: np.ndarray, num_nodes: int) -> Dict[str, np.ndarray]:
+    """`buglab.data.collate.message_run_arrays` (the runs of a collated minibatch and the backward row space built on them) by
+    `bl_message_runs`, one GIL-free call."""
+    lib = load_library()
+    if lib.bl_data_version() < 4:
+        raise RuntimeError("libbuglab_data.so predates bl_message_runs: rebuild it")
+    msg_src, msg_tgt = np.ascontiguousarray(msg_src, dtype=np.int32), np.ascontiguousarray(msg_tgt, dtype=np.int32)
+    type_ptr = np.ascontiguousarray(type_ptr, dtype=np.int32)
+    E, T, N = int(msg_tgt.shape[0]), int(type_ptr.shape[0]) - 1, int(num_nodes)
+    o = {"run_ptr": np.empty(E + 1, np.int32), "bwd_group_ptr": np.empty(2 * T + 1, np.int32), "bwd_group_w": np.empty(2 * T, np.int32),
+         "bwd_rows_tgt": np.empty(2 * E, np.int32), "bwd_rows_src": np.empty(2 * E, np.int32), "tgt_run_ptr": np.empty(N + 1, np.int32),
+         "tgt_run_rows": np.empty(E, np.int32)}
+    R = c_int64(0)
+    rc = lib.bl_message_runs(msg_src.ctypes.data, msg_tgt.ctypes.data, type_ptr.ctypes.data, E, T, N, *[o[k].ctypes.data for k in RUN_KEYS],
+                             ctypes.byref(R))
+    if rc != 0:
+        raise ValueError(lib.bl_data_last_error().decode())
+    R = int(R.value)
+    o["run_ptr"] = o["run_ptr"][: R + 1]
+    o["bwd_rows_tgt"], o["bwd_rows_src"] = o["bwd_rows_tgt"][: E + R], o["bwd_rows_src"][: E + R]
+    o["tgt_run_rows"] = o["tgt_run_rows"][:R]
     return o
 
 

@@ -62,7 +62,9 @@ class bl_mp_layer_t(Structure):
                 ("src_ptr", c_void_p), ("src_msgs", c_void_p), ("node_order", c_void_p),
                 ("W", c_void_p), ("ln_g", c_void_p), ("ln_b", c_void_p), ("Wd", c_void_p), ("bd", c_void_p),
                 ("msg_act", c_int32), ("ln_eps", c_float), ("drop", bl_dropout_t), ("Wt", c_void_p),
-                ("Wd_packed", c_void_p), ("Wd_packed_bwd", c_void_p), ("num_hub_slots", c_int32), ("aggregation", c_int32)]
+                ("Wd_packed", c_void_p), ("Wd_packed_bwd", c_void_p), ("num_hub_slots", c_int32), ("aggregation", c_int32),
+                ("num_runs", c_int32), ("run_ptr", c_void_p), ("bwd_group_ptr", c_void_p), ("bwd_group_w", c_void_p),
+                ("bwd_rows_tgt", c_void_p), ("bwd_rows_src", c_void_p), ("tgt_run_ptr", c_void_p), ("tgt_run_rows", c_void_p)]
 
 
 class bl_x6_epi_t(Structure):
@@ -125,6 +127,10 @@ _SIGNATURES = {
     "bl_node_update_bwd": ([c_void_p, c_void_p, c_int32, c_int32, bl_dropout_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                             c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p], ctypes.c_int),
     "bl_set_fused_node_bwd": ([c_int32], c_int32),
+    "bl_set_run_rows": ([c_int32], c_int32),
+    "bl_winbits_or_runs": ([c_void_p, c_int32, c_void_p, c_int32, c_int32, c_int32, c_void_p], ctypes.c_int),
+    "bl_mp_scatter_grad_runs": ([c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_int32, c_void_p,
+                                 c_int32, c_void_p, c_int32, c_void_p], ctypes.c_int),
     "bl_last_error": ([], ctypes.c_char_p),
     "bl_embed_subtoken_pool_fwd": ([c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_int32, c_int32, c_int32, bl_dropout_t, c_int32, c_void_p, c_int32, c_void_p, c_void_p], ctypes.c_int),
     "bl_embed_subtoken_pool_bwd": ([c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, bl_dropout_t, c_int32, c_void_p, c_void_p], ctypes.c_int),

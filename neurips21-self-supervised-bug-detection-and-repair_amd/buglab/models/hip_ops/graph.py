@@ -16,10 +16,32 @@ from .gemm import (act_bwd, gemm_rows, gemm_rows_routed, gemm_rows_x6, gemm_wgra
                    layernorm_bwd, pack_bf16x3, pack_weights_x6, scatter_add_rows, segment_max, x6_ok)
 from .weights import _as_groups, _packed_layer_weights, _packed_message_weights, _transposed_layer_weights
 
-__all__ = ["GraphIndex", "POOLINGS", "AGGREGATIONS", "_EmbedSubtokenMax", "embed_subtoken_max", "_MpLayer", "node_update_bwd",
+__all__ = ["GraphIndex", "MessageRuns", "POOLINGS", "AGGREGATIONS", "_EmbedSubtokenMax", "embed_subtoken_max", "_MpLayer", "node_update_bwd",
            "_use_vector_dgrad", "_layer_desc", "_MpLayerFused", "_pending_uses", "set_grad_ready_callback", "_note_use",
            "_notify_backward_launched", "fused_layer_ok", "_GatedMpLayer", "gated_mp_layer", "_MpLayerFeat",
            "mp_layer_with_edge_features", "mp_layer"]
+
+
+class MessageRuns(NamedTuple):
+    """Device-side run arrays of one minibatch (buglab.data.collate.message_run_arrays): the backward row space of E + R rows in
+    which the target halves of the routed gradients are computed once per run (bl_mp_layer_t.num_runs)."""
+
+    run_ptr: torch.Tensor
+    bwd_group_ptr: torch.Tensor
+    bwd_group_w: torch.Tensor
+    bwd_rows_tgt: torch.Tensor
+    bwd_rows_src: torch.Tensor
+    tgt_run_ptr: torch.Tensor
+    tgt_run_rows: torch.Tensor
+
+    @classmethod
+    def of(cls, *arrays) -> Optional["MessageRuns"]:
+        """The tuple, or None when the minibatch carries none of the arrays (hand-built minibatches: per-message backward)."""
+        return cls(*arrays) if all(a is not None for a in arrays) else None
+
+    @property
+    def num_runs(self) -> int:
+        return int(self.run_ptr.shape[0]) - 1
 
 
 class GraphIndex(NamedTuple):
@@ -37,6 +59,7 @@ class GraphIndex(NamedTuple):
     num_types: int
     node_order: Optional[torch.Tensor] = None  # processing order of the per-node kernels: high-degree nodes first
     num_hubs: int = -1  # leading entries of node_order that are hubs (-1: unknown, the kernels look at the first 4096)
+    runs: Optional[MessageRuns] = None  # None: backward works message by message
 
 
 POOLINGS = ("max", "sum", "mean")  # BL_POOL_MAX / _SUM / _MEAN
@@ -249,6 +272,10 @@ def _layer_desc(g: "GraphIndex", W, ln_g, ln_b, Wd, bd, Din, msg_act, drop: Drop
     L.num_hub_slots = int(g.num_hubs)
     L.W, L.ln_g, L.ln_b, L.Wd, L.bd = W.data_ptr(), ln_g.data_ptr(), ln_b.data_ptr(), Wd.data_ptr(), bd.data_ptr()
     L.msg_act, L.ln_eps, L.drop = int(msg_act), 1e-5, drop.c()
+    if g.runs is not None and g.runs.num_runs > 0:  # (forward and backward must agree: the routing bitmask in `saved` has E + R rows)
+        L.num_runs = g.runs.num_runs
+        for name in MessageRuns._fields:
+            setattr(L, name, getattr(g.runs, name).data_ptr())
     return L
 
 
@@ -287,7 +314,7 @@ class _MpLayerFused(torch.autograd.Function):
         infer = not need_bwd and _switches.INFERENCE_MODE
         # ("mean" without an activation keeps the derivative array all the same: it carries the 1 / in-degree)
         saved_act = ACT_GELU_AGG if (agg == 2 and msg_act == ACT_NONE) else msg_act
-        saved = None if infer else torch.empty((lib.bl_mp_layer_saved_bytes(N, E, Din, Dm, saved_act),), dtype=torch.uint8, device=dev)
+        saved = None if infer else torch.empty((lib.bl_mp_layer_saved_bytes(N, E + L.num_runs, Din, Dm, saved_act),), dtype=torch.uint8, device=dev)
         ws = torch.empty((lib.bl_mp_layer_workspace_bytes(N, E, Din, Dm, Dout, 3 if infer else 0),), dtype=torch.uint8, device=dev)
         out = torch.empty((N, Dout), dtype=torch.float32, device=dev)
         winner = torch.empty((N, Dm), dtype=torch.int32, device=dev) if (_switches.WINNER_SINK is not None and agg == 0) else None

@@ -7,7 +7,7 @@ from . import _switches
 from ._cabi import load_library
 
 __all__ = ["set_deterministic", "_MSG_GEMM_MODES", "set_msg_gemm_mode", "msg_gemm_mode", "set_seq_gemm_mode", "seq_gemm_mode", "set_wgrad_tile",
-           "set_wgrad_kchunk_cap", "set_fused_node_bwd", "deterministic"]
+           "set_wgrad_kchunk_cap", "set_fused_node_bwd", "set_run_rows", "deterministic"]
 
 
 def set_deterministic(on: bool = True) -> None:
@@ -68,6 +68,12 @@ def set_wgrad_kchunk_cap(rows: int) -> int:
 def set_fused_node_bwd(on: bool) -> bool:
     """A/B switch: the node update's backward chain of the fused layer call as one kernel (default) or three.  -> previous."""
     return bool(load_library().bl_set_fused_node_bwd(1 if on else 0))
+
+
+def set_run_rows(on: bool) -> bool:
+    """A/B switch (BL_RUN_ROWS=0 starts with it off): backward of the fused layer call computes the target halves of the routed
+    f16x3 gradients once per run of messages (default) or once per message, on the same arrays.  -> previous."""
+    return bool(load_library().bl_set_run_rows(1 if on else 0))
 
 
 def deterministic() -> bool:

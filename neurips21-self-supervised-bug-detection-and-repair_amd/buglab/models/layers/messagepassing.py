@@ -21,7 +21,7 @@ import torch
 from torch import nn
 
 from buglab.models import hip_ops
-from buglab.models.hip_ops import Dropout, GraphIndex
+from buglab.models.hip_ops import Dropout, GraphIndex, MessageRuns
 
 
 class GnnOutput(NamedTuple):
@@ -208,11 +208,14 @@ class GraphNeuralNetwork(nn.Module):
     def forward(self, *, token_ids, token_lens, msg_src, msg_tgt, type_ptr, tgt_ptr, tgt_msgs, src_ptr, src_msgs,
                 node_to_graph, reference_node_ids, reference_node_graph_idx, num_graphs, num_nodes, num_messages,
                 return_all_states: bool = False, dropout_seed: Optional[int] = None, tok_occ=None, tok_chunk_ptr=None,
-                tok_chunk_id=None, node_order=None, num_hub_nodes: int = -1, msg_feat=None, input_transform=None, **_unused) -> GnnOutput:
+                tok_chunk_id=None, node_order=None, num_hub_nodes: int = -1, msg_feat=None, input_transform=None, run_ptr=None,
+                bwd_group_ptr=None, bwd_group_w=None, bwd_rows_tgt=None, bwd_rows_src=None, tgt_run_ptr=None, tgt_run_rows=None,
+                **_unused) -> GnnOutput:
         """input_transform: applied to the embedder's output before the first layer (buglab/models/explain.py scales and
         re-leafs it there); None, as every other caller leaves it, changes nothing."""
         graph = GraphIndex(msg_src, msg_tgt, type_ptr, tgt_ptr, tgt_msgs, src_ptr, src_msgs, int(num_nodes),
-                           int(num_messages), int(type_ptr.shape[0]) - 1, node_order, int(num_hub_nodes))
+                           int(num_messages), int(type_ptr.shape[0]) - 1, node_order, int(num_hub_nodes),
+                           MessageRuns.of(run_ptr, bwd_group_ptr, bwd_group_w, bwd_rows_tgt, bwd_rows_src, tgt_run_ptr, tgt_run_rows))
         training = self.training and dropout_seed is not None
         seed = int(dropout_seed or 0)
         mk = lambda rate, stream: Dropout(rate if training else 0.0, seed, stream)

@@ -32,10 +32,17 @@ int bl_act_bwd_impl(const float* g_y, const float* y, int32_t nrows, int32_t N, 
 int bl_mp_scatter_src_accum_impl(const float* g_src, int32_t ld_src, const int32_t* src_ptr, const int32_t* src_msgs, int32_t N,
                                  int32_t Din, int32_t split, float* g_h_lo, int32_t ld_lo, float* g_h_hi, int32_t ld_hi,
                                  const int32_t* node_order, int32_t hub_slots, void* stream);
-// bl_mp_scatter_grad / _split with the number of hub entries at the front of node_order (g_h_hi == NULL: one output)
+// bl_mp_scatter_grad / _split with the number of hub entries at the front of node_order (g_h_hi == NULL: one output);
+// col_tgt: column of g_a where the rows listed by tgt_msgs start (Din: the per-message [E, 2 Din] layout, 0: the run-row layout)
 int bl_mp_scatter_grad_hubs_impl(const float* g_a, int32_t ld_ga, const int32_t* src_ptr, const int32_t* src_msgs, const int32_t* tgt_ptr,
                                  const int32_t* tgt_msgs, int32_t N, int32_t Din, int32_t split, float* g_h_lo, int32_t ld_lo, float* g_h_hi,
-                                 int32_t ld_hi, const int32_t* node_order, int32_t hub_slots, void* stream);
+                                 int32_t ld_hi, const int32_t* node_order, int32_t hub_slots, int32_t col_tgt, void* stream);
+// bl_gemm_wgrad_h3 for a group_w that maps every group to a slice of its own: the chunks of a (group, tile) may then add in order
+// like those of a launch without group_w (deterministic mode; csrc/bl_gemm_h3.hip)
+int bl_gemm_wgrad_h3_impl(const bl_rows_packed_t* a, const uint16_t* g_packed, const int32_t* g_idx, const uint32_t* win_bits,
+                          int32_t ld_bits, const int32_t* group_ptr, const int32_t* group_w, int32_t G, int32_t M, int32_t N, int32_t K,
+                          float out_scale, const float* g_amax_dev, float* gw, int64_t gw_group_stride, int32_t ld_gw,
+                          bool group_w_one_to_one, void* stream);
 
 int bl_node_update_bwd_impl(const float* g_out, const float* h_out, int32_t nrows, int32_t Dout, bl_dropout_t drop,
                             const uint16_t* wd_packed_bwd, const float* agg, const float* mean, const float* rstd, const float* ln_g,

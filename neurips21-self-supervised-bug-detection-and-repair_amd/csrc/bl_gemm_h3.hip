@@ -223,6 +223,14 @@ extern "C" int bl_gemm_wgrad_h3(const bl_rows_packed_t* a, const uint16_t* g_pac
                                 int32_t ld_bits, const int32_t* group_ptr, const int32_t* group_w, int32_t G, int32_t M, int32_t N,
                                 int32_t K, float out_scale, const float* g_amax_dev, float* gw, int64_t gw_group_stride, int32_t ld_gw,
                                 void* stream) {
+  return bl_gemm_wgrad_h3_impl(a, g_packed, g_idx, win_bits, ld_bits, group_ptr, group_w, G, M, N, K, out_scale, g_amax_dev, gw,
+                               gw_group_stride, ld_gw, false, stream);
+}
+
+int bl_gemm_wgrad_h3_impl(const bl_rows_packed_t* a, const uint16_t* g_packed, const int32_t* g_idx, const uint32_t* win_bits,
+                          int32_t ld_bits, const int32_t* group_ptr, const int32_t* group_w, int32_t G, int32_t M, int32_t N, int32_t K,
+                          float out_scale, const float* g_amax_dev, float* gw, int64_t gw_group_stride, int32_t ld_gw,
+                          bool group_w_one_to_one, void* stream) {
   const char* who = "bl_gemm_wgrad_h3";
   if (M == 0) return BL_OK;
   BlPackedRows r;
@@ -232,7 +240,7 @@ extern "C" int bl_gemm_wgrad_h3(const bl_rows_packed_t* a, const uint16_t* g_pac
   const bool routed = win_bits != nullptr;
   BL_CHECK_ARG(!routed || (g_idx && ld_bits * 32 >= N), "%s: the routed form needs g_idx and ld_bits >= N / 32", who);
   const BlWgradPlan p = bl_wgrad_plan(group_ptr, group_w, G, M, N, K, XBM, XBN, routed ? wgrad_h3_resident<true>() : wgrad_h3_resident<false>(),
-                                      stream);
+                                      stream, group_w_one_to_one);
   const dim3 grid = p.grid;
 #define HW_ARGS                                                                                                                  \
   BL_PACKED_ROWS_ARGS(r), reinterpret_cast<const uint4*>(g_packed), g_idx, win_bits, ld_bits, group_ptr, group_w, G, M, N, K, p.kchunk, \

@@ -88,13 +88,14 @@ struct BlWgradPlan {
   unsigned* order_ctr;
 };
 static inline BlWgradPlan bl_wgrad_plan(const int32_t* group_ptr, const int32_t* group_w, int G, int M, int N, int K, int tile_rows,
-                                        int tile_cols, int resident, void* stream) {
+                                        int tile_cols, int resident, void* stream, bool group_w_one_to_one = false) {
   BlWgradPlan p;
   p.ntiles_n = (N + tile_cols - 1) / tile_cols;
   const int ntiles_all = ((K + tile_rows - 1) / tile_rows) * p.ntiles_n;
   p.kchunk = bl_wgrad_kchunk(M, ntiles_all, (group_ptr ? G : 0) * ntiles_all, resident, g_wgrad_kchunk_cap);
   p.grid = dim3((M + p.kchunk - 1) / p.kchunk + (group_ptr ? G : 0), ntiles_all);
-  p.order_ctr = group_w ? nullptr : bl_order_counters((group_ptr ? G : 1) * ntiles_all, stream);
+  // (a group_w the caller vouches for as one-to-one leaves every (group, tile) its own output: ordered like no group_w at all)
+  p.order_ctr = (group_w && !group_w_one_to_one) ? nullptr : bl_order_counters((group_ptr ? G : 1) * ntiles_all, stream);
   p.xcd = p.order_ctr ? 0 : 1;  // ordered flushes want "lower chunk = lower workgroup id"
   return p;
 }

@@ -758,7 +758,8 @@ __global__ __launch_bounds__(256) void mp_scatter_grad_kernel(const float* __res
                                                               const int* __restrict__ tgt_msgs, int N, int Din,
                                                               int accumulate, float* __restrict__ g_h, int ld_gh,
                                                               const int* __restrict__ node_order, int split,
-                                                              float* __restrict__ g_h2, int ld_gh2, int hub_slots) {
+                                                              float* __restrict__ g_h2, int ld_gh2, int hub_slots,
+                                                              int col_tgt) {
   // The first hub_slots entries of node_order are the nodes with many incident messages (the collators put them in front).
   // One wave walking a 512-row segment eight rows at a time is 64 dependent round trips -- at the power-law configuration
   // that one wave WAS the kernel's duration (207 vs 152 us at hidden 256).  Workgroups 0 .. hub_slots - 1 therefore take ONE
@@ -788,7 +789,7 @@ __global__ __launch_bounds__(256) void mp_scatter_grad_kernel(const float* __res
     if (part == 1 && tgt_ptr == nullptr) continue;  // source-only messages (GGNN)
     const int* __restrict__ ptr = part == 0 ? src_ptr : tgt_ptr;
     const int* __restrict__ items = part == 0 ? src_msgs : tgt_msgs;
-    const int coff = part == 0 ? 0 : Din;
+    const int coff = part == 0 ? 0 : col_tgt;  // (Din: per-message rows [src half | tgt half]; 0: run rows of their own)
     int beg = ptr[n], end = ptr[n + 1];
     if (split4) {  // this wave's contiguous share of the segment
       const int share = (end - beg + 3) >> 2;
@@ -1147,12 +1148,13 @@ int bl_act_bwd_impl(const float* g_y, const float* y, int32_t nrows, int32_t N, 
 static int mp_scatter_launch(const char* who, const float* g_a, int32_t ld_ga, const int32_t* src_ptr, const int32_t* src_msgs,
                              const int32_t* tgt_ptr, const int32_t* tgt_msgs, int32_t N, int32_t Din, int32_t accumulate, float* g_h,
                              int32_t ld_gh, const int32_t* node_order, int32_t split, float* g_h2, int32_t ld_gh2, int32_t hub_slots,
-                             void* stream) {
+                             void* stream, int32_t col_tgt = -1) {
+  if (col_tgt < 0) col_tgt = Din;
   hipStream_t st = (hipStream_t)stream;
   const int hubs = (node_order && hub_slots > 0) ? min(hub_slots, N) : 0;
   const dim3 grid(hubs + (N - hubs + 3) / 4);
   DISPATCH_NV(Din, hipLaunchKernelGGL((mp_scatter_grad_kernel<NV>), grid, dim3(256), 0, st, g_a, ld_ga, src_ptr, src_msgs, tgt_ptr,
-                                       tgt_msgs, N, Din, accumulate, g_h, ld_gh, node_order, split, g_h2, ld_gh2, hubs))
+                                       tgt_msgs, N, Din, accumulate, g_h, ld_gh, node_order, split, g_h2, ld_gh2, hubs, col_tgt))
   BL_LAUNCH_CHECK(who);
   return BL_OK;
 }
@@ -1172,13 +1174,66 @@ extern "C" int bl_mp_scatter_grad(const float* g_a, int32_t ld_ga, const int32_t
 // (bl_mp_layer_t.num_hub_slots): g_h_hi == NULL -> one output of Din columns (split ignored)
 int bl_mp_scatter_grad_hubs_impl(const float* g_a, int32_t ld_ga, const int32_t* src_ptr, const int32_t* src_msgs, const int32_t* tgt_ptr,
                                  const int32_t* tgt_msgs, int32_t N, int32_t Din, int32_t split, float* g_h_lo, int32_t ld_lo, float* g_h_hi,
-                                 int32_t ld_hi, const int32_t* node_order, int32_t hub_slots, void* stream) {
+                                 int32_t ld_hi, const int32_t* node_order, int32_t hub_slots, int32_t col_tgt, void* stream) {
   if (N == 0) return BL_OK;
-  BL_CHECK_ARG(g_a && src_ptr && src_msgs && tgt_ptr && tgt_msgs && g_h_lo && Din > 0 && Din <= 512 && ld_ga >= 2 * Din,
+  BL_CHECK_ARG(g_a && src_ptr && src_msgs && tgt_ptr && tgt_msgs && g_h_lo && Din > 0 && Din <= 512 && col_tgt >= 0 && ld_ga >= col_tgt + Din,
                "bl_mp_scatter_grad (layer call): bad argument");
   BL_CHECK_ARG(g_h_hi == nullptr || (split > 0 && split < Din && ld_lo >= split && ld_hi >= Din - split), "bl_mp_scatter_grad (layer call): split");
   return mp_scatter_launch("bl_mp_scatter_grad", g_a, ld_ga, src_ptr, src_msgs, tgt_ptr, tgt_msgs, N, Din, 0, g_h_lo, ld_lo, node_order,
-                           g_h_hi ? split : Din, g_h_hi, ld_hi, hub_slots, stream);
+                           g_h_hi ? split : Din, g_h_hi, ld_hi, hub_slots, stream, col_tgt);
+}
+
+extern "C" int bl_mp_scatter_grad_runs(const float* g_a, int32_t ld_ga, const int32_t* src_ptr, const int32_t* src_msgs,
+                                       const int32_t* tgt_run_ptr, const int32_t* tgt_run_rows, int32_t N, int32_t Din, int32_t split,
+                                       float* g_h_lo, int32_t ld_lo, float* g_h_hi, int32_t ld_hi, const int32_t* node_order,
+                                       int32_t num_hub_slots, void* stream) {
+  return bl_mp_scatter_grad_hubs_impl(g_a, ld_ga, src_ptr, src_msgs, tgt_run_ptr, tgt_run_rows, N, Din, split, g_h_lo, ld_lo, g_h_hi, ld_hi,
+                                      node_order, num_hub_slots, 0, stream);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Routing masks of the runs (maximal consecutive messages of one type with one target): row E + r = OR of the rows of run r's
+// members.  One thread per (run, V-sized piece of a row); a run's members are consecutive rows and runs follow each other, so
+// neighbouring threads read neighbouring words.  Streaming: every word is read once and (R / E of them) written once.
+template <class V>
+__global__ __launch_bounds__(256) void winbits_or_runs_kernel(uint32_t* __restrict__ bits, int ld_bits, const int* __restrict__ run_ptr,
+                                                              int E, int R, int pieces) {
+  const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= (long long)R * pieces) return;
+  const int r = (int)(t / pieces), p = (int)(t - (long long)r * pieces);
+  const int e0 = max(run_ptr[r], 0), e1 = min(run_ptr[r + 1], E);  // (never a row outside the message rows, whatever the array holds)
+  constexpr int NW = sizeof(V) / 4;
+  uint32_t acc[NW];
+#pragma unroll
+  for (int j = 0; j < NW; ++j) acc[j] = 0u;
+  for (int e = e0; e < e1; ++e) {
+    const V v = *reinterpret_cast<const V*>(bits + (size_t)e * ld_bits + (size_t)p * NW);
+    uint32_t w[NW];
+    __builtin_memcpy(w, &v, sizeof(V));
+#pragma unroll
+    for (int j = 0; j < NW; ++j) acc[j] |= w[j];
+  }
+  V out;
+  __builtin_memcpy(&out, acc, sizeof(V));
+  *reinterpret_cast<V*>(bits + (size_t)(E + r) * ld_bits + (size_t)p * NW) = out;
+}
+
+extern "C" int bl_winbits_or_runs(uint32_t* bits, int32_t ld_bits, const int32_t* run_ptr, int32_t E, int32_t R, int32_t words,
+                                  void* stream) {
+  if (R == 0) return BL_OK;
+  BL_CHECK_ARG(bits && run_ptr && E > 0 && R > 0 && R <= E && words > 0 && ld_bits >= words,
+               "bl_winbits_or_runs: null pointer, R outside 1..E or ld_bits < words");
+  BL_CHECK_RANGE((long long)E + R <= 0x7fffffffLL, "bl_winbits_or_runs: E + R beyond int32");
+  const bool vec = words % 4 == 0 && ld_bits % 4 == 0 && bl_aligned16(bits);
+  const int pieces = vec ? words / 4 : words;
+  const long long total = (long long)R * pieces;
+  const dim3 grid((unsigned)((total + 255) / 256));
+  if (vec)
+    hipLaunchKernelGGL((winbits_or_runs_kernel<uint4>), grid, dim3(256), 0, (hipStream_t)stream, bits, ld_bits, run_ptr, E, R, pieces);
+  else
+    hipLaunchKernelGGL((winbits_or_runs_kernel<uint32_t>), grid, dim3(256), 0, (hipStream_t)stream, bits, ld_bits, run_ptr, E, R, pieces);
+  BL_LAUNCH_CHECK("bl_winbits_or_runs");
+  return BL_OK;
 }
 
 // g_h (+)= sums of the SOURCE-half rows g_src [E, Din] over the source CSR (the second step of the half-atomic input gradient,

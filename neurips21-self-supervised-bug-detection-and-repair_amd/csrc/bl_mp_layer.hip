@@ -9,7 +9,9 @@
 //             gradient, LayerNorm backward, packed results; three kernels where its shapes do not apply) -> dense weight
 //             gradient (side stream) || routed bf16x6 weight gradient (side stream) || routed input gradient (vector
 //             units from the non-zeros, or bf16x6 GEMM) -> segmented sums over the src / tgt CSRs (two outputs for a
-//             folded concat)
+//             folded concat).  With the run arrays of the minibatch (bl_mp_layer_t.num_runs; f16x3, max aggregation, matrix cores):
+//             OR of the routing masks per run -> both routed GEMMs over E + R rows of Din columns (source halves per message,
+//             target halves per run) -> segmented sums over the source CSR and the run CSR
 //   forward-only (saved == NULL): the same forward without any store that only a backward pass reads
 // The caller owns every buffer: `saved` lives from forward to backward, `ws` only during the call
 // (sizes from bl_mp_layer_saved_bytes / bl_mp_layer_workspace_bytes); nothing is allocated here except three
@@ -37,8 +39,12 @@ const char* kProfNames[] = {"pack_rows",      "msg_gemm_x6",  "segment_max_ln", 
                             "node_update_bwd", "msg_gemm_h3", "msg_wgrad_h3", "msg_dgrad_h3", "pack_gq_h3",
                             // the relational transformer block (csrc/bl_great_layer.hip; BL_PROF_GREAT_* in bl_common.h)
                             "linear_x6_epi", "linear_dgrad_x6", "gemm_wgrad_x6", "attn_probs_fwd", "attn_probs_bwd", "attn_rows_times",
-                            "attn_transposed_times", "add_layernorm", "layernorm_bwd_branch"};
+                            "attn_transposed_times", "add_layernorm", "layernorm_bwd_branch",
+                            // the run rows of bl_mp_layer_bwd: OR of the routing masks per run (bl_winbits_or_runs)
+                            "winbits_or_runs"};
+constexpr int kProfWinbitsOrRuns = 26;
 constexpr int kProfKinds = sizeof(kProfNames) / sizeof(kProfNames[0]);
+static_assert(kProfWinbitsOrRuns == kProfKinds - 1, "kProfWinbitsOrRuns must index its name");
 
 hipEvent_t prof_event() {
   if (!g_prof_pool.empty()) {
@@ -132,13 +138,14 @@ inline size_t packed_w_elems(int G, int K, int N) { return (size_t)G * ((N + 127
 struct Saved {  // forward -> backward
   uint16_t* hp;      // [N, 3 Din]  packed layer input
   float* dact;       // [N, Dm]     message activation derivative at each winner (GELU only)
-  uint32_t* bits;    // [E, Dm/32]  routing bitmask
+  uint32_t* bits;    // [E + R, Dm/32]  routing bitmask of the messages, then (backward fills them) of the R runs of the layer descriptor
   float* agg;        // [N, Dm]
   float* mean;       // [N]
   float* rstd;       // [N]
   float* ln_out;     // [N, Dm] fp32, or (dense node update as bf16x6) the bf16x3-packed form [N, 3 Dm] in the same region
   size_t bytes;
 };
+// (E counts the rows of the routing bitmask and nothing else: callers with run arrays pass E + R)
 Saved carve_saved(void* base, int N, int E, int Din, int Dm, int msg_act) {
   Saved s;
   char* p = (char*)base;
@@ -212,6 +219,21 @@ bool msg_h3() {
 
 bool g_fused_node_bwd = true;  // bl_set_fused_node_bwd: act backward -> dense input gradient -> LayerNorm backward in one kernel
 
+// bl_set_run_rows / BL_RUN_ROWS: the target halves of the routed f16x3 gradients once per run instead of once per message
+int g_run_rows = -1;
+bool run_rows_on() {
+  if (g_run_rows < 0) {
+    const char* e = getenv("BL_RUN_ROWS");
+    g_run_rows = (e && e[0] == '0') ? 0 : 1;
+  }
+  return g_run_rows != 0;
+}
+// R of a descriptor that carries the run arrays (all of them), else 0; decides the rows of the routing bitmask in `saved`
+inline int layer_runs(const bl_mp_layer_t* L) {
+  return (L->num_runs > 0 && L->run_ptr && L->bwd_group_ptr && L->bwd_group_w && L->bwd_rows_tgt && L->bwd_rows_src && L->tgt_run_ptr &&
+          L->tgt_run_rows) ? L->num_runs : 0;
+}
+
 // fork / join events of the side stream, one set per device (a process that drives several GPUs -- tests, tools -- must not
 // record an event created on another device)
 constexpr int kMaxDevices = 16;
@@ -243,6 +265,7 @@ int check_layer(const bl_mp_layer_t* L, const char* who) {
   BL_CHECK_ARG(L->msg_act == BL_ACT_NONE || L->msg_act == BL_ACT_GELU || L->msg_act == BL_ACT_GELU_AGG,
                "%s: message activation must be none, gelu (per message) or gelu_agg (on the aggregate)", who);
   BL_CHECK_ARG(L->aggregation >= BL_AGG_MAX && L->aggregation <= BL_AGG_MEAN, "%s: aggregation must be BL_AGG_MAX, BL_AGG_SUM or BL_AGG_MEAN", who);
+  BL_CHECK_ARG(L->num_runs >= 0 && L->num_runs <= L->E && (long long)L->E + L->num_runs <= 0x7fffffffLL, "%s: num_runs outside 0..E", who);
   BL_CHECK_ARG(L->aggregation == BL_AGG_MAX || L->msg_act != BL_ACT_GELU,
                "%s: sum / mean aggregation takes the activation on the aggregate (BL_ACT_GELU_AGG) or none: a per-message activation would need "
                "the [E, Dm] messages again in backward", who);
@@ -255,6 +278,12 @@ int check_layer(const bl_mp_layer_t* L, const char* who) {
 extern "C" int32_t bl_set_fused_node_bwd(int32_t on) {
   const int32_t prev = g_fused_node_bwd ? 1 : 0;
   g_fused_node_bwd = on != 0;
+  return prev;
+}
+
+extern "C" int32_t bl_set_run_rows(int32_t on) {
+  const int32_t prev = run_rows_on() ? 1 : 0;
+  g_run_rows = on != 0 ? 1 : 0;
   return prev;
 }
 
@@ -314,7 +343,7 @@ extern "C" int bl_mp_layer_fwd(const bl_mp_layer_t* L, const float* h_lo, int32_
   // kernels skip the load (one dependent round trip less per wave)
   const int32_t* node_order = L->num_hub_slots == 0 ? nullptr : L->node_order;
   // ("mean" without an activation still needs the [N, Dm] derivative array: it carries the 1 / in-degree)
-  Saved S = carve_saved(saved, N, E, Din, Dm, saved_act_code(L));
+  Saved S = carve_saved(saved, N, E + layer_runs(L), Din, Dm, saved_act_code(L));
   float* pre = (float*)ws;
   if (infer) {
     const WsInfer I = carve_infer(ws, N, E, Din, Dm);
@@ -403,12 +432,19 @@ extern "C" int bl_mp_layer_bwd(const bl_mp_layer_t* L, const float* h_out, const
   const bool two = side != st;
   SideEvents* ev = two ? ensure_events() : nullptr;
   if (two) BL_CHECK_ARG(ev != nullptr, "bl_mp_layer_bwd: cannot create HIP events");
-  Saved S = carve_saved(const_cast<void*>(saved), N, E, Din, Dm, saved_act_code(L));
+  const int R = layer_runs(L);
+  Saved S = carve_saved(const_cast<void*>(saved), N, E + R, Din, Dm, saved_act_code(L));
   const uint32_t* bits = L->aggregation == BL_AGG_MAX ? S.bits : nullptr;  // sum / mean: every message receives its target's gradient
   // the input gradient from the non-zeros of the routed message gradient (vector units) when the caller supplied W^T and
   // W[t]^T fits one LDS block; node sums fused in (atomics) unless the deterministic mode asks for a fixed summation order
   const bool vec_dgrad = L->Wt != nullptr && E > 0 && bl_routed_dgrad_vec_ok(Dm, 2 * Din) && L->aggregation == BL_AGG_MAX;
   const bool fused_sums = vec_dgrad && !bl_get_deterministic();
+  // Run rows: the target halves of the routed input and weight gradients as one GEMM row per run (the masks of a run's members are
+  // disjoint, their target halves are summed anyway) -- E + R rows of Din columns instead of E rows of 2 Din.  f16x3 with max
+  // aggregation on the matrix cores; Din a multiple of 128 because the backward weight image of [T] groups x 2 Din columns, read
+  // with half the group stride, then IS the image of [2 T] groups x Din columns (blocks are ordered [column tile][stage] in a group)
+  const bool run_rows = R > 0 && E > 0 && run_rows_on() && msg_h3() && g_msg_h3 == 1 && !vec_dgrad && L->aggregation == BL_AGG_MAX &&
+                        Din % 128 == 0 && w_packed_bwd != nullptr;
   WsBwd B = carve_bwd(ws, N, E, Din, Dm, Dout, !fused_sums);
 
   // dense node update on the bf16x6 path: forward must have run with Wd_packed too (it decides the form of `saved`)
@@ -472,6 +508,10 @@ extern "C" int bl_mp_layer_bwd(const bl_mp_layer_t* L, const float* h_out, const
     if (!fused_node) BL_TRY(bl_amax(B.g_ln, (int64_t)N * Dm, B.amax, st));  // (the fused node-update backward took it on the way)
     BL_TRY(bl_pack_f16x2(B.g_ln, Dm, N, Dm, Dm, 0, 1.0f, B.amax, B.gqp, st));
   }
+  if (run_rows) {  // (before the weight-gradient fork: both GEMMs read the runs' masks)
+    ProfScope ps(kProfWinbitsOrRuns, 0.0, st, two);
+    BL_TRY(bl_winbits_or_runs(S.bits, Dm / 32, L->run_ptr, E, R, Dm / 32, st));
+  }
   // The routed weight gradient (side stream) reads what is ready at this point: the packed layer input, the packed gradient operand, the
   // routing bits.  WHEN it is forked decides what it runs next to.  Layers up to 128 wide: here, side by side with the routed input
   // gradient.  Wider layers (the hidden-256 configurations): behind the segmented sums, i.e. next to the bandwidth-bound tail of this layer
@@ -489,7 +529,13 @@ extern "C" int bl_mp_layer_bwd(const bl_mp_layer_t* L, const float* h_out, const
       (void)hipEventRecord(ev->fork2, st);
       (void)hipStreamWaitEvent(side, ev->fork2, 0);
     }
-    if (h3) {
+    if (run_rows) {  // one source: the message rows gather h[src], the run rows h[tgt]; gW viewed as [2 T, Din, Dm]
+      ProfScope ps(14, 2.0 * ((double)E + R) * Din * Dm, side, two);
+      a.idx[0] = L->bwd_rows_src; a.xp[1] = nullptr; a.idx[1] = nullptr; a.width[1] = 0;
+      a.nsrc = 1;
+      BL_TRY(bl_gemm_wgrad_h3_impl(&a, B.gqp, L->bwd_rows_tgt, bits, Dm / 32, L->bwd_group_ptr, L->bwd_group_w, 2 * T, E + R, Dm, Din,
+                                   1.0f / BL_H3_ROW_SCALE, B.amax, g_W, (int64_t)Din * Dm, Dm, true, side));
+    } else if (h3) {
       ProfScope ps(14, 2.0 * E * (2.0 * Din) * Dm, side, two);
       BL_TRY(bl_gemm_wgrad_h3(&a, B.gqp, L->msg_tgt, bits, Dm / 32, L->type_ptr, nullptr, T, E, Dm, 2 * Din, 1.0f / BL_H3_ROW_SCALE, B.amax,
                               g_W, (int64_t)2 * Din * Dm, Dm, side));
@@ -529,6 +575,11 @@ extern "C" int bl_mp_layer_bwd(const bl_mp_layer_t* L, const float* h_out, const
     } else if (vec_dgrad) {
       ProfScope ps(9, 2.0 * N * (2.0 * Din) * Dm, st, two);
       BL_TRY(bl_routed_dgrad_vec(B.g_ln, Dm, L->msg_tgt, S.bits, Dm / 32, L->type_ptr, T, L->Wt, E, Dm, 2 * Din, B.g_a, 2 * Din, st));
+    } else if (run_rows) {  // g_a [E + R, Din]: rows 0..E-1 the messages' source halves, E..E+R-1 the runs' target halves
+      ProfScope ps(15, 2.0 * ((double)E + R) * Din * Dm, st, two);
+      g.idx[0] = L->bwd_rows_tgt;
+      BL_TRY(bl_gemm_rows_h3(&g, bits, Dm / 32, w_packed_bwd, bl_packed_weight_elems_h3(1, Dm, Din), L->bwd_group_ptr, L->bwd_group_w, 2 * T,
+                             E + R, Din, Dm, 1.0f / BL_H3_W_SCALE, B.amax, B.g_a, Din, st));
     } else if (h3) {
       ProfScope ps(15, 2.0 * E * (2.0 * Din) * Dm, st, two);
       BL_TRY(bl_gemm_rows_h3(&g, bits, Dm / 32, w_packed_bwd, bl_packed_weight_elems_h3(1, Dm, 2 * Din), L->type_ptr, nullptr, T, E, 2 * Din,
@@ -546,8 +597,12 @@ extern "C" int bl_mp_layer_bwd(const bl_mp_layer_t* L, const float* h_out, const
   if (!fused_sums) {
     ProfScope ps(10, 0.0, st, two);
     // E == 0: both CSRs are empty and g_a is never read
+    if (run_rows)
+      BL_TRY(bl_mp_scatter_grad_hubs_impl(B.g_a, Din, L->src_ptr, L->src_msgs, L->tgt_run_ptr, L->tgt_run_rows, N, Din, width_lo, g_h_lo, ld_lo,
+                                          g_h_hi, ld_hi, node_order, L->num_hub_slots, 0, st));
+    else
     BL_TRY(bl_mp_scatter_grad_hubs_impl(B.g_a, 2 * Din, L->src_ptr, L->src_msgs, L->tgt_ptr, L->tgt_msgs, N, Din, width_lo, g_h_lo, ld_lo,
-                                        g_h_hi, ld_hi, node_order, L->num_hub_slots, st));
+                                        g_h_hi, ld_hi, node_order, L->num_hub_slots, Din, st));
   }
   if (E > 0 && late_fork) BL_TRY(launch_wgrad());
   if (two && join_side) {

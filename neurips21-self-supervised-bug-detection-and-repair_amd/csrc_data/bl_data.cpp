@@ -490,7 +490,7 @@ bool parse_datapoint(bl_reader* r, P p, P end, bl_datapoint_t* out) {
 }  // namespace
 
 extern "C" const char* bl_data_last_error(void) { return g_err; }
-extern "C" int32_t bl_data_version(void) { return 3; }  // 3: bl_graph_in_t.adj_feat / bl_collated_t.msg_feat
+extern "C" int32_t bl_data_version(void) { return 4; }  // 3: bl_graph_in_t.adj_feat / bl_collated_t.msg_feat; 4: bl_message_runs
 
 extern "C" int32_t bl_pyset_order(const int32_t* inserted, int32_t n, int32_t* out) {
   if (n < 0 || (n > 0 && (!inserted || !out))) { set_err("bl_pyset_order: bad arguments"); return -1; }
@@ -750,5 +750,49 @@ extern "C" int32_t bl_collate_graphs(const bl_graph_in_t* graphs, int32_t B, int
     out->num_occ = n_occ;
     out->num_chunks = nchunks;
   }
+  return 0;
+}
+
+// ---- runs of a collated minibatch (buglab/data/collate.py::message_run_arrays) ---------------------------------
+// A run = maximal consecutive messages of one type with one target (messages are type-major and target-sorted inside a type).
+// The backward pass of a message-passing layer computes the target half of a run's gradients once (csrc/bl_mp_layer.hip); these
+// are the index arrays it reads, made once per minibatch.  Outputs are caller-allocated for the largest case R == E:
+//   run_ptr [E + 1], bwd_group_ptr [2 T + 1], bwd_group_w [2 T], bwd_rows_tgt / bwd_rows_src [2 E], tgt_run_ptr [N + 1],
+//   tgt_run_rows [E]; *num_runs = R says how much of them is filled (R + 1, -, -, E + R, E + R, -, R).
+extern "C" int32_t bl_message_runs(const int32_t* msg_src, const int32_t* msg_tgt, const int32_t* type_ptr, int64_t E, int32_t T, int64_t N,
+                                   int32_t* run_ptr, int32_t* bwd_group_ptr, int32_t* bwd_group_w, int32_t* bwd_rows_tgt,
+                                   int32_t* bwd_rows_src, int32_t* tgt_run_ptr, int32_t* tgt_run_rows, int64_t* num_runs) {
+  if (!type_ptr || !run_ptr || !bwd_group_ptr || !bwd_group_w || !tgt_run_ptr || !num_runs || T < 1 || N < 0 || E < 0 ||
+      (E > 0 && (!msg_src || !msg_tgt || !bwd_rows_tgt || !bwd_rows_src || !tgt_run_rows))) { set_err("bl_message_runs: bad argument"); return -1; }
+  if (2 * E > 0x7fffffffLL || N > 0x7fffffffLL) { set_err("bl_message_runs: E + R may exceed 2^31 rows"); return -1; }
+  if (type_ptr[0] != 0 || type_ptr[T] != E) { set_err("bl_message_runs: type_ptr does not span the messages"); return -1; }
+  int64_t R = 0;
+  for (int32_t t = 0; t < T; ++t) {
+    if (type_ptr[t + 1] < type_ptr[t]) { set_err("bl_message_runs: type_ptr not monotone"); return -1; }
+    bwd_group_ptr[t] = type_ptr[t];
+    bwd_group_ptr[T + t] = (int32_t)(E + R);
+    bwd_group_w[t] = 2 * t;
+    bwd_group_w[T + t] = 2 * t + 1;
+    for (int32_t e = type_ptr[t]; e < type_ptr[t + 1]; ++e) {
+      const int32_t v = msg_tgt[e];
+      if (v < 0 || v >= N) { set_err("bl_message_runs: message %d: target out of range", e); return -2; }
+      if (e == type_ptr[t] || v != msg_tgt[e - 1]) {
+        run_ptr[R] = e;
+        bwd_rows_tgt[E + R] = v;
+        bwd_rows_src[E + R] = v;
+        ++R;
+      }
+    }
+  }
+  run_ptr[R] = (int32_t)E;
+  bwd_group_ptr[2 * T] = (int32_t)(E + R);
+  for (int64_t e = 0; e < E; ++e) { bwd_rows_tgt[e] = msg_tgt[e]; bwd_rows_src[e] = msg_src[e]; }
+  // CSR node -> rows of its runs (E + run id, ascending)
+  for (int64_t k = 0; k <= N; ++k) tgt_run_ptr[k] = 0;
+  for (int64_t r = 0; r < R; ++r) ++tgt_run_ptr[bwd_rows_tgt[E + r] + 1];
+  for (int64_t k = 0; k < N; ++k) tgt_run_ptr[k + 1] += tgt_run_ptr[k];
+  std::vector<int32_t> next(tgt_run_ptr, tgt_run_ptr + N);
+  for (int64_t r = 0; r < R; ++r) tgt_run_rows[next[bwd_rows_tgt[E + r]]++] = (int32_t)(E + r);
+  *num_runs = R;
   return 0;
 }
