@@ -4,7 +4,7 @@ from __future__ import annotations
 
 import threading
 from collections import deque
-from typing import Any, Callable, Dict, Iterable, Iterator, List, NamedTuple, Sequence, Tuple
+from typing import Any, Callable, Dict, Iterable, Iterator, List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -130,6 +130,94 @@ def flat_prediction_output_and_encoding(trained_nn, mb_data) -> Tuple[torch.Tens
 def flat_prediction_output(trained_nn, mb_data) -> torch.Tensor:
     """The flat output of `flat_prediction_output_and_encoding` alone."""
     return flat_prediction_output_and_encoding(trained_nn, mb_data)[0]
+
+
+SAMPLES = -1  # the sample axis in the shape of a `RunColumns` column
+
+
+class RunColumns:
+    """The run-long results of a scan tool: named columns, all views of ONE device allocation, so that a run ends with one
+    copy back.  `spec` = ordered (name, "float64" | "float32" | "int32", shape) with exactly one SAMPLES axis in each shape:
+    (SAMPLES,), (SAMPLES, k), (2, SAMPLES).  Every column starts 8-byte aligned and is contiguous at full capacity, whatever the
+    capacity and the other sizes are.  `reserve(B)` makes room for the next minibatch and gives the sample offset its kernel
+    writes at; read the views (`cols[name]`) after it, because it may have moved them."""
+
+    def __init__(self, device, capacity: int, spec: Sequence[Tuple[str, str, Tuple[int, ...]]]):
+        self.device, self.capacity, self.n = torch.device(device), max(int(capacity), 1), 0
+        self._spec = [(name, getattr(torch, dtype), tuple(shape)) for name, dtype, shape in spec]
+        assert all(shape.count(SAMPLES) == 1 and dtype in (torch.float64, torch.float32, torch.int32) for _, dtype, shape in self._spec)
+        self._blob, self._cols = self._views(self.capacity)
+
+    def _views(self, capacity: int, blob: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, Dict[str, torch.Tensor]]:
+        """(the allocation, name -> view of it) at `capacity`; without `blob` a new one is allocated"""
+        shapes = [tuple(capacity if s == SAMPLES else s for s in shape) for _, _, shape in self._spec]
+        cells = [int(np.prod(shape)) for shape in shapes]
+        doubles = [c if dtype == torch.float64 else (c + 1) // 2 for c, (_, dtype, _) in zip(cells, self._spec)]  # odd 4-byte cells: padded
+        if blob is None:
+            blob = torch.empty(sum(doubles), dtype=torch.float64, device=self.device)
+        out, pos = {}, 0
+        for (name, dtype, _), shape, c, d in zip(self._spec, shapes, cells, doubles):
+            out[name] = blob[pos:pos + d].view(dtype)[:c].view(shape)
+            pos += d
+        return blob, out
+
+    def __getitem__(self, name: str) -> torch.Tensor:
+        return self._cols[name]
+
+    def _trimmed(self, cols: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
+        return {name: cols[name].narrow(shape.index(SAMPLES), 0, self.n) for name, _, shape in self._spec}
+
+    def reserve(self, B: int) -> int:
+        """Room for B more samples -> their offset (the count before).  A stream of unknown length: double, on the device --
+        one new allocation, every column's samples so far copied along its own sample axis, no synchronisation."""
+        n = self.n
+        if n + B > self.capacity:
+            old = self._trimmed(self._cols)
+            self.capacity = max(2 * self.capacity, n + B)
+            self._blob, self._cols = self._views(self.capacity)
+            for name, t in self._trimmed(self._cols).items():
+                t.copy_(old[name])
+        self.n = n + B
+        return n
+
+    def device_columns(self) -> Dict[str, torch.Tensor]:
+        """The columns trimmed to the samples reserved so far, still on the device."""
+        return self._trimmed(self._cols)
+
+    def to_host(self) -> Dict[str, np.ndarray]:
+        """The trimmed columns as arrays: the one copy (and the one synchronisation) of the run."""
+        return {name: t.numpy() for name, t in self._trimmed(self._views(self.capacity, self._blob.cpu())[1]).items()}
+
+
+def run_capacity(capacity: Optional[int], data, of_a_stream: int) -> int:
+    """The samples a tool's `RunColumns` start with: what the caller asked for, else `len(data)`, else the tool's constant."""
+    return capacity if capacity is not None else len(data) if hasattr(data, "__len__") else of_a_stream
+
+
+def predictions_in_order(model, nn, tagged: Iterable[Tuple[Any, Any]], device, parallelize: bool, rejected: Callable[[Any], None],
+                         what: str) -> Iterator[Tuple[Any, Any, Any, Any]]:
+    """`model.predict` over the datapoints of `tagged` = (datapoint, tag) pairs -> (tag, datapoint, location_logprobs,
+    rewrite_logprobs) in input order.  `predict` keeps the input order and yields the datapoint objects it was given, so what it
+    passed over -- its `tensorize` rejected them -- is what was sent before the one that comes out: `rejected(tag)` is called
+    for those, in input order, and for the tail.  `what` names the caller and its predict in the error."""
+    pending: "deque" = deque()  # (datapoint, tag) of what went in and has not come out
+
+    def tracked():
+        for point, tag in tagged:
+            pending.append((point, tag))
+            yield point
+
+    for point, location_logprobs, rewrite_logprobs in model.predict(tracked(), nn, device, parallelize):
+        while True:
+            if not pending:
+                raise RuntimeError(f"{what} yielded a datapoint it was not given")
+            sent, tag = pending.popleft()
+            if sent is point:
+                break
+            rejected(tag)
+        yield tag, point, location_logprobs, rewrite_logprobs
+    while pending:
+        rejected(pending.popleft()[1])
 
 
 class InOrder:

@@ -210,15 +210,11 @@ def load_datapoints(path) -> Iterator[Any]:
 
 
 def run(args: argparse.Namespace) -> Dict[str, float]:
-    import torch
-
     from buglab.controllers._batching import save_msgpack_l_gz_reproducibly
-    from buglab.runtime.neuralmodel import AbstractNeuralModel
+    from buglab.models._cli import open_model, require_gpu
 
-    if not torch.cuda.is_available():
-        raise RuntimeError("bugselector: no ROCm GPU visible; the BugLab hot path has no CPU fallback")
-    device = torch.device("cuda")
-    model, nn = AbstractNeuralModel.restore_model(Path(args.MODEL_FILENAME), device)
+    require_gpu(None, "bugselector")
+    model, nn, device, _ = open_model(args.MODEL_FILENAME)
     stats = BugSelectionStats()
     replies = select_rewrites(model, nn, load_datapoints(args.DATA_PATH), device, num_rewrites_per_sample=args.num_rewrites_per_sample,
                               temperature=args.temperature_scaling, epsilon=args.epsilon, seed=args.seed,

@@ -133,15 +133,11 @@ def load_records(path) -> Iterator[Any]:
 
 
 def run(args: argparse.Namespace) -> int:
-    import torch
-
     from buglab.controllers._batching import save_msgpack_l_gz_reproducibly
-    from buglab.runtime.neuralmodel import AbstractNeuralModel
+    from buglab.models._cli import open_model, require_gpu
 
-    if not torch.cuda.is_available():
-        raise RuntimeError("detectorscoring: no ROCm GPU visible; the BugLab hot path has no CPU fallback")
-    device = torch.device("cuda")
-    model, nn = AbstractNeuralModel.restore_model(Path(args.MODEL_FILENAME), device)
+    require_gpu(None, "detectorscoring")
+    model, nn, device, _ = open_model(args.MODEL_FILENAME)
     count = 0
 
     def scored():

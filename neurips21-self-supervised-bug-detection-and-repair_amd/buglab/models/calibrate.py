@@ -23,7 +23,6 @@ from hip_ops.eval_judge on the raw and on the calibrated outputs, binned on the 
 from __future__ import annotations
 
 import argparse
-import json
 import logging
 import sys
 from pathlib import Path
@@ -252,25 +251,19 @@ def parse_args(argv=None) -> argparse.Namespace:
 
 
 def run(args: argparse.Namespace) -> ConfidenceCalibration:
-    import torch
-
-    from buglab.runtime.neuralmodel import AbstractNeuralModel
+    from buglab.models._cli import open_model, require_gpu, write_report_json
     from buglab.runtime.richpath import RichPath
     from buglab.utils.msgpackutils import load_all_msgpack_l_gz
 
-    if not torch.cuda.is_available():
-        raise RuntimeError("calibrate: no ROCm GPU visible; the BugLab hot path has no CPU fallback")
-    device = torch.device("cuda")
-    model, nn = AbstractNeuralModel.restore_model(Path(args.MODEL_FILENAME), device)
+    require_gpu(None, "calibrate")
+    model, nn, device, _ = open_model(args.MODEL_FILENAME)
     data = load_all_msgpack_l_gz(RichPath.create(args.VALID_DATA_PATH), shuffle=True, limit_num_yielded_elements=args.limit_num_elements)
     report: Dict[str, Any] = {}
     cal = calibrate_model(model, nn, data, device, parallelize=not args.sequential, fit_bias=not args.no_bias,
                           fit_repair=not args.no_repair, num_bins=args.num_bins, report=report)
     model.save(Path(args.OUT_MODEL_FILENAME), nn)
     sys.stdout.write(format_report(report))
-    if args.report_json is not None:
-        with open(args.report_json, "w", encoding="utf-8") as f:
-            f.write(json.dumps(report, indent=1, sort_keys=True) + "\n")
+    write_report_json(args.report_json, report)
     return cal
 
 

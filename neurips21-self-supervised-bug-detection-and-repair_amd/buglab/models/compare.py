@@ -182,17 +182,14 @@ def parse_args(argv=None) -> argparse.Namespace:
 def run(args: argparse.Namespace) -> ComparisonReport:
     import torch
 
-    from buglab.runtime.neuralmodel import AbstractNeuralModel
-    from buglab.runtime.richpath import RichPath
-    from buglab.utils.msgpackutils import load_all_msgpack_l_gz
+    from buglab.models._cli import open_model, read_data, require_gpu
 
-    if not torch.cuda.is_available():
-        raise RuntimeError("compare: no ROCm GPU visible; the BugLab hot path has no CPU fallback")
+    require_gpu(None, "compare")
     if len(args.MODEL) > C.MAX_MODELS:
         raise ValueError(f"compare: {len(args.MODEL)} models; a comparison takes 1 to {C.MAX_MODELS} (BL_BOOTSTRAP_MAX_MODELS)")
     device = torch.device("cuda")
-    data = list(load_all_msgpack_l_gz(RichPath.create(args.DATA), shuffle=False, limit_num_yielded_elements=args.limit_num_elements))
-    models = [AbstractNeuralModel.restore_model(Path(name), device) for name in args.MODEL]
+    data = read_data(args.DATA, args.limit_num_elements)
+    models = [open_model(name)[:2] for name in args.MODEL]
     report = compare_models(models, data, device, num_replicates=args.num_replicates, seed=args.seed, confidence=args.confidence,
                             assume_buggy=args.assume_buggy, eval_only_no_bug=args.eval_only_no_bug, parallelize=not args.sequential,
                             host_bootstrap=args.host_bootstrap, names=[str(name) for name in args.MODEL], curves=args.curves,

@@ -31,10 +31,8 @@ not sum to 1, and the training kernel renormalises what it is given.  Such recor
 from __future__ import annotations
 
 import argparse
-import json
 import logging
 import sys
-from collections import deque
 from pathlib import Path
 from typing import Any, Dict, Iterable, Iterator, Optional
 
@@ -93,24 +91,19 @@ def annotate_with_teacher(model, nn, data: Iterable[Any], device, parallelize: b
     if getattr(model, "confidence_calibration", None) is not None:
         LOGGER.info("The teacher carries a confidence calibration %s: records are annotated with CALIBRATED log-probabilities "
                     "(what its predict reports).", model.confidence_calibration)
-    pending: "deque" = deque()  # (view handed to predict, record), in input order; predict yields its inputs in order too
+    from buglab.controllers._batching import predictions_in_order
 
-    def views():
+    def views():  # (view handed to predict, record)
         for record in data:
-            if record is None:
-                continue
-            report["records_in"] += 1
-            view = _teacher_view(record)
-            pending.append((view, record))
-            yield view
+            if record is not None:
+                report["records_in"] += 1
+                yield _teacher_view(record), record
 
-    for seen, location_logprobs, rewrite_logprobs in model.predict(views(), nn, device, parallelize):
-        while pending and pending[0][0] is not seen:  # what predict passed over: its tensorize rejected the record
-            pending.popleft()
-            report["records_dropped"] += 1
-        if not pending:
-            raise RuntimeError("distill: the teacher's predict yielded a datapoint it was not given")
-        _, record = pending.popleft()
+    def dropped(_record):  # what predict passed over: its tensorize rejected the record
+        report["records_dropped"] += 1
+
+    for record, _, location_logprobs, rewrite_logprobs in predictions_in_order(model, nn, views(), device, parallelize, dropped,
+                                                                               "distill: the teacher's predict"):
         nodes = np.unique(record["graph"]["reference_nodes"]).tolist()
         if sorted(k for k in location_logprobs if k != -1) != nodes or -1 not in location_logprobs:
             raise RuntimeError("distill: the teacher's location distribution is not over the record's candidate nodes + NO_BUG")
@@ -133,8 +126,6 @@ def annotate_with_teacher(model, nn, data: Iterable[Any], device, parallelize: b
         report["records_out"] += 1
         report["location_entropy_sum"] += K.entropy(loc)
         yield record
-    report["records_dropped"] += len(pending)
-    pending.clear()
 
 
 def annotate_shards(model, nn, data_path, out_dir, device, *, parallelize: bool = False, limit_num_elements: Optional[int] = None
@@ -194,22 +185,16 @@ def parse_args(argv=None) -> argparse.Namespace:
 
 
 def main(argv=None) -> Dict[str, Any]:
-    import torch
-
-    from buglab.runtime.neuralmodel import AbstractNeuralModel
+    from buglab.models._cli import open_model, require_gpu, write_report_json
 
     args = parse_args(argv)
-    if not torch.cuda.is_available():
-        raise RuntimeError("distill: no ROCm GPU visible; the BugLab hot path has no CPU fallback")
-    device = torch.device("cuda")
-    model, nn = AbstractNeuralModel.restore_model(Path(args.TEACHER_MODEL), device)
+    require_gpu(None, "distill")
+    model, nn, device, _ = open_model(args.TEACHER_MODEL)
     require_teacher(model)
     report = annotate_shards(model, nn, args.DATA_PATH, args.OUT_DIR, device, parallelize=not args.sequential,
                              limit_num_elements=args.limit_num_elements)
     sys.stdout.write(format_report(report))
-    if args.report_json is not None:
-        with open(args.report_json, "w", encoding="utf-8") as f:
-            f.write(json.dumps(report, indent=1, sort_keys=True) + "\n")
+    write_report_json(args.report_json, report)
     return report
 
 

@@ -29,12 +29,11 @@ and one copy back; `--host` runs the NumPy twin (buglab/models/_drift.py, fp64) 
 from __future__ import annotations
 
 import argparse
-import json
 import logging
 import math
 import sys
 from pathlib import Path
-from typing import Any, Iterable, List, Optional, Tuple
+from typing import Any, Iterable, Optional
 
 if __package__ in (None, ""):
     sys.path.insert(0, str(Path(__file__).resolve().parents[2]))
@@ -43,6 +42,8 @@ import numpy as np
 
 from buglab.models import _drift as Dr
 from buglab.models import _similar as S
+from buglab.models._cli import embedding_dim as _embedding_dim, open_model as _open_model, read_data as _read_data
+from buglab.models._cli import require_gpu, write_records, write_report_json
 from buglab.models._drift import DriftReport
 from buglab.models._similar import SiteIndex
 
@@ -157,33 +158,7 @@ def parse_args(argv=None) -> argparse.Namespace:
     return args
 
 
-def _open_model(path: str) -> Tuple[Any, Any, Any, bool]:
-    import torch
-
-    from buglab.runtime.neuralmodel import AbstractNeuralModel
-
-    have_gpu = torch.cuda.is_available()
-    device = torch.device("cuda" if have_gpu else "cpu")
-    model, nn = AbstractNeuralModel.restore_model(Path(path), device)
-    return model, nn, device, have_gpu
-
-
-def _embedding_dim(nn) -> int:
-    from buglab.models import similar
-
-    return similar.embedding_dim(nn)
-
-
-def _read_data(path: str, limit: Optional[int]) -> List[Any]:
-    from buglab.runtime.richpath import RichPath
-    from buglab.utils.msgpackutils import load_all_msgpack_l_gz
-
-    return list(load_all_msgpack_l_gz(RichPath.create(path), shuffle=False, limit_num_yielded_elements=limit))
-
-
 def run(args: argparse.Namespace) -> int:
-    from buglab.models.suggest import write_records
-
     model, nn, device, have_gpu = _open_model(args.MODEL)
     index = SiteIndex.load(args.INDEX)
     try:  # before anything is read or run: an index of another model's embeddings is the caller's mistake
@@ -191,8 +166,7 @@ def run(args: argparse.Namespace) -> int:
     except S.DimensionMismatch as e:
         print(str(e), file=sys.stderr)
         return EXIT_DIMENSION_MISMATCH
-    if not have_gpu:
-        raise RuntimeError("drift: no ROCm GPU visible; the BugLab hot path has no CPU fallback")
+    require_gpu(have_gpu, "drift")
     data = _read_data(args.DATA, args.limit_num_elements)
     report = detect_drift(model, nn, index, data, device, args.num_permutations, args.seed, alpha=args.alpha,
                           bandwidth_scale=args.bandwidth_scale, top_k=args.top_k, site=args.site, assume_buggy=args.assume_buggy,
@@ -202,9 +176,7 @@ def run(args: argparse.Namespace) -> int:
     print(f"drift: {'DRIFT' if report.drift else 'no drift'} at alpha {report.alpha:g}: p-value {report.p_value:.4g}, MMD2 "
           f"{report.statistic:.6g} (null mean {report.null_mean:.6g}, 95 % {report.null_q95:.6g}){spread}; {report.n} reference and "
           f"{report.m} scanned sites of size {report.dim}, {report.num_rejected} samples rejected, {report.num_without_site} without a site.")
-    if args.report_json is not None:
-        with open(args.report_json, "w", encoding="utf-8") as f:
-            f.write(json.dumps(report.record(), indent=1, sort_keys=True) + "\n")
+    write_report_json(args.report_json, report.record())
     return EXIT_DRIFT if report.drift else EXIT_NO_DRIFT
 
 

@@ -54,7 +54,7 @@ if __package__ in (None, ""):
 import numpy as np
 import torch
 
-from buglab.models.gnn import GnnBugLabModel
+from buglab.models._cli import open_model, require_gpu
 from buglab.runtime.richpath import RichPath
 from buglab.utils.msgpackutils import load_all_msgpack_l_gz
 
@@ -356,8 +356,8 @@ class ColumnarEvaluationReport(EvaluationReport):
 
 
 def evaluate_on_device(model, nn, data: Iterable[Any], device, *, assume_buggy: bool = False, eval_only_no_bug: bool = False,
-                       parallelize: bool = True, positions_out: Optional[list] = None, top_k: Optional[int] = None
-                       ) -> ColumnarEvaluationReport:
+                       parallelize: bool = True, positions_out: Optional[list] = None, top_k: Optional[int] = None,
+                       capacity: Optional[int] = None) -> ColumnarEvaluationReport:
     """`evaluate_predictions(model.predict(data, nn, device, parallelize), ...)` without the per-sample host work: the
     minibatches `predict` forms (same `tensorize`, same 50 samples), the same forward, and one hip_ops.eval_judge launch per
     minibatch that writes the verdicts into outcome buffers kept on the device until the end (24 bytes per sample, one copy
@@ -367,8 +367,9 @@ def evaluate_on_device(model, nn, data: Iterable[Any], device, *, assume_buggy: 
     receives the position in `data` of every judged sample, in the order of the outcome columns before `eval_only_no_bug`
     (a datapoint `tensorize` rejects has none): what buglab/models/compare.py pairs two models' samples by.  With `top_k` one
     hip_ops.rank_suggestions launch follows each judge launch, on index arrays that extend the judge's by two, and writes the
-    ranks of the true fix and the true location into buffers kept next to the outcome buffers (the ranks do not depend on how
-    many entries are listed, so one is); they are copied back after the outcomes and the report carries `top_k_summary`."""
+    ranks of the true fix and the true location into columns of the same allocation (the ranks do not depend on how many entries
+    are listed, so one is); the report carries `top_k_summary`.  `capacity`: the samples the buffers (`RunColumns`) start with,
+    by default `len(data)`, or 1 << 14 for a stream."""
     from buglab.controllers import _batching as Bt
     from buglab.models import _evaluate as E
     from buglab.models import _suggest as S
@@ -391,18 +392,10 @@ def evaluate_on_device(model, nn, data: Iterable[Any], device, *, assume_buggy: 
         scouts = ["NoBug" if t is None else p["candidate_rewrite_metadata"][t][0] for p, t in zip(points, targets)]
         return {"ix": dict(zip(index_fields, Bt.to_device_i32([getattr(ix, f) for f in index_fields], dev))), "scouts": scouts}
 
-    def buffers(capacity):  # [confidence | the four verdict rows] in one allocation: one copy back
-        blob = torch.empty(3 * capacity, dtype=torch.float64, device=device)
-        return blob, blob[:capacity], blob[capacity:].view(torch.int32).view(4, capacity)
-
-    def rank_buffers(capacity):  # [the two rank rows | one listed entry | its log-probability]
-        return (torch.empty((2, capacity), dtype=torch.int32, device=device), torch.empty((capacity, 1), dtype=torch.int32, device=device),
-                torch.empty((capacity, 1), dtype=torch.float64, device=device))
-
-    capacity = max(len(data), 1) if hasattr(data, "__len__") else 1 << 14
-    blob, conf, verdict = buffers(capacity)
-    ranks = rank_buffers(capacity) if top_k is not None else None
-    n = 0
+    spec = [("confidence", "float64", (Bt.SAMPLES,)), ("verdict", "int32", (4, Bt.SAMPLES))]
+    if top_k is not None:  # the two rank rows, one listed entry and its log-probability
+        spec += [("rank", "int32", (2, Bt.SAMPLES)), ("entry", "int32", (Bt.SAMPLES, 1)), ("logprob", "float64", (Bt.SAMPLES, 1))]
+    cols = Bt.RunColumns(device, Bt.run_capacity(capacity, data, 1 << 14), spec)
     nn.eval()
     with torch.no_grad(), model._tensorize_all_location_rewrites():
         for mb, tags in Bt.prediction_minibatches(model, ((d, i) for i, d in enumerate(data)), device, parallelize, extend,
@@ -412,32 +405,23 @@ def evaluate_on_device(model, nn, data: Iterable[Any], device, *, assume_buggy: 
             if positions_out is not None:
                 assert len(tags) == B
                 positions_out.extend(tags)
-            if n + B > capacity:  # a stream of unknown length: double, on the device
-                capacity = max(2 * capacity, n + B)
-                _, new_conf, new_verdict = grown = buffers(capacity)
-                new_conf[:n].copy_(conf[:n]), new_verdict[:, :n].copy_(verdict[:, :n])
-                blob, conf, verdict = grown
-                if ranks is not None:
-                    new_ranks = rank_buffers(capacity)
-                    new_ranks[0][:, :n].copy_(ranks[0][:, :n])
-                    ranks = new_ranks
-            hip_ops.eval_judge(flat, mb["selfsup"]["ix"], conf, verdict, n, assume_buggy=assume_buggy)
-            if ranks is not None:
-                hip_ops.rank_suggestions(flat, mb["selfsup"]["ix"], *ranks, n, k=1, skip_nobug=assume_buggy)
+            n = cols.reserve(B)
+            hip_ops.eval_judge(flat, mb["selfsup"]["ix"], cols["confidence"], cols["verdict"], n, assume_buggy=assume_buggy)
+            if top_k is not None:
+                hip_ops.rank_suggestions(flat, mb["selfsup"]["ix"], cols["rank"], cols["entry"], cols["logprob"], n, k=1,
+                                         skip_nobug=assume_buggy)
             for name in mb["selfsup"]["scouts"]:
                 has_bug.append(name != "NoBug")
                 scout.append(ids.setdefault(name, len(ids)))
                 if scout[-1] == len(names):
                     names.append(name)
-            n += B
-    host = blob.cpu()  # the one copy (and the one synchronisation) of the run
-    conf, verdict = host[:capacity][:n].numpy(), host[capacity:].view(torch.int32).view(4, capacity)[:, :n].numpy()
-    report = ColumnarEvaluationReport(conf, has_bug, verdict[0] != 0, verdict[1] != 0, verdict[2], verdict[3] != 0, scout, names,
-                                      eval_only_no_bug)
-    if ranks is not None:
-        columns = ranks[0][:, :n].cpu().numpy()
-        keep = ~np.asarray(has_bug, dtype=bool) if eval_only_no_bug else np.ones(n, dtype=bool)
-        report.top_k = S.top_k_summary(columns[0][keep], columns[1][keep], report.has_bug, report.scout, names, top_k)
+    host = cols.to_host()  # the one copy (and the one synchronisation) of the run
+    verdict = host["verdict"]
+    report = ColumnarEvaluationReport(host["confidence"], has_bug, verdict[0] != 0, verdict[1] != 0, verdict[2], verdict[3] != 0, scout,
+                                      names, eval_only_no_bug)
+    if top_k is not None:
+        keep = ~np.asarray(has_bug, dtype=bool) if eval_only_no_bug else np.ones(cols.n, dtype=bool)
+        report.top_k = S.top_k_summary(host["rank"][0][keep], host["rank"][1][keep], report.has_bug, report.scout, names, top_k)
     return report
 
 
@@ -489,10 +473,8 @@ def run(arguments):
     data_path = RichPath.create(arguments["TEST_DATA_PATH"])
     lim = None if arguments["--limit-num-elements"] is None else int(arguments["--limit-num-elements"])
     data = load_all_msgpack_l_gz(data_path, shuffle=True, limit_num_yielded_elements=lim)
-    if not torch.cuda.is_available():
-        raise RuntimeError("evaluate.py: no ROCm GPU visible; the BugLab hot path has no CPU fallback")
-    device = torch.device("cuda")
-    model, nn = GnnBugLabModel.restore_model(Path(arguments["MODEL_FILENAME"]), device)
+    require_gpu(None, "evaluate.py")
+    model, nn, device, _ = open_model(arguments["MODEL_FILENAME"])
     top_k = None if arguments.get("--top-k") is None else _checked_top_k(arguments["--top-k"])
     if arguments.get("--on-device"):
         report = evaluate_on_device(model, nn, data, device, assume_buggy=arguments["--assume-buggy"],

@@ -28,7 +28,7 @@ import argparse
 import json
 import sys
 from pathlib import Path
-from typing import Any, Dict, Iterable, List, NamedTuple
+from typing import Any, Dict, Iterable, List, NamedTuple, Optional
 
 if __package__ in (None, ""):
     sys.path.insert(0, str(Path(__file__).resolve().parents[2]))
@@ -122,12 +122,12 @@ class GreatEvaluation(NamedTuple):
 
 
 def evaluate_great(model, nn, data: Iterable[Any], device, *, minibatch_size: int = 30, parallelize: bool = True,
-                   on_device: bool = True) -> GreatEvaluation:
+                   on_device: bool = True, capacity: Optional[int] = None) -> GreatEvaluation:
     """Labelled records -> GreatEvaluation.  The samples are those a validation pass sees (`tensorize_for_prediction(...,
     labelled=True)` rejects what `tensorize` rejects), in input order, `minibatch_size` at a time.  `on_device`: the records of
-    all minibatches stay in one device buffer (72 bytes per sample, doubled when a stream of unknown length outgrows it) that is
-    copied back once, the run's only synchronisation.  Otherwise every minibatch's logits are copied back and judged by
-    `judge_great_host`.  Leaves `nn`'s training flag, metric counters and dropout step counter alone."""
+    all minibatches stay in one device buffer (`RunColumns`: 72 bytes per sample, `capacity` samples to start with, by default
+    `len(data)` or 1 << 14 for a stream) that is copied back once, the run's only synchronisation.  Otherwise every
+    minibatch's logits are copied back and judged by `judge_great_host`.  Leaves `nn`'s training flag, metric counters and dropout step counter alone."""
     from buglab.models import hip_ops
 
     device = torch.device(device)
@@ -139,15 +139,12 @@ def evaluate_great(model, nn, data: Iterable[Any], device, *, minibatch_size: in
     def rejected(_record):
         skipped[0] += 1
 
-    def buffers(capacity):  # [out_d | out_i] in one allocation: one copy back
-        blob = torch.empty((RECORD_D + RECORD_I // 2) * capacity, dtype=torch.float64, device=device)
-        return blob, blob[: RECORD_D * capacity].view(RECORD_D, capacity), blob[RECORD_D * capacity:].view(torch.int32).view(RECORD_I, capacity)
+    if on_device:  # [out_d | out_i] in one allocation: one copy back
+        from buglab.controllers import _batching as Bt
 
-    capacity = max(len(data), 1) if hasattr(data, "__len__") else 1 << 14
-    if on_device:
-        blob, out_d, out_i = buffers(capacity)
+        cols = Bt.RunColumns(device, Bt.run_capacity(capacity, data, 1 << 14),
+                             [("out_d", "float64", (RECORD_D, Bt.SAMPLES)), ("out_i", "int32", (RECORD_I, Bt.SAMPLES))])
     host_d, host_i = [], []
-    n = 0
     for mb, records in model.prediction_minibatches(data, device, parallelize, minibatch_size, labelled=True, rejected=rejected):
         B = len(records)
         for r in records:
@@ -155,12 +152,8 @@ def evaluate_great(model, nn, data: Iterable[Any], device, *, minibatch_size: in
             error_location.append(err)
             kinds.append(str(r.get("bug_kind_name") or "VARIABLE_MISUSE") if err != 0 else "NoBug")
         if on_device:
-            if n + B > capacity:  # a stream of unknown length: double, on the device
-                capacity = max(2 * capacity, n + B)
-                _, new_d, new_i = grown = buffers(capacity)
-                new_d[:, :n].copy_(out_d[:, :n]), new_i[:, :n].copy_(out_i[:, :n])
-                blob, out_d, out_i = grown
-            nn.predict_minibatch(mb, out_d, out_i, n)
+            n = cols.reserve(B)
+            nn.predict_minibatch(mb, cols["out_d"], cols["out_i"], n)
         else:
             scratch_d = torch.empty((RECORD_D, B), dtype=torch.float64, device=device)
             scratch_i = torch.empty((RECORD_I, B), dtype=torch.int32, device=device)
@@ -168,11 +161,8 @@ def evaluate_great(model, nn, data: Iterable[Any], device, *, minibatch_size: in
             h = mb["host"]
             d, i = judge_great_host(logits, mb["token_ids"].shape[1], h["lens_att"], h["error_locations"], h["target_mask"])
             host_d.append(d), host_i.append(i)
-        n += B
     if on_device:
-        host = blob.cpu()  # the one copy (and the one synchronisation) of the run
-        rec_d = host[: RECORD_D * capacity].view(RECORD_D, capacity)[:, :n].numpy()
-        rec_i = host[RECORD_D * capacity:].view(torch.int32).view(RECORD_I, capacity)[:, :n].numpy()
+        rec_d, rec_i = cols.to_host().values()  # the one copy (and the one synchronisation) of the run
     else:
         rec_d = np.concatenate(host_d, axis=1) if host_d else np.empty((RECORD_D, 0))
         rec_i = np.concatenate(host_i, axis=1) if host_i else np.empty((RECORD_I, 0), dtype=np.int32)
@@ -181,14 +171,12 @@ def evaluate_great(model, nn, data: Iterable[Any], device, *, minibatch_size: in
 
 def run(arguments):
     from buglab.models.traingreat import load_all_json_l_gz
-    from buglab.runtime.neuralmodel import AbstractNeuralModel
+    from buglab.models._cli import open_model, require_gpu
 
-    if not torch.cuda.is_available():
-        raise RuntimeError("evaluategreat.py: no ROCm GPU visible; the GREAT model has no CPU fallback")
-    device = torch.device("cuda")
+    require_gpu(None, "evaluategreat.py", "the GREAT model")
     lim = None if arguments.get("--limit-num-elements") is None else int(arguments["--limit-num-elements"])
     data = load_all_json_l_gz(arguments["TEST_DATA_PATH"], limit_num_yielded_elements=lim)
-    model, nn = AbstractNeuralModel.restore_model(Path(arguments["MODEL_FILENAME"]), device)
+    model, nn, device, _ = open_model(arguments["MODEL_FILENAME"])
     result = evaluate_great(model, nn, data, device, minibatch_size=int(arguments.get("--minibatch-size") or 30),
                             parallelize=not arguments.get("--sequential"), on_device=not arguments.get("--host-judge"))
     sys.stdout.write(result.format())

@@ -47,8 +47,9 @@ import torch
 
 from buglab.models import _explain as E
 from buglab.models import _suggest as S
+from buglab.models._cli import open_model, require_gpu, write_records
 from buglab.models._suggest import Ranked
-from buglab.models.suggest import suggestion_record, write_records
+from buglab.models.suggest import suggestion_record
 
 
 def node_kinds(graph, nodes: Iterable[int]) -> List[str]:
@@ -101,28 +102,6 @@ class Explanation(NamedTuple):
         return [{"label": a["label"], "kind": a["kind"], "share": a["share"]} for a in self.record()["attributions"]]
 
 
-# the run-long results, one fp64 allocation (one copy back): name -> (dtype, rows are [capacity, cols] or [rows, capacity])
-def _views(blob: torch.Tensor, capacity: int, k: int, R: int) -> Dict[str, torch.Tensor]:
-    half = lambda cells: (cells + 1) // 2
-    layout = (("score", None, (capacity, k)), ("sums", None, (2, capacity)), ("objective", None, (capacity,)),
-              ("baseline", None, (capacity,)), ("logprob", None, (capacity, R)), ("node", torch.int32, (capacity, k)),
-              ("entry", torch.int32, (capacity, R)), ("rank", torch.int32, (2, capacity)))
-    out, pos = {}, 0
-    for name, dtype, shape in layout:
-        cells = int(np.prod(shape))
-        size = cells if dtype is None else half(cells)
-        part = blob[pos:pos + size]
-        out[name] = (part if dtype is None else part.view(dtype)[:cells]).view(shape)
-        pos += size
-    assert pos <= blob.shape[0]
-    return out
-
-
-def _blob(capacity: int, k: int, R: int, device) -> torch.Tensor:
-    doubles = capacity * k + 4 * capacity + capacity * R + (capacity * k + 1) // 2 + (capacity * R + 1) // 2 + capacity
-    return torch.empty(doubles, dtype=torch.float64, device=device)
-
-
 def _chosen_on_device(entry: torch.Tensor, ix: Dict[str, torch.Tensor]) -> torch.Tensor:
     """_explain.chosen_flat_indices with device ops: int32 [B, 2]"""
     rw_off = ix["rw_off"].long()
@@ -138,7 +117,8 @@ def _chosen_on_device(entry: torch.Tensor, ix: Dict[str, torch.Tensor]) -> torch
     return torch.stack([first, torch.where(is_rw, ix["rw_idx"][at], minus)], dim=1)
 
 
-def _explain_run(model, nn, data, device, k, steps, rank, signed, assume_buggy, host, parallelize, rejected) -> Iterator[Explanation]:
+def _explain_run(model, nn, data, device, k, steps, rank, signed, assume_buggy, host, parallelize, rejected, capacity
+                 ) -> Iterator[Explanation]:
     from buglab.controllers import _batching as Bt
     from buglab.models import hip_ops
     from buglab.models._calibrate import apply_to_flat
@@ -154,13 +134,13 @@ def _explain_run(model, nn, data, device, k, steps, rank, signed, assume_buggy, 
         tensors = Bt.to_device_i32([getattr(six, f) for f in fields] + [eix.node_off], dev)
         return {"ix": dict(zip(fields + ("node_off",), tensors)), "points": points, "node_off": eix.node_off}
 
-    capacity = max(len(data), 1) if hasattr(data, "__len__") else 1 << 12
-    blob = _blob(capacity, k, R, device)
-    out = _views(blob, capacity, k, R)
+    one, per_k, per_rank, pair = (Bt.SAMPLES,), (Bt.SAMPLES, k), (Bt.SAMPLES, R), (2, Bt.SAMPLES)
+    out = Bt.RunColumns(device, Bt.run_capacity(capacity, data, 1 << 12),
+                        [("score", "float64", per_k), ("sums", "float64", pair), ("objective", "float64", one), ("baseline", "float64", one),
+                         ("logprob", "float64", per_rank), ("node", "int32", per_k), ("entry", "int32", per_rank), ("rank", "int32", pair)])
     points: List[Any] = []
     positions: List[int] = []
     host_parts: List[Any] = []  # --host: (node, score, sums) of every minibatch
-    n = 0
     nn.eval()
     with torch.no_grad(), model._tensorize_all_location_rewrites():
         for mb, tags in Bt.prediction_minibatches(model, ((d, i) for i, d in enumerate(data)), device, parallelize, extend, rejected,
@@ -168,15 +148,7 @@ def _explain_run(model, nn, data, device, k, steps, rank, signed, assume_buggy, 
             ix = mb["selfsup"]["ix"]
             B = len(mb["selfsup"]["points"])
             assert len(tags) == B
-            if n + B > capacity:  # a stream of unknown length: double, on the device
-                old, capacity = out, max(2 * capacity, n + B)
-                blob = _blob(capacity, k, R, device)
-                out = _views(blob, capacity, k, R)
-                for name, t in old.items():  # "sums" and "rank" are [2, capacity], the others [capacity, ..]
-                    if name in ("sums", "rank"):
-                        out[name][:, :n].copy_(t[:, :n])
-                    else:
-                        out[name][:n].copy_(t[:n])
+            n = out.reserve(B)
             # which entry: the ranking of suggest.py, on calibrated values where the checkpoint carries a calibration
             raw = E.flat_output(nn, mb)
             flat = raw
@@ -203,13 +175,12 @@ def _explain_run(model, nn, data, device, k, steps, rank, signed, assume_buggy, 
             else:
                 hip_ops.attribute_topk(score, ix["node_off"], out["node"], out["score"], out["sums"], n, k=k, by_abs=not signed)
             points.extend(mb["selfsup"]["points"]), positions.extend(tags)
-            n += B
-    got = {name: t.numpy() for name, t in _views(blob.cpu(), capacity, k, R).items()}  # the one copy (and synchronisation) of the run
+    got = out.to_host()  # the one copy (and the one synchronisation) of the run
     if host and host_parts:
         got["node"] = np.concatenate([p[0] for p in host_parts])
         got["score"] = np.concatenate([p[1] for p in host_parts])
         got["sums"] = np.concatenate([p[2] for p in host_parts], axis=1)
-    for b in range(n):
+    for b in range(out.n):
         listed = int((got["entry"][b] >= 0).sum())
         ranked = Ranked(got["entry"][b, :listed].tolist(), got["logprob"][b, :listed].tolist(), int(got["rank"][0, b]),
                         int(got["rank"][1, b]))
@@ -221,13 +192,14 @@ def _explain_run(model, nn, data, device, k, steps, rank, signed, assume_buggy, 
 
 def explain(model, nn, data: Iterable[Any], device, k: int = 10, *, steps: int = 1, rank: int = 0, signed: bool = False,
             assume_buggy: bool = False, host: bool = False, parallelize: bool = True,
-            rejected: Optional[Callable[[int], None]] = None) -> Iterator[Explanation]:
+            rejected: Optional[Callable[[int], None]] = None, capacity: Optional[int] = None) -> Iterator[Explanation]:
     """The node attributions of the suggestion at position `rank` of `suggest`'s ranking, for every datapoint of `data` that
     `tensorize` accepts, in input order; `rejected(position)` is called for the others.  Attributions are of the model's own
     log-probability of that entry (the raw output), not of the calibrated one; the ranking uses the calibrated values where the
     checkpoint carries a calibration.  `steps` 1: gradient x input; M > 1: integrated gradients over M midpoint steps from the
     zero input.  Graph models (gnn-mlp, ggnn) only: ensembles, the seq-* models and the GREAT var-misuse model are refused
-    before any GPU work.  Yields after the run's one copy back; every parameter's `.grad` and `requires_grad` is left as it was."""
+    before any GPU work.  Yields after the run's one copy back; every parameter's `.grad` and `requires_grad` is left as it was.
+    `capacity`: the samples the result buffers (`RunColumns`) start with, by default `len(data)`, or 1 << 12 for a stream."""
     E.require_graph_model(model, nn, "explain")
     if not 1 <= int(k) <= E.MAX_K:
         raise ValueError(f"explain: k must be in [1, {E.MAX_K}] (got {k})")
@@ -237,20 +209,17 @@ def explain(model, nn, data: Iterable[Any], device, k: int = 10, *, steps: int =
         raise ValueError(f"explain: rank must be in [0, {S.MAX_K - 1}] (got {rank})")
     rejected = rejected or (lambda position: None)
     return _explain_run(model, nn, data, device, int(k), int(steps), int(rank), bool(signed), bool(assume_buggy), bool(host),
-                        parallelize, rejected)
+                        parallelize, rejected, capacity)
 
 
 def run(arguments) -> int:
-    from buglab.models.gnn import GnnBugLabModel
     from buglab.runtime.richpath import RichPath
     from buglab.utils.msgpackutils import load_all_msgpack_l_gz
 
     lim = None if arguments["--limit-num-elements"] is None else int(arguments["--limit-num-elements"])
-    data = load_all_msgpack_l_gz(RichPath.create(arguments["DATA_PATH"]), shuffle=False, limit_num_yielded_elements=lim)
-    if not torch.cuda.is_available():
-        raise RuntimeError("explain.py: no ROCm GPU visible; the BugLab hot path has no CPU fallback")
-    device = torch.device("cuda")
-    model, nn = GnnBugLabModel.restore_model(Path(arguments["MODEL_FILENAME"]), device)
+    data = load_all_msgpack_l_gz(RichPath.create(arguments["DATA_PATH"]), shuffle=False, limit_num_yielded_elements=lim)  # a stream
+    require_gpu(None, "explain.py")
+    model, nn, device, _ = open_model(arguments["MODEL_FILENAME"])
     refused: List[int] = []
     found = explain(model, nn, data, device, int(arguments["--top-k"]), steps=int(arguments["--steps"]), rank=int(arguments["--rank"]),
                     signed=bool(arguments.get("--signed")), assume_buggy=bool(arguments.get("--assume-buggy")),

@@ -32,9 +32,7 @@ triples of `model.predict` through the NumPy twin (buglab/models/_fdr.py).  Exit
 from __future__ import annotations
 
 import argparse
-import json
 import sys
-from collections import deque
 from pathlib import Path
 from typing import Any, Callable, Dict, Iterable, List, NamedTuple, Optional, Tuple
 
@@ -44,6 +42,7 @@ if __package__ in (None, ""):
 import numpy as np
 
 from buglab.models import _fdr as F
+from buglab.models._cli import open_model, read_data, require_gpu, write_records, write_report_json
 from buglab.models._fdr import NullReference
 
 EXIT_NO_REFERENCE = 2
@@ -65,23 +64,11 @@ class _Scores(NamedTuple):
 
 def _scores_host(model, nn, tagged: Iterable[Tuple[Any, int]], device, parallelize: bool, ref: np.ndarray,
                  rejected: Callable[[int], None]) -> _Scores:
-    pending: "deque" = deque()  # (position, datapoint) of what went in and has not come out: `predict` keeps the input order
-
-    def tracked():
-        for point, position in tagged:
-            pending.append((position, point))
-            yield point
+    from buglab.controllers._batching import predictions_in_order
 
     positions, labels, values = [], [], []
-    for point, location_logprobs, _ in model.predict(tracked(), nn, device, parallelize):
-        while True:
-            position, sent = pending.popleft()
-            if sent is point:
-                break
-            rejected(position)
+    for position, point, location_logprobs, _ in predictions_in_order(model, nn, tagged, device, parallelize, rejected, "fdr: predict"):
         positions.append(position), labels.append(_label(point)), values.append(location_logprobs[-1])
-    for position, _ in pending:
-        rejected(position)
     src = np.asarray(values, np.float32)  # the fp32 values `predict` copied back, as they were
     score, count = F.counts_host(src, np.arange(src.shape[0]), ref)
     return _Scores(positions, labels, score, count)
@@ -101,33 +88,20 @@ def _scores_on_device(model, nn, tagged: Iterable[Tuple[Any, int]], device, para
         nobug = np.asarray(layout.loc_idx, np.int64)[np.asarray(layout.loc_off, np.int64)[1:] - 1]  # NO_BUG: a sample's last entry
         return {"nobug_idx": Bt.to_device_i32([nobug], dev)[0], "labels": [_label(p) for p in points]}
 
-    def buffers(cap):  # [scores | counts] in one allocation: one copy back
-        blob = torch.empty(2 * cap, dtype=torch.int32, device=device)
-        return blob, blob[:cap].view(torch.float32), blob[cap:]
-
-    capacity = max(int(capacity), 1)
-    blob, score, count = buffers(capacity)
+    cols = Bt.RunColumns(device, capacity, [("score", "float32", (Bt.SAMPLES,)), ("count", "int32", (Bt.SAMPLES,))])
     positions: List[int] = []
     labels: List[Optional[bool]] = []
-    n = 0
     nn.eval()
     with torch.no_grad(), model._tensorize_all_location_rewrites():
         for mb, tags in Bt.prediction_minibatches(model, tagged, device, parallelize, extend, rejected):
             flat = Bt.flat_prediction_output(nn, mb)
             B = len(tags)
             assert mb["selfsup"]["nobug_idx"].shape[0] == B
-            if n + B > capacity:  # a stream of unknown length: double, on the device
-                old, capacity = (score, count), max(2 * capacity, n + B)
-                blob, score, count = buffers(capacity)
-                score[:n].copy_(old[0][:n]), count[:n].copy_(old[1][:n])
-            hip_ops.fdr_counts(flat, mb["selfsup"]["nobug_idx"], d_ref, score, count, n)
+            n = cols.reserve(B)
+            hip_ops.fdr_counts(flat, mb["selfsup"]["nobug_idx"], d_ref, cols["score"], cols["count"], n)
             positions.extend(tags), labels.extend(mb["selfsup"]["labels"])
-            n += B
-    return _Scores(positions, labels, score[:n], count[:n])
-
-
-def _capacity(data) -> int:
-    return max(len(data), 1) if hasattr(data, "__len__") else 1 << 14
+    found = cols.device_columns()
+    return _Scores(positions, labels, found["score"], found["count"])
 
 
 def fit_null_reference(model, nn, data: Iterable[Any], device, *, max_reference: int = F.MAX_REFERENCE, parallelize: bool = True,
@@ -152,7 +126,7 @@ def fit_null_reference(model, nn, data: Iterable[Any], device, *, max_reference:
 
     anything = np.zeros(1, np.float32)  # the counts of a fit are not used: any reference serves
     run = _scores_host if host else _scores_on_device
-    extra = () if host else (_capacity(data),)
+    extra = () if host else (Bt.run_capacity(None, data, 1 << 14),)
     found = run(model, nn, clean(), device, parallelize, anything, lambda position: None, *extra)
     scores = found.score if host else found.score.cpu().numpy()  # the one copy (and the one synchronisation) of the run
     reference = F.make_null_reference(scores, max_reference, skipped[0], getattr(model, "confidence_calibration", None))
@@ -210,7 +184,8 @@ def scan_with_fdr(model, nn, data: Iterable[Any], device, q: float = 0.1, *, dep
     if host:
         found = _scores_host(model, nn, tagged, device, parallelize, reference.scores, refused.append)
     else:
-        found = _scores_on_device(model, nn, tagged, device, parallelize, reference.scores, refused.append, _capacity(data))
+        found = _scores_on_device(model, nn, tagged, device, parallelize, reference.scores, refused.append,
+                                  Bt.run_capacity(None, data, 1 << 14))
     N = len(found.positions)
     q_effective = F.effective_level(q, N, dependence) if N else float(q)
     if N == 0:
@@ -286,26 +261,15 @@ def parse_args(argv=None) -> argparse.Namespace:
 
 
 def run(args: argparse.Namespace) -> int:
-    import torch
-
-    from buglab.models.suggest import write_records
-    from buglab.runtime.neuralmodel import AbstractNeuralModel
-    from buglab.runtime.richpath import RichPath
-    from buglab.utils.msgpackutils import load_all_msgpack_l_gz
-
-    have_gpu = torch.cuda.is_available()
-    device = torch.device("cuda" if have_gpu else "cpu")
-    model, nn = AbstractNeuralModel.restore_model(Path(args.MODEL), device)
+    model, nn, device, have_gpu = open_model(args.MODEL)
     if args.command == "scan":  # before anything is read or run: a checkpoint without a reference is the caller's mistake
         try:
             F.check_reference(getattr(model, "null_reference", None), getattr(model, "confidence_calibration", None), "fdr scan")
         except LookupError as e:
             print(str(e), file=sys.stderr)
             return EXIT_NO_REFERENCE
-    if not have_gpu:
-        raise RuntimeError("fdr: no ROCm GPU visible; the BugLab hot path has no CPU fallback")
-    path = args.CLEAN_DATA if args.command == "fit" else args.DATA
-    data = list(load_all_msgpack_l_gz(RichPath.create(path), shuffle=False, limit_num_yielded_elements=args.limit_num_elements))
+    require_gpu(have_gpu, "fdr")
+    data = read_data(args.CLEAN_DATA if args.command == "fit" else args.DATA, args.limit_num_elements)
     if args.command == "fit":
         reference = fit_null_reference(model, nn, data, device, max_reference=args.max_reference, parallelize=not args.sequential)
         print(f"fdr fit: kept {reference.num_kept} clean scores ({reference.num_dropped_nan} NaN dropped, {reference.num_skipped_buggy} "
@@ -319,9 +283,7 @@ def run(args: argparse.Namespace) -> int:
     if args.html is not None:
         with open(args.html, "w", encoding="utf-8") as f:
             f.write(found.html)
-    if args.report_json is not None:
-        with open(args.report_json, "w", encoding="utf-8") as f:
-            f.write(json.dumps(found.summary, indent=1, sort_keys=True) + "\n")
+    write_report_json(args.report_json, found.summary)
     return 0
 
 

@@ -30,7 +30,6 @@ arithmetic: include/buglab_hip.h).  `--host` runs the NumPy twin (buglab/models/
 from __future__ import annotations
 
 import argparse
-import json
 import logging
 import sys
 from pathlib import Path
@@ -43,6 +42,7 @@ import numpy as np
 
 from buglab.models import _group as G
 from buglab.models import _similar as S
+from buglab.models._cli import open_model, read_data, require_gpu, write_records, write_report_json
 from buglab.models._group import Grouping, WarningGroup, WarningGroups
 from buglab.models._similar import SiteEmbeddings, SiteIndex
 
@@ -207,18 +207,10 @@ def parse_args(argv=None) -> argparse.Namespace:
 
 
 def run(args: argparse.Namespace) -> int:
-    import torch
-
     from buglab.models import similar
-    from buglab.models.suggest import write_records
-    from buglab.runtime.neuralmodel import AbstractNeuralModel
-    from buglab.runtime.richpath import RichPath
-    from buglab.utils.msgpackutils import load_all_msgpack_l_gz
 
     G.thresholds(args.similarity)
-    have_gpu = torch.cuda.is_available()
-    device = torch.device("cuda" if have_gpu else "cpu")
-    model, nn = AbstractNeuralModel.restore_model(Path(args.MODEL), device)
+    model, nn, device, have_gpu = open_model(args.MODEL)
     index = None
     if args.index is not None:  # before anything is read or run: an index of another model's embeddings is the caller's mistake
         index = SiteIndex.load(args.index)
@@ -227,9 +219,8 @@ def run(args: argparse.Namespace) -> int:
         except S.DimensionMismatch as e:
             print(str(e), file=sys.stderr)
             return EXIT_DIMENSION_MISMATCH
-    if not have_gpu:
-        raise RuntimeError("group: no ROCm GPU visible; the BugLab hot path has no CPU fallback")
-    data = list(load_all_msgpack_l_gz(RichPath.create(args.DATA), shuffle=False, limit_num_yielded_elements=args.limit_num_elements))
+    require_gpu(have_gpu, "group")
+    data = read_data(args.DATA, args.limit_num_elements)
     found = group_warnings(model, nn, data, device, args.similarity, site=args.site, assume_buggy=args.assume_buggy,
                            min_confidence=args.min_confidence, center=not args.no_center, index=index, candidates=args.candidates,
                            min_group_size=args.min_group_size, host=args.host, parallelize=not args.sequential)
@@ -238,9 +229,7 @@ def run(args: argparse.Namespace) -> int:
     print(f"group: {s['num_warnings']} warnings of {s['num_samples']} samples in {s['num_groups']} groups at similarity "
           f"{s['similarity']} ({s['num_singletons']} singletons, the largest of {s['largest_group']}; {s['num_edges']} links among "
           f"{s['num_candidates']} candidate pairs); {100.0 * s['spared']:.1f}% of the warnings spared.")
-    if args.report_json is not None:
-        with open(args.report_json, "w", encoding="utf-8") as f:
-            f.write(json.dumps(s, indent=1, sort_keys=True) + "\n")
+    write_report_json(args.report_json, s)
     return 0
 
 

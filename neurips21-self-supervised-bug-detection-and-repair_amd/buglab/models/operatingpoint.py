@@ -24,7 +24,6 @@ replicate, over the draws of buglab/models/compare.py's bootstrap (the contract 
 from __future__ import annotations
 
 import argparse
-import json
 import sys
 from pathlib import Path
 from typing import Any, Dict, Iterable, List, Optional, Sequence
@@ -202,17 +201,11 @@ def parse_args(argv=None) -> argparse.Namespace:
 
 
 def run(args: argparse.Namespace) -> Optional[OperatingPoint]:
-    import torch
+    from buglab.models._cli import open_model, read_data, require_gpu, write_report_json
 
-    from buglab.runtime.neuralmodel import AbstractNeuralModel
-    from buglab.runtime.richpath import RichPath
-    from buglab.utils.msgpackutils import load_all_msgpack_l_gz
-
-    if not torch.cuda.is_available():
-        raise RuntimeError("operatingpoint: no ROCm GPU visible; the BugLab hot path has no CPU fallback")
-    device = torch.device("cuda")
-    model, nn = AbstractNeuralModel.restore_model(Path(args.MODEL), device)
-    data = list(load_all_msgpack_l_gz(RichPath.create(args.VALID_DATA), shuffle=False, limit_num_yielded_elements=args.limit_num_elements))
+    require_gpu(None, "operatingpoint")
+    model, nn, device, _ = open_model(args.MODEL)
+    data = read_data(args.VALID_DATA, args.limit_num_elements)
     details: Dict[str, Any] = {}
     point = fit_operating_point(model, nn, data, device, target_precision=args.target_precision, curve=args.curve,
                                 confidence=args.confidence, num_replicates=args.num_replicates, seed=args.seed, max_bins=args.max_bins,
@@ -221,9 +214,7 @@ def run(args: argparse.Namespace) -> Optional[OperatingPoint]:
     sys.stdout.write(format_details(details))
     if point is None:  # nothing is written: neither the checkpoint nor the report
         return None
-    if args.report_json is not None:
-        with open(args.report_json, "w", encoding="utf-8") as f:
-            f.write(json.dumps(details, indent=1, sort_keys=True) + "\n")
+    write_report_json(args.report_json, details)
     model.save(Path(args.OUT_MODEL), nn)
     return point
 

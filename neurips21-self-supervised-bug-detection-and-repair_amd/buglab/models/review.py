@@ -40,11 +40,10 @@ include/buglab_hip.h).  `--host` runs the NumPy twin (buglab/models/_review.py);
 from __future__ import annotations
 
 import argparse
-import json
 import logging
 import sys
 from pathlib import Path
-from typing import Any, Dict, Iterable, List, Optional, Sequence, Tuple
+from typing import Any, Iterable, List, Optional, Sequence
 
 if __package__ in (None, ""):
     sys.path.insert(0, str(Path(__file__).resolve().parents[2]))
@@ -53,6 +52,8 @@ import numpy as np
 
 from buglab.models import _review as R
 from buglab.models import _similar as S
+from buglab.models._cli import embed_sites as _embed_sites, embedding_dim as _embedding_dim, open_model as _open_model
+from buglab.models._cli import read_data as _read_data, require_gpu, write_records, write_report_json
 from buglab.models._review import QueuedWarning, ReviewQueue, Selection
 from buglab.models._similar import SiteEmbeddings, SiteIndex
 
@@ -266,18 +267,6 @@ def review_sites(sites: SiteEmbeddings, budget: int, *, reviewed: Optional[SiteI
     return ReviewQueue(out, summary)
 
 
-def _embed_sites(model, nn, data, device, site: str, **options) -> SiteEmbeddings:
-    from buglab.models import similar
-
-    return similar.embed_sites(model, nn, data, device, site, **options)
-
-
-def _embedding_dim(nn) -> int:
-    from buglab.models import similar
-
-    return similar.embedding_dim(nn)
-
-
 def review_queue(model, nn, data: Iterable[Any], device, budget: int, reviewed: Optional[SiteIndex] = None, triage=None, *,
                  band: Sequence[float] = DEFAULT_BAND, max_similarity: float = 1.0, min_confidence: Optional[float] = None,
                  site: str = "predicted", assume_buggy: bool = False, center: bool = True, host: bool = False,
@@ -333,28 +322,8 @@ def parse_args(argv=None) -> argparse.Namespace:
     return args
 
 
-def _open_model(path: str) -> Tuple[Any, Any, Any, bool]:
-    import torch
-
-    from buglab.runtime.neuralmodel import AbstractNeuralModel
-
-    have_gpu = torch.cuda.is_available()
-    device = torch.device("cuda" if have_gpu else "cpu")
-    model, nn = AbstractNeuralModel.restore_model(Path(path), device)
-    return model, nn, device, have_gpu
-
-
-def _read_data(path: str, limit: Optional[int]) -> List[Any]:
-    from buglab.runtime.richpath import RichPath
-    from buglab.utils.msgpackutils import load_all_msgpack_l_gz
-
-    return list(load_all_msgpack_l_gz(RichPath.create(path), shuffle=False, limit_num_yielded_elements=limit))
-
-
 def run(args: argparse.Namespace) -> int:
     from buglab.models._triage import TriageModel
-    from buglab.models.suggest import write_records
-
     R.stop_of(args.max_similarity)
     model, nn, device, have_gpu = _open_model(args.MODEL)
     reviewed = triage = None
@@ -370,8 +339,7 @@ def run(args: argparse.Namespace) -> int:
     except S.DimensionMismatch as e:
         print(str(e), file=sys.stderr)
         return EXIT_DIMENSION_MISMATCH
-    if not have_gpu:
-        raise RuntimeError("review: no ROCm GPU visible; the BugLab hot path has no CPU fallback")
+    require_gpu(have_gpu, "review")
     data = _read_data(args.DATA, args.limit_num_elements)
     queue = review_queue(model, nn, data, device, args.budget, reviewed, triage, band=args.uncertainty_band or DEFAULT_BAND,
                          max_similarity=args.max_similarity, min_confidence=args.min_confidence, site=args.site,
@@ -385,9 +353,7 @@ def run(args: argparse.Namespace) -> int:
           f"has cosine {text(worst)} to something reviewed or queued; {text(other)} had the {s['budget']} most confident been "
           f"reviewed instead" + ("" if s["beats_most_confident"] is None else
                                  (": the queue covers better." if s["beats_most_confident"] else ": the queue does not cover better.")))
-    if args.report_json is not None:
-        with open(args.report_json, "w", encoding="utf-8") as f:
-            f.write(json.dumps(s, indent=1, sort_keys=True) + "\n")
+    write_report_json(args.report_json, s)
     return 0
 
 

@@ -36,11 +36,10 @@ the rest in the NumPy twin (buglab/models/_similar.py).
 from __future__ import annotations
 
 import argparse
-import json
 import logging
 import sys
 from pathlib import Path
-from typing import Any, Callable, Dict, Iterable, Iterator, List, NamedTuple, Optional, Tuple
+from typing import Any, Dict, Iterable, Iterator, List, NamedTuple, Optional, Tuple
 
 if __package__ in (None, ""):
     sys.path.insert(0, str(Path(__file__).resolve().parents[2]))
@@ -48,6 +47,7 @@ if __package__ in (None, ""):
 import numpy as np
 
 from buglab.models import _similar as S
+from buglab.models._cli import open_model, read_data, require_gpu, write_records, write_report_json
 from buglab.models._similar import Neighbours, SiteEmbeddings, SiteIndex
 
 LOGGER = logging.getLogger(__name__)
@@ -105,12 +105,13 @@ def _collect_sites(model, nn, data: Iterable[Any], device, site: str, assume_bug
         loc_idx, loc_off, truth = arrays if host else Bt.to_device_i32(arrays, dev)
         return {"loc_idx": loc_idx, "loc_off": loc_off, "truth": truth, "points": points}
 
-    capacity = max(int(capacity if capacity is not None else (len(data) if hasattr(data, "__len__") else 1 << 12)), 1)
+    cols = None if host else Bt.RunColumns(device, Bt.run_capacity(capacity, data, 1 << 12),
+                                           [("rows", "float32", (Bt.SAMPLES, embedding_dim(nn))), ("place", "int32", (Bt.SAMPLES,)),
+                                            ("logprob", "float32", (Bt.SAMPLES,))])
     rows = place = logprob = None
     host_parts: List[Tuple[np.ndarray, np.ndarray, np.ndarray]] = []
     positions: List[int] = []
     points: List[Any] = []
-    n = 0
     nn.eval()
     with torch.no_grad(), model._tensorize_all_location_rewrites():
         for mb, tags in Bt.prediction_minibatches(model, tagged(), device, parallelize, extend, refused.append):
@@ -123,21 +124,14 @@ def _collect_sites(model, nn, data: Iterable[Any], device, site: str, assume_bug
                 host_parts.append(S.embed_sites_host(flat.cpu().numpy(), ix["loc_idx"], ix["loc_off"], np.arange(h_cand.shape[0]), h_cand,
                                                      site, truth, assume_buggy))
             else:
-                if rows is None or n + B > capacity:  # a stream of unknown length: double, on the device
-                    old, capacity = (rows, place, logprob), max(2 * capacity, n + B) if rows is not None else max(capacity, B)
-                    rows = torch.empty((capacity, h.shape[1]), dtype=torch.float32, device=device)
-                    place = torch.empty(capacity, dtype=torch.int32, device=device)
-                    logprob = torch.empty(capacity, dtype=torch.float32, device=device)
-                    if old[0] is not None:
-                        rows[:n].copy_(old[0][:n]), place[:n].copy_(old[1][:n]), logprob[:n].copy_(old[2][:n])
-                hip_ops.similar_embed_sites(flat, ix["loc_idx"], ix["loc_off"], cand, h, rows, place, logprob, n, mode=site, truth=truth,
-                                            skip_nobug=assume_buggy)
+                n = cols.reserve(B)
+                hip_ops.similar_embed_sites(flat, ix["loc_idx"], ix["loc_off"], cand, h, cols["rows"], cols["place"], cols["logprob"], n,
+                                            mode=site, truth=truth, skip_nobug=assume_buggy)
             positions.extend(tags), points.extend(ix["points"])
-            n += B
     if host and host_parts:
         rows, place, logprob = (np.concatenate([p[i] for p in host_parts]) for i in range(3))
-    elif rows is not None:
-        rows, place, logprob = rows[:n], place[:n], logprob[:n]
+    elif positions:  # (nothing accepted: no rows, as on the host path)
+        rows, place, logprob = cols.device_columns().values()
     return _Sites(positions, points, rows, place, logprob, seen[0], len(refused))
 
 
@@ -291,16 +285,7 @@ def parse_args(argv=None) -> argparse.Namespace:
 
 
 def run(args: argparse.Namespace) -> int:
-    import torch
-
-    from buglab.models.suggest import write_records
-    from buglab.runtime.neuralmodel import AbstractNeuralModel
-    from buglab.runtime.richpath import RichPath
-    from buglab.utils.msgpackutils import load_all_msgpack_l_gz
-
-    have_gpu = torch.cuda.is_available()
-    device = torch.device("cuda" if have_gpu else "cpu")
-    model, nn = AbstractNeuralModel.restore_model(Path(args.MODEL), device)
+    model, nn, device, have_gpu = open_model(args.MODEL)
     if args.command == "query":  # before anything is read or run: an index of another model's embeddings is the caller's mistake
         index = SiteIndex.load(args.INDEX)
         try:
@@ -308,9 +293,8 @@ def run(args: argparse.Namespace) -> int:
         except S.DimensionMismatch as e:
             print(str(e), file=sys.stderr)
             return EXIT_DIMENSION_MISMATCH
-    if not have_gpu:
-        raise RuntimeError("similar: no ROCm GPU visible; the BugLab hot path has no CPU fallback")
-    data = list(load_all_msgpack_l_gz(RichPath.create(args.DATA), shuffle=False, limit_num_yielded_elements=args.limit_num_elements))
+    require_gpu(have_gpu, "similar")
+    data = read_data(args.DATA, args.limit_num_elements)
     options = dict(assume_buggy=args.assume_buggy, host=args.host, parallelize=not args.sequential)
     if args.command == "index":
         index = build_site_index(model, nn, data, device, args.site, args.tag, not args.no_center, **options)
@@ -323,9 +307,7 @@ def run(args: argparse.Namespace) -> int:
     s = found.summary
     print(f"similar query: {s['num_with_site']} of {s['num_samples']} samples have a site ({s['num_rejected']} rejected, "
           f"{s['num_invalid_embeddings']} invalid embeddings); {s['num_with_neighbours']} have neighbours.")
-    if args.report_json is not None:
-        with open(args.report_json, "w", encoding="utf-8") as f:
-            f.write(json.dumps(s, indent=1, sort_keys=True) + "\n")
+    write_report_json(args.report_json, s)
     return 0
 
 

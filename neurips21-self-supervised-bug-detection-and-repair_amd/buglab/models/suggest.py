@@ -27,11 +27,8 @@ A suggestion's `rank` 0 is not what evaluate.py calls a repaired sample: that ta
 location, this ranks the products.
 """
 import argparse
-import gzip
-import json
 import math
 import sys
-from collections import deque
 from pathlib import Path
 from typing import Any, Callable, Dict, Iterable, Iterator, List, NamedTuple, Optional
 
@@ -41,6 +38,7 @@ if __package__ in (None, ""):
 import torch
 
 from buglab.models import _suggest as S
+from buglab.models._cli import open_model, require_gpu, write_records  # noqa: F401  (write_records: imported from here too)
 from buglab.models._suggest import Ranked
 
 
@@ -87,25 +85,15 @@ def suggestion_record(position: int, datapoint, ranked: Ranked, min_probability:
 
 
 def _suggest_host(model, nn, data, device, k, assume_buggy, parallelize, rejected) -> Iterator[Suggestions]:
-    pending: "deque" = deque()  # (position, datapoint) of what went in and has not come out: `predict` keeps the input order
+    from buglab.controllers._batching import predictions_in_order
 
-    def tracked():
-        for position, point in enumerate(data):
-            pending.append((position, point))
-            yield point
-
-    for point, location_logprobs, rewrite_logprobs in model.predict(tracked(), nn, device, parallelize):
-        while True:
-            position, sent = pending.popleft()
-            if sent is point:
-                break
-            rejected(position)
+    tagged = ((point, position) for position, point in enumerate(data))
+    for position, point, location_logprobs, rewrite_logprobs in predictions_in_order(model, nn, tagged, device, parallelize, rejected,
+                                                                                     "suggest: predict"):
         yield Suggestions(position, point, S.suggestions_of_prediction(point, location_logprobs, rewrite_logprobs, k, assume_buggy))
-    for position, _ in pending:
-        rejected(position)
 
 
-def _suggest_on_device(model, nn, data, device, k, assume_buggy, parallelize, rejected) -> Iterator[Suggestions]:
+def _suggest_on_device(model, nn, data, device, k, assume_buggy, parallelize, rejected, capacity) -> Iterator[Suggestions]:
     from buglab.controllers import _batching as Bt
     from buglab.models import hip_ops
 
@@ -117,17 +105,10 @@ def _suggest_on_device(model, nn, data, device, k, assume_buggy, parallelize, re
         fields = hip_ops.SUGGEST_INDEX_FIELDS
         return {"ix": dict(zip(fields, Bt.to_device_i32([getattr(ix, f) for f in fields], dev))), "points": points}
 
-    def buffers(capacity):  # [log-probabilities | entries | the two rank rows] in one allocation: one copy back
-        cells = capacity * k
-        blob = torch.empty(cells + (cells + 1) // 2 + capacity, dtype=torch.float64, device=device)
-        return blob, blob[cells + (cells + 1) // 2:].view(torch.int32).view(2, capacity), \
-            blob[cells:cells + (cells + 1) // 2].view(torch.int32)[:cells].view(capacity, k), blob[:cells].view(capacity, k)
-
-    capacity = max(len(data), 1) if hasattr(data, "__len__") else 1 << 14
-    blob, rank, entry, logprob = buffers(capacity)
+    cols = Bt.RunColumns(device, Bt.run_capacity(capacity, data, 1 << 14),
+                         [("logprob", "float64", (Bt.SAMPLES, k)), ("entry", "int32", (Bt.SAMPLES, k)), ("rank", "int32", (2, Bt.SAMPLES))])
     points: List[Any] = []
     positions: List[int] = []
-    n = 0
     nn.eval()
     with torch.no_grad(), model._tensorize_all_location_rewrites():
         for mb, tags in Bt.prediction_minibatches(model, ((d, i) for i, d in enumerate(data)), device, parallelize, extend, rejected,
@@ -135,60 +116,43 @@ def _suggest_on_device(model, nn, data, device, k, assume_buggy, parallelize, re
             flat = Bt.flat_prediction_output(nn, mb)
             B = len(mb["selfsup"]["points"])
             assert len(tags) == B
-            if n + B > capacity:  # a stream of unknown length: double, on the device
-                old, capacity = (rank, entry, logprob), max(2 * capacity, n + B)
-                blob, rank, entry, logprob = buffers(capacity)
-                rank[:, :n].copy_(old[0][:, :n]), entry[:n].copy_(old[1][:n]), logprob[:n].copy_(old[2][:n])
-            hip_ops.rank_suggestions(flat, mb["selfsup"]["ix"], rank, entry, logprob, n, k=k, skip_nobug=assume_buggy)
+            n = cols.reserve(B)
+            hip_ops.rank_suggestions(flat, mb["selfsup"]["ix"], cols["rank"], cols["entry"], cols["logprob"], n, k=k,
+                                     skip_nobug=assume_buggy)
             points.extend(mb["selfsup"]["points"]), positions.extend(tags)
-            n += B
-    host = blob.cpu()  # the one copy (and the one synchronisation) of the run
-    cells = capacity * k
-    logprob = host[:cells].view(capacity, k)[:n].numpy()
-    entry = host[cells:cells + (cells + 1) // 2].view(torch.int32)[:cells].view(capacity, k)[:n].numpy()
-    rank = host[cells + (cells + 1) // 2:].view(torch.int32).view(2, capacity)[:, :n].numpy()
-    for b in range(n):
+    host = cols.to_host()  # the one copy (and the one synchronisation) of the run
+    logprob, entry, rank = host["logprob"], host["entry"], host["rank"]
+    for b in range(cols.n):
         listed = int((entry[b] >= 0).sum())
         yield Suggestions(positions[b], points[b], Ranked(entry[b, :listed].tolist(), logprob[b, :listed].tolist(), int(rank[0, b]),
                                                           int(rank[1, b])))
 
 
 def suggest(model, nn, data: Iterable[Any], device, k: int = 5, *, host: bool = False, assume_buggy: bool = False,
-            parallelize: bool = True, rejected: Optional[Callable[[int], None]] = None) -> Iterator[Suggestions]:
+            parallelize: bool = True, rejected: Optional[Callable[[int], None]] = None, capacity: Optional[int] = None
+            ) -> Iterator[Suggestions]:
     """The ranked suggestions of every datapoint of `data` that `tensorize` accepts, in input order; `rejected(position)` is
     called for the others.  On the device unless `host` is set or `model` is an ensemble (`EnsembleWrapper`), which
-    `require_single_model` refuses there.  The device path yields after the run's one copy back."""
+    `require_single_model` refuses there.  The device path yields after the run's one copy back; `capacity`: the samples its
+    buffers (`RunColumns`) start with, by default `len(data)`, or 1 << 14 for a stream."""
     from buglab.models.ensemble.wrapper import EnsembleWrapper
 
     if not 1 <= int(k) <= S.MAX_K:
         raise ValueError(f"suggest: k must be in [1, {S.MAX_K}] (got {k})")
     rejected = rejected or (lambda position: None)
-    run = _suggest_host if host or isinstance(model, EnsembleWrapper) else _suggest_on_device
-    return run(model, nn, data, device, int(k), bool(assume_buggy), parallelize, rejected)
-
-
-def write_records(records: Iterable[Dict[str, Any]], out_path) -> int:
-    out_path = str(out_path)
-    opened = gzip.open(out_path, "wt", encoding="utf-8") if out_path.endswith(".gz") else open(out_path, "w", encoding="utf-8")
-    count = 0
-    with opened as f:
-        for record in records:
-            f.write(json.dumps(record, sort_keys=True) + "\n")
-            count += 1
-    return count
+    if host or isinstance(model, EnsembleWrapper):
+        return _suggest_host(model, nn, data, device, int(k), bool(assume_buggy), parallelize, rejected)
+    return _suggest_on_device(model, nn, data, device, int(k), bool(assume_buggy), parallelize, rejected, capacity)
 
 
 def run(arguments) -> int:
-    from buglab.models.gnn import GnnBugLabModel
     from buglab.runtime.richpath import RichPath
     from buglab.utils.msgpackutils import load_all_msgpack_l_gz
 
     lim = None if arguments["--limit-num-elements"] is None else int(arguments["--limit-num-elements"])
-    data = load_all_msgpack_l_gz(RichPath.create(arguments["DATA_PATH"]), shuffle=False, limit_num_yielded_elements=lim)
-    if not torch.cuda.is_available():
-        raise RuntimeError("suggest.py: no ROCm GPU visible; the BugLab hot path has no CPU fallback")
-    device = torch.device("cuda")
-    model, nn = GnnBugLabModel.restore_model(Path(arguments["MODEL_FILENAME"]), device)
+    data = load_all_msgpack_l_gz(RichPath.create(arguments["DATA_PATH"]), shuffle=False, limit_num_yielded_elements=lim)  # a stream
+    require_gpu(None, "suggest.py")
+    model, nn, device, _ = open_model(arguments["MODEL_FILENAME"])
     min_probability = None if arguments.get("--min-probability") is None else float(arguments["--min-probability"])
     refused: List[int] = []
     found = suggest(model, nn, data, device, int(arguments["--top-k"]), host=bool(arguments.get("--host")),

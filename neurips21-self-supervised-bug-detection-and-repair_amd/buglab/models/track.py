@@ -48,11 +48,10 @@ the same bytes.
 from __future__ import annotations
 
 import argparse
-import json
 import logging
 import sys
 from pathlib import Path
-from typing import Any, Iterable, List, Optional, Sequence, Tuple
+from typing import Any, Iterable, List, Optional, Sequence
 
 if __package__ in (None, ""):
     sys.path.insert(0, str(Path(__file__).resolve().parents[2]))
@@ -62,6 +61,8 @@ import numpy as np
 from buglab.models import _review as R
 from buglab.models import _similar as S
 from buglab.models import _track as T
+from buglab.models._cli import embed_sites as _embed_sites, embedding_dim as _embedding_dim, open_model as _open_model
+from buglab.models._cli import read_data as _read_data, require_gpu, write_records, write_report_json
 from buglab.models._similar import SiteEmbeddings, SiteIndex
 from buglab.models._track import Matching, TrackedScan, TrackedWarning
 
@@ -210,18 +211,6 @@ def track_sites(sites: SiteEmbeddings, index: SiteIndex, *, min_similarity: floa
     return TrackedScan(listed, summary, new_index, hidden)
 
 
-def _embed_sites(model, nn, data, device, site: str, **options) -> SiteEmbeddings:
-    from buglab.models import similar
-
-    return similar.embed_sites(model, nn, data, device, site, **options)
-
-
-def _embedding_dim(nn) -> int:
-    from buglab.models import similar
-
-    return similar.embedding_dim(nn)
-
-
 def track_warnings(model, nn, index: SiteIndex, data: Iterable[Any], device, min_similarity: float = 0.9, within: str = "none", *,
                    site: str = "predicted", assume_buggy: bool = False, min_confidence: Optional[float] = None,
                    hide_tags: Sequence[str] = (), tag: Optional[str] = None, max_rounds: Optional[int] = None, host: bool = False,
@@ -275,27 +264,7 @@ def parse_args(argv=None) -> argparse.Namespace:
     return args
 
 
-def _open_model(path: str) -> Tuple[Any, Any, Any, bool]:
-    import torch
-
-    from buglab.runtime.neuralmodel import AbstractNeuralModel
-
-    have_gpu = torch.cuda.is_available()
-    device = torch.device("cuda" if have_gpu else "cpu")
-    model, nn = AbstractNeuralModel.restore_model(Path(path), device)
-    return model, nn, device, have_gpu
-
-
-def _read_data(path: str, limit: Optional[int]) -> List[Any]:
-    from buglab.runtime.richpath import RichPath
-    from buglab.utils.msgpackutils import load_all_msgpack_l_gz
-
-    return list(load_all_msgpack_l_gz(RichPath.create(path), shuffle=False, limit_num_yielded_elements=limit))
-
-
 def run(args: argparse.Namespace) -> int:
-    from buglab.models.suggest import write_records
-
     T.floor_of(args.min_similarity)
     model, nn, device, have_gpu = _open_model(args.MODEL)
     try:  # before anything is read or run: an index of another model's embeddings is the caller's mistake.  Only the SIZE is checked
@@ -305,8 +274,7 @@ def run(args: argparse.Namespace) -> int:
     except S.DimensionMismatch as e:
         print(str(e), file=sys.stderr)
         return EXIT_DIMENSION_MISMATCH
-    if not have_gpu:
-        raise RuntimeError("track: no ROCm GPU visible; the BugLab hot path has no CPU fallback")
+    require_gpu(have_gpu, "track")
     data = _read_data(args.DATA, args.limit_num_elements)
     scan = track_warnings(model, nn, index, data, device, args.min_similarity, args.within, site=args.site, assume_buggy=args.assume_buggy,
                           min_confidence=args.min_confidence, hide_tags=args.hide_tag, tag=args.tag, max_rounds=args.max_rounds,
@@ -319,9 +287,7 @@ def run(args: argparse.Namespace) -> int:
     print(f"track: {s['num_new']} new, {s['num_persisting']} persisting ({s['num_hidden']} more hidden) and {s['num_gone']} gone: "
           f"{s['num_warnings']} warnings of {s['num_samples']} samples against {s['num_old']} earlier ones, matched in {s['rounds']} rounds at "
           f"cosine >= {s['min_similarity']:g} within {s['within']}; the lowest listed cosine is {'n/a' if low is None else f'{low:.3f}'}.")
-    if args.report_json is not None:
-        with open(args.report_json, "w", encoding="utf-8") as f:
-            f.write(json.dumps(s, indent=1, sort_keys=True) + "\n")
+    write_report_json(args.report_json, s)
     return EXIT_NEW_WARNINGS if s["num_new"] else 0
 
 

@@ -35,7 +35,6 @@ P^2 + P + 4 doubles.  `--host` runs the NumPy twin (buglab/models/_triage.py) th
 from __future__ import annotations
 
 import argparse
-import json
 import logging
 import sys
 from pathlib import Path
@@ -48,6 +47,8 @@ import numpy as np
 
 from buglab.models import _similar as S
 from buglab.models import _triage as R
+from buglab.models._cli import collect_sites as _collect_sites, embed_sites as _embed_sites, embedding_dim as _embedding_dim
+from buglab.models._cli import open_model as _open_model, read_data as _read_data, require_gpu, write_records, write_report_json
 from buglab.models._triage import TriageModel
 
 LOGGER = logging.getLogger(__name__)
@@ -162,24 +163,6 @@ def fit_triage_embeddings(rows, logprobs, labels, *, folds: int = 5, seed: int =
         report["baseline_logprob"] = R.ranking_metrics(lp[in_fold].astype(np.float64), y[in_fold])
         report["beats_baseline"] = bool(report["triage"]["auc"] > report["baseline_logprob"]["auc"])
     return TriageFit(model, report)
-
-
-def _embed_sites(model, nn, data, device, site: str, **options) -> S.SiteEmbeddings:
-    from buglab.models import similar
-
-    return similar.embed_sites(model, nn, data, device, site, **options)
-
-
-def _collect_sites(model, nn, data, device, site: str, assume_buggy: bool, host: bool, parallelize: bool):
-    from buglab.models import similar
-
-    return similar._collect_sites(model, nn, data, device, site, assume_buggy, host, parallelize)
-
-
-def _embedding_dim(nn) -> int:
-    from buglab.models import similar
-
-    return similar.embedding_dim(nn)
 
 
 def fit_triage(model, nn, accepted: Iterable[Any], dismissed: Iterable[Any], device, *, site: str = "predicted", assume_buggy: bool = False,
@@ -366,33 +349,7 @@ def parse_args(argv=None) -> argparse.Namespace:
     return args
 
 
-def _open_model(path: str) -> Tuple[Any, Any, Any, bool]:
-    import torch
-
-    from buglab.runtime.neuralmodel import AbstractNeuralModel
-
-    have_gpu = torch.cuda.is_available()
-    device = torch.device("cuda" if have_gpu else "cpu")
-    model, nn = AbstractNeuralModel.restore_model(Path(path), device)
-    return model, nn, device, have_gpu
-
-
-def _read_data(path: str, limit: Optional[int]) -> List[Any]:
-    from buglab.runtime.richpath import RichPath
-    from buglab.utils.msgpackutils import load_all_msgpack_l_gz
-
-    return list(load_all_msgpack_l_gz(RichPath.create(path), shuffle=False, limit_num_yielded_elements=limit))
-
-
-def _write_report(path: Optional[str], report: Dict[str, Any]) -> None:
-    if path is not None:
-        with open(path, "w", encoding="utf-8") as f:
-            f.write(json.dumps(report, indent=1, sort_keys=True) + "\n")
-
-
 def run(args: argparse.Namespace) -> int:
-    from buglab.models.suggest import write_records
-
     model, nn, device, have_gpu = _open_model(args.MODEL)
     if args.command == "rank":  # before anything is read or run: a re-ranker of another model's embeddings is the caller's mistake
         triage = TriageModel.load(args.TRIAGE)
@@ -401,8 +358,7 @@ def run(args: argparse.Namespace) -> int:
         except S.DimensionMismatch as e:
             print(str(e), file=sys.stderr)
             return EXIT_DIMENSION_MISMATCH
-    if not have_gpu:
-        raise RuntimeError("triage: no ROCm GPU visible; the BugLab hot path has no CPU fallback")
+    require_gpu(have_gpu, "triage")
     if args.command == "fit":
         accepted = [p for path in args.accepted for p in _read_data(path, args.limit_num_elements)]
         dismissed = [p for path in args.dismissed for p in _read_data(path, args.limit_num_elements)]
@@ -421,7 +377,7 @@ def run(args: argparse.Namespace) -> int:
             line += (f"; out of fold: log-loss {t['log_loss']:.4f}, AUC {t['auc']:.4f} (the detector's log-probability alone: "
                      f"{b['auc']:.4f}), precision in the top 10 % {t['precision_at_10']:.3f} ({b['precision_at_10']:.3f})")
         print(line + ("." if fitted.converged else "; THE FIT DID NOT CONVERGE."))
-        _write_report(args.report_json, report)
+        write_report_json(args.report_json, report)
         return 0
     data = _read_data(args.DATA, args.limit_num_elements)
     ranked = rank_scan(model, nn, triage, data, device, site=args.site, assume_buggy=args.assume_buggy, min_confidence=args.min_confidence,
@@ -431,7 +387,7 @@ def run(args: argparse.Namespace) -> int:
     s = ranked.summary
     print(f"triage rank: {s['num_listed']} of {s['num_warnings']} warnings of {s['num_samples']} samples listed "
           f"({s['num_invalid_embeddings']} without a probability); {100.0 * s['share_above_half']:.1f}% above 1/2.")
-    _write_report(args.report_json, s)
+    write_report_json(args.report_json, s)
     return 0
 
 

@@ -488,19 +488,15 @@ def parse_args(argv=None) -> argparse.Namespace:
 
 
 def run(args: argparse.Namespace) -> Report:
-    import torch
-
-    from buglab.runtime.neuralmodel import AbstractNeuralModel
+    from buglab.models._cli import open_model, require_gpu
     from buglab.runtime.richpath import RichPath
     from buglab.utils.msgpackutils import load_all_msgpack_l_gz
 
-    if not torch.cuda.is_available():
-        raise RuntimeError("visualize.py: no ROCm GPU visible; the BugLab hot path has no CPU fallback")
-    device = torch.device("cuda")
+    require_gpu(None, "visualize.py")
     data = sampled(load_all_msgpack_l_gz(RichPath.create(args.DATA_PATH), shuffle=args.sample_pct < 1), args.num_elements, args.sample_pct)
     if args.only_no_bug:
         data = (d for d in data if d["target_fix_action_idx"] is None)
-    model, nn = AbstractNeuralModel.restore_model(Path(args.MODEL_FILENAME), device)
+    model, nn, device, _ = open_model(args.MODEL_FILENAME)
     report = scan(model, nn, data, device, parallelize=not args.sequential, only_incorrect=args.only_incorrect,
                   order_by_confidence=args.order_by_confidence, show_top_k=args.show_only_top_k, min_confidence=args.min_confidence,
                   at_operating_point=args.at_operating_point, explain=args.explain)

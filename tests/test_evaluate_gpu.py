@@ -267,7 +267,7 @@ def test_on_device_report_is_the_host_report(family, trained):
     s = host.summary()
     assert 0 < s["num_buggy_samples"] < s["num_samples"] == 130
     # a stream of unknown length, collated in worker threads
-    assert evaluate_on_device(model, nn_, iter(data), device, parallelize=True).format() == host.format()
+    assert evaluate_on_device(model, nn_, iter(data), device, parallelize=True, capacity=1).format() == host.format()
     # --eval-only-no-bug
     clean = evaluate_predictions(predictions, eval_only_no_bug=True)
     assert clean.summary()["num_samples"] == s["num_samples"] - s["num_buggy_samples"]

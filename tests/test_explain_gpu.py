@@ -425,7 +425,7 @@ def test_explain_end_to_end(family, untrained):
         again = [x.record() for x in explain(model, nn_, data, device, 10, parallelize=False)]
         assert json.dumps(plain, sort_keys=True) == json.dumps(again, sort_keys=True)  # two runs: identical records
         # a stream of unknown length, collated in worker threads: the buffers grow on the device
-        streamed = [x.record() for x in explain(model, nn_, iter(data), device, 10, parallelize=True)]
+        streamed = [x.record() for x in explain(model, nn_, iter(data), device, 10, parallelize=True, capacity=1)]
         assert json.dumps(streamed, sort_keys=True) == json.dumps(plain, sort_keys=True)
         on_host = [x.record() for x in explain(model, nn_, data, device, 10, host=True, parallelize=False)]
         assert json.dumps(on_host, sort_keys=True) == json.dumps(plain, sort_keys=True)

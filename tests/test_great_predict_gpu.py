@@ -207,7 +207,7 @@ def test_evaluate_great_on_device_equals_host_judge(trained):
     from buglab.models.evaluategreat import evaluate_great
 
     model, nn, recs = trained
-    dev = evaluate_great(model, nn, iter(recs), "cuda", minibatch_size=16, parallelize=True)  # (a stream: no len())
+    dev = evaluate_great(model, nn, iter(recs), "cuda", minibatch_size=16, parallelize=True, capacity=1)  # (a stream: no len(); it grows)
     host = evaluate_great(model, nn, recs, "cuda", minibatch_size=16, parallelize=False, on_device=False)
     assert np.array_equal(dev.out_i, host.out_i) and dev.kinds == host.kinds and np.array_equal(dev.error_location, host.error_location)
     _assert_records(dev.out_d, dev.out_i, host.out_d, host.out_i)

@@ -188,7 +188,7 @@ def test_suggest_on_the_device_equals_the_host_path(family, assume_buggy, untrai
     # (without NO_BUG the rest is not renormalised, and is below 1 all the more)
     assert max(masses) <= 1.0 + 1e-5
     # a stream of unknown length, collated in worker threads: the buffers grow on the device
-    streamed = list(suggest(model, nn_, iter(data), device, 5, assume_buggy=assume_buggy, parallelize=True))
+    streamed = list(suggest(model, nn_, iter(data), device, 5, assume_buggy=assume_buggy, parallelize=True, capacity=1))
     assert [s.ranked for s in streamed] == [s.ranked for s in on_device]
 
 
@@ -208,7 +208,7 @@ def test_evaluate_on_device_with_top_k_prints_the_host_text(family, untrained):
     plain = evaluate_on_device(model, nn_, data, device, parallelize=False)
     assert plain.top_k is None and plain.format() == report.format() and "top_k" not in json.loads(report_to_json(plain))
     # --eval-only-no-bug, and a stream of unknown length
-    clean = evaluate_on_device(model, nn_, iter(data), device, eval_only_no_bug=True, top_k=2)
+    clean = evaluate_on_device(model, nn_, iter(data), device, eval_only_no_bug=True, top_k=2, capacity=1)
     assert same(clean.top_k, evaluate_predictions(model.predict(iter(data), nn_, device, False), eval_only_no_bug=True, top_k=2).top_k)
     assert clean.top_k["num_samples"] == {"all": 30, "buggy": 0, "correct": 30}
 
