@@ -111,6 +111,20 @@ int32_t bl_message_runs(const int32_t* msg_src, const int32_t* msg_tgt, const in
                         int32_t* run_ptr, int32_t* bwd_group_ptr, int32_t* bwd_group_w, int32_t* bwd_rows_tgt, int32_t* bwd_rows_src,
                         int32_t* tgt_run_ptr, int32_t* tgt_run_rows, int64_t* num_runs);
 
+/* Live rows of a collated minibatch (buglab/data/collate.py::live_set_arrays).  The scoring heads (localizationmodule.py:54-60,
+ * fixermodules.py:31-39) read the encoder's output through one gather of the rows head_idx, so the backward pass of the last
+ * message-passing layer meets a non-zero gradient only at those nodes, the layer below only at those nodes and the sources of the
+ * messages into them, and so on.  Per live layer, the last one first, the index arrays of the reduced backward problem go into
+ * ONE caller-allocated array `arrays` (capacity elements; every piece starts at a multiple of 4 elements, gaps zeroed) and one row
+ * of 15 int32 into layout [max_layers, 15]: N' (nodes), N'' (receiving nodes), E' (messages), R' (runs), then the offsets of
+ *   nodes [N'], recv [N''], msgs [E'], run_ptr [R' + 1], group_ptr [2T + 1], rows_tgt [E' + R'] (positions in nodes),
+ *   rows_src [E' + R'] (node ids), src_ptr [N'' + 1], src_msgs [E'], run_csr_ptr [N'' + 1], run_csr_rows [R'].
+ * The descent ends after max_layers layers or at the first layer with E' > fraction * E (not emitted).  *num_layers and *total
+ * (elements of `arrays` written) on return; -3 when capacity is too small.  (bl_data_version() >= 5) */
+int32_t bl_live_sets(const int32_t* msg_src, const int32_t* msg_tgt, const int32_t* type_ptr, int64_t E, int32_t T, int64_t N,
+                     const int32_t* head_idx, int64_t num_head, int32_t max_layers, double fraction, int32_t* arrays, int64_t capacity,
+                     int32_t* layout, int32_t* num_layers, int64_t* total);
+
 /* Stable counting sort of keys in [0, K): perm[E] = item indices ordered by key (ties keep input order),
  * ptr[K + 1] = where each key's run starts.  The collator's CSRs and per-type target order
  * (reference gnn.py:463-542 builds these with Python lists; here: one pass). */

@@ -451,6 +451,28 @@ typedef struct {
   const int32_t* bwd_rows_src;    /* [E + R] = [msg_src ; run target] */
   const int32_t* tgt_run_ptr;     /* [N + 1] CSR node -> the rows of its runs ... */
   const int32_t* tgt_run_rows;    /* [R]     ... E + run id, ascending */
+  /* Optional (backward only): the LIVE ROWS of this layer (the collators make these arrays per minibatch and layer,
+   * buglab/data/collate.py::live_set_arrays).  By handing them in the caller states that g_out is zero outside the rows
+   * live_nodes: the heads read the encoder's output through one gather of a few rows, and a layer's input can receive a
+   * gradient only at the layer's live nodes and at the sources of the messages into them (live_recv = the layer below's
+   * live_nodes).  Backward then runs over the live rows only -- N' nodes, the E' messages and R' runs into them -- and writes
+   * the rows live_recv of g_h_lo / g_h_hi, every other row zero.  Taken where the run-row path and bl_node_update_bwd apply
+   * (bl_set_live_backward); every other configuration ignores the arrays.  live_nodes == NULL: none. */
+  int32_t live_num_nodes;           /* N' */
+  int32_t live_num_recv;            /* N'' */
+  int32_t live_num_msgs;            /* E' (messages keep their order: type-major, target-sorted inside a type) */
+  int32_t live_num_runs;            /* R' */
+  const int32_t* live_nodes;        /* [N']  node ids, ascending */
+  const int32_t* live_recv;         /* [N''] node ids, ascending: live_nodes and the sources of the live messages */
+  const int32_t* live_msgs;         /* [E']  message ids, ascending (rows of the routing bitmask) */
+  const int32_t* live_run_ptr;      /* [R' + 1] range of every live run in 0..E' */
+  const int32_t* live_group_ptr;    /* [2 T + 1] bwd_group_ptr of the E' + R' rows (weight slices: bwd_group_w) */
+  const int32_t* live_rows_tgt;     /* [E' + R'] target of a message / run as a position in live_nodes */
+  const int32_t* live_rows_src;     /* [E' + R'] [source node id of a message ; target node id of a run] */
+  const int32_t* live_src_ptr;      /* [N'' + 1] CSR position in live_recv -> live messages it is the source of ... */
+  const int32_t* live_src_msgs;     /* [E']      ... as rows 0..E'-1, ascending */
+  const int32_t* live_run_csr_ptr;  /* [N'' + 1] CSR position in live_recv -> rows of the live runs into it ... */
+  const int32_t* live_run_csr_rows; /* [R']      ... E' + run, ascending */
 } bl_mp_layer_t;
 #define BL_AGG_MAX 0
 #define BL_AGG_SUM 1
@@ -523,6 +545,27 @@ int bl_mp_scatter_grad_runs(const float* g_a, int32_t ld_ga, const int32_t* src_
                             float* g_h_lo, int32_t ld_lo, float* g_h_hi, int32_t ld_hi, const int32_t* node_order,
                             int32_t num_hub_slots, void* stream);
 int32_t bl_set_run_rows(int32_t on);
+/* The pieces of bl_mp_layer_bwd's live-row path (bl_mp_layer_t.live_nodes):
+ *   bl_winbits_gather: out[i, 0:words] = bits[rows[i], 0:words] for i < n (rows ld_bits / ld_out words apart; bits has nrows_in
+ *     rows) -- the compact copy of the live messages' routing masks.
+ *   bl_node_update_bwd_rows: bl_node_update_bwd over the nodes rows[0..nrows-1]: every per-node input (g_out, h_out, agg, mean,
+ *     rstd, dact) is read at row rows[i], the dropout mask is that row's, g_z_packed / gq / gq_packed are written at row i.
+ *   bl_mp_scatter_grad_rows: bl_mp_scatter_grad_runs over CSRs of `n` segments whose sums go to row out_rows[i] of g_h_lo /
+ *     g_h_hi (other rows untouched).
+ *   bl_set_live_backward: A/B switch, 1 (default; BL_LIVE_BWD=0 in the environment starts with 0) = bl_mp_layer_bwd takes the
+ *     live-row path where it applies, 0 = the full backward on the same descriptor.  Returns the previous value;
+ *     bl_get_live_backward the current one. */
+int bl_winbits_gather(const uint32_t* bits, int32_t ld_bits, int32_t nrows_in, const int32_t* rows, int32_t n, int32_t words,
+                      uint32_t* out, int32_t ld_out, void* stream);
+int bl_node_update_bwd_rows(const float* g_out, const float* h_out, const int32_t* rows, int32_t nrows, int32_t Dout, bl_dropout_t drop,
+                            const uint16_t* wd_packed_bwd, const float* agg, const float* mean, const float* rstd, const float* ln_g,
+                            const float* dact, int32_t Dm, uint16_t* g_z_packed, float* g_bias, float* gq, uint16_t* gq_packed,
+                            float* g_ln_g, float* g_ln_b, void* stream);
+int bl_mp_scatter_grad_rows(const float* g_a, int32_t ld_ga, const int32_t* src_ptr, const int32_t* src_msgs,
+                            const int32_t* run_csr_ptr, const int32_t* run_csr_rows, const int32_t* out_rows, int32_t n, int32_t Din,
+                            int32_t split, float* g_h_lo, int32_t ld_lo, float* g_h_hi, int32_t ld_hi, void* stream);
+int32_t bl_set_live_backward(int32_t on);
+int32_t bl_get_live_backward(void);
 
 /* optional per-kernel timing of the launches made inside bl_mp_layer_fwd / _bwd (HIP events on the stream each
  * kernel is launched on); read after a device synchronisation.  bench.py's roofline numbers come from here. */

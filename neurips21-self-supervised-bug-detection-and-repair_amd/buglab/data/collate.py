@@ -13,6 +13,8 @@ adjacency lists:
   src_ptr/src_msgs : int32[N+1]/int32[E]  CSR node -> ids of the messages it is the source of
   run_ptr, bwd_*, tgt_run_* : the runs (consecutive messages of one type into one node) and the backward pass's row space of
                      E + R rows built on them (`message_run_arrays`)
+  live_arrays, live_layout : the rows the scoring heads can reach through the last layers, and the reduced backward problem of
+                     each of those layers (`live_set_arrays`)
 
 Target-sorted CSR turns the reference's atomic `scatter_max` (torch_scatter) into
 a segmented reduction: no atomics, deterministic, ties resolve to the lowest
@@ -176,6 +178,95 @@ def message_run_arrays(msg_src: np.ndarray, msg_tgt: np.ndarray, type_ptr: np.nd
             "tgt_run_ptr": np.asarray(tgt_run_ptr, dtype=I32), "tgt_run_rows": (E + np.asarray(order, dtype=np.int64)).astype(I32)}
 
 
+# ---- live rows: the part of the last layers' backward the heads can reach -------------------------------------------------
+# The heads read the encoder's output through ONE gather (head_gather_idx), so the gradient of the last layer's output is zero
+# outside those rows, the gradient of the layer below outside those rows and the sources of the messages into them, and so on.
+# LIVE_LAYOUT_COLUMNS names the columns of `live_layout` (one row per live layer, the LAST layer first): four counts, then the
+# offset of each piece inside `live_arrays`.
+LIVE_LAYOUT_COLUMNS = ("num_nodes", "num_recv", "num_msgs", "num_runs", "nodes", "recv", "msgs", "run_ptr", "group_ptr", "rows_tgt",
+                       "rows_src", "src_ptr", "src_msgs", "run_csr_ptr", "run_csr_rows")
+# The descent stops at the first layer whose live messages exceed LIVE_FRACTION of all messages (that layer and everything below
+# keep the full backward) and after LIVE_MAX_LAYERS layers at the latest; measured values: tools/experiments/README.md.
+LIVE_FRACTION = 0.5
+LIVE_MAX_LAYERS = 3
+
+
+def live_limits() -> Tuple[int, float]:
+    """(most live layers, largest live fraction of the messages); BL_LIVE_LAYERS / BL_LIVE_FRACTION override the defaults (A/B knobs)."""
+    return int(os.environ.get("BL_LIVE_LAYERS", LIVE_MAX_LAYERS)), float(os.environ.get("BL_LIVE_FRACTION", LIVE_FRACTION))
+
+
+def _live_piece_sizes(nn: int, nr: int, ex: int, rx: int, T: int) -> Tuple[int, ...]:
+    """Lengths of the eleven pieces of one live layer, in LIVE_LAYOUT_COLUMNS order."""
+    return (nn, nr, ex, rx + 1, 2 * T + 1, ex + rx, ex + rx, nr + 1, ex, nr + 1, rx)
+
+
+def live_set_arrays(msg_src: np.ndarray, msg_tgt: np.ndarray, type_ptr: np.ndarray, num_nodes: int, head_idx: np.ndarray,
+                    max_layers: Optional[int] = None, fraction: Optional[float] = None) -> Dict[str, np.ndarray]:
+    """The live sets of a minibatch, per layer from the last one downwards, and the index arrays of the reduced backward problem
+    of each (NumPy; `buglab.data.native.live_set_arrays` is the native twin and must return the same arrays).
+
+    Layer 0 (the last): nodes = sorted unique head_idx.  Per layer: msgs = the messages whose target is in nodes, in their order
+    (type-major, target-sorted inside a type); recv = nodes + the sources of msgs = the nodes of the next layer down.  Pieces, all
+    inside ONE int32 array `live_arrays` (each starts at a multiple of 4 elements), offsets and counts in `live_layout`
+    [layers, len(LIVE_LAYOUT_COLUMNS)]:
+      nodes [N']  recv [N'']  msgs [E'] (message ids)            run_ptr [R'+1] runs of the live messages, in 0..E'
+      group_ptr [2T+1]  as bwd_group_ptr, over the E' + R' rows   rows_tgt [E'+R'] targets as positions in nodes
+      rows_src [E'+R'] [source node of a message ; target node of a run] (node ids)
+      src_ptr [N''+1], src_msgs [E']      CSR position in recv -> rows 0..E'-1 of the messages it is the source of
+      run_csr_ptr [N''+1], run_csr_rows [R']  CSR position in recv -> rows E' + run of the runs into it
+    A layer whose live messages exceed `fraction` of all messages ends the descent and is not emitted; no head rows: no layers."""
+    if max_layers is None or fraction is None:
+        dl, df = live_limits()
+        max_layers, fraction = (dl if max_layers is None else max_layers), (df if fraction is None else fraction)
+    msg_src, msg_tgt = np.asarray(msg_src, dtype=I32), np.asarray(msg_tgt, dtype=I32)
+    type_ptr = np.asarray(type_ptr, dtype=np.int64)
+    E, T, N = int(msg_tgt.shape[0]), int(type_ptr.shape[0]) - 1, int(num_nodes)
+    nodes = np.unique(np.asarray(head_idx, dtype=np.int64))
+    pieces: List[np.ndarray] = []
+    layout: List[List[int]] = []
+    total = 0
+    while nodes.size and len(layout) < max_layers:
+        in_set = np.zeros(N, dtype=bool)
+        in_set[nodes] = True
+        msgs = np.flatnonzero(in_set[msg_tgt])
+        ex = int(msgs.shape[0])
+        if ex > float(fraction) * E:
+            break
+        pos = np.full(N, -1, dtype=np.int64)
+        pos[nodes] = np.arange(nodes.shape[0])
+        src_c, tgt_c = msg_src[msgs].astype(np.int64), msg_tgt[msgs].astype(np.int64)
+        tp_c = np.searchsorted(msgs, type_ptr, side="left")  # live messages before each type boundary
+        first = np.zeros(ex, dtype=bool)
+        if ex:
+            first[1:] = tgt_c[1:] != tgt_c[:-1]
+            first[tp_c[:-1][tp_c[:-1] < ex]] = True
+        starts = np.flatnonzero(first)
+        rx = int(starts.shape[0])
+        run_tgt = tgt_c[starts]
+        runs_before = np.searchsorted(starts, tp_c, side="left")
+        recv = np.union1d(nodes, src_c)
+        rpos = np.full(N, -1, dtype=np.int64)
+        rpos[recv] = np.arange(recv.shape[0])
+        src_ptr, src_rows = _csr(rpos[src_c], int(recv.shape[0]))
+        rc_ptr, rc_order = _csr(rpos[run_tgt], int(recv.shape[0]))
+        layer = [nodes, recv, msgs, np.concatenate([starts, [ex]]), np.concatenate([tp_c[:-1], ex + runs_before]),
+                 np.concatenate([pos[tgt_c], pos[run_tgt]]), np.concatenate([src_c, run_tgt]), src_ptr, src_rows, rc_ptr,
+                 ex + np.asarray(rc_order, dtype=np.int64)]
+        row = [int(nodes.shape[0]), int(recv.shape[0]), ex, rx]
+        assert tuple(int(a.shape[0]) for a in layer) == _live_piece_sizes(row[0], row[1], ex, rx, T)
+        for a in layer:
+            row.append(total)
+            pieces.append(np.asarray(a, dtype=I32))
+            total += (int(a.shape[0]) + 3) // 4 * 4
+        layout.append(row)
+        nodes = recv
+    arrays = np.zeros(total, dtype=I32)  # (the padding between pieces is zeros in both collators)
+    for a, o in zip(pieces, (o for row in layout for o in row[4:])):
+        arrays[o : o + a.shape[0]] = a
+    return {"live_arrays": arrays, "live_layout": np.asarray(layout, dtype=I32).reshape(len(layout), len(LIVE_LAYOUT_COLUMNS))}
+
+
 def _collate_graph_arrays_numpy(graphs, num_edge_types: int, node_off: np.ndarray, N: int) -> Dict[str, np.ndarray]:
     """NumPy version of `buglab.data.native.collate_graph_arrays` (used when the native library is not built, and as
     its test reference)."""
@@ -293,6 +384,11 @@ def collate_graphs(graphs: Sequence[TensorizedGraphData], num_edge_types: int) -
         parts.append(r)
         pos += int(r.shape[0])
     head_gather_idx = np.concatenate(parts).astype(I32) if parts else np.zeros(0, I32)
+    # what the backward of the last layers can reach from those rows (the native collator when it made the other arrays)
+    if native.available() and os.environ.get("BUGLAB_NATIVE_COLLATE", "1") != "0":
+        live = native.live_set_arrays(msg_src, msg_tgt, type_ptr, N, head_gather_idx, *live_limits())
+    else:
+        live = live_set_arrays(msg_src, msg_tgt, type_ptr, N, head_gather_idx)
 
     node_to_graph = np.repeat(np.arange(B, dtype=I32), n_per_graph)
     cand_graph = ref_graph["candidate_nodes"]
@@ -323,6 +419,7 @@ def collate_graphs(graphs: Sequence[TensorizedGraphData], num_edge_types: int) -
         "src_ptr": src_ptr,
         "src_msgs": src_msgs,
         **{k: arr[k] for k in RUN_KEYS},
+        **live,
         "node_to_graph": node_to_graph,
         "num_nodes_per_graph": n_per_graph.astype(I32),
         "num_graphs": B,
@@ -445,7 +542,7 @@ _INT_KEYS_GD = ("loc_group_ptr", "loc_group_items", "token_ids", "token_lens", "
 
 # present only in minibatches of the sequence models (buglab.models.seqmodel.collate_sequences) / with edge features on / made by
 # collate_graphs (a hand-built graph_data without the run arrays takes the per-message backward)
-_INT_KEYS_GD_SEQ = ("seq_lens", "erow_ptr", "ekey", "ecode", "msg_feat") + RUN_KEYS
+_INT_KEYS_GD_SEQ = ("seq_lens", "erow_ptr", "ekey", "ecode", "msg_feat") + RUN_KEYS + ("live_arrays", "live_layout")
 
 
 def pack_minibatch(mb: Dict[str, Any], out: Optional[np.ndarray] = None):
@@ -517,6 +614,8 @@ def upload_packed(blob: np.ndarray, meta: Dict[str, Any], device) -> Dict[str, A
     out: Dict[str, Any] = {"graph_data": out_gd}
     for where, k, shape, o in meta["layout"]:
         t = dblob[o : o + int(np.prod(shape, dtype=np.int64))].view(shape)
+        if k == "live_layout":  # counts and offsets that size launches: the host's copy, straight from the host blob
+            t = np.array(blob[o : o + int(np.prod(shape, dtype=np.int64))], dtype=I32).reshape(shape)
         if where == "gd":
             out_gd[k] = t
         elif where == "ref":

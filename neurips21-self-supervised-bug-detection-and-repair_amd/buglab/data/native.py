@@ -67,6 +67,8 @@ _SIGNATURES = {
     "bl_collate_graphs": ([c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, POINTER(bl_collated_t)], c_int32),
     "bl_message_runs": ([c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                          c_void_p, POINTER(c_int64)], c_int32),
+    "bl_live_sets": ([c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int64, c_void_p, c_int64, c_int32, ctypes.c_double, c_void_p, c_int64,
+                      c_void_p, POINTER(c_int32), POINTER(c_int64)], c_int32),
 }
 RUN_KEYS = ("run_ptr", "bwd_group_ptr", "bwd_group_w", "bwd_rows_tgt", "bwd_rows_src", "tgt_run_ptr", "tgt_run_rows")
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
@@ -202,6 +204,27 @@ def message_run_arrays(msg_src: np.ndarray, msg_tgt: np.ndarray, type_ptr: np.nd
     o["bwd_rows_tgt"], o["bwd_rows_src"] = o["bwd_rows_tgt"][: E + R], o["bwd_rows_src"][: E + R]
     o["tgt_run_rows"] = o["tgt_run_rows"][:R]
     return o
+
+
+def live_set_arrays(msg_src: np.ndarray, msg_tgt: np.ndarray, type_ptr: np.ndarray, num_nodes: int, head_idx: np.ndarray, max_layers: int,
+                    fraction: float) -> Dict[str, np.ndarray]:
+    """`buglab.data.collate.live_set_arrays` (the rows the heads can reach through the last layers and the reduced backward problem
+    of each) by `bl_live_sets`, one GIL-free call."""
+    lib = load_library()
+    if lib.bl_data_version() < 5:
+        raise RuntimeError("libbuglab_data.so predates bl_live_sets: rebuild it")
+    msg_src, msg_tgt = np.ascontiguousarray(msg_src, dtype=np.int32), np.ascontiguousarray(msg_tgt, dtype=np.int32)
+    type_ptr, head_idx = np.ascontiguousarray(type_ptr, dtype=np.int32), np.ascontiguousarray(head_idx, dtype=np.int32).reshape(-1)
+    E, T, N, L = int(msg_tgt.shape[0]), int(type_ptr.shape[0]) - 1, int(num_nodes), max(int(max_layers), 0)
+    ex_max = min(E, int(float(fraction) * E) + 1) if fraction >= 0 else 0  # most live messages of an emitted layer
+    cap = L * (4 * N + 8 * ex_max + 2 * T + 64)
+    arrays, layout = np.empty(cap, np.int32), np.zeros((L, 15), np.int32)
+    n_layers, total = c_int32(0), c_int64(0)
+    rc = lib.bl_live_sets(msg_src.ctypes.data, msg_tgt.ctypes.data, type_ptr.ctypes.data, E, T, N, head_idx.ctypes.data, int(head_idx.shape[0]),
+                          L, float(fraction), arrays.ctypes.data, cap, layout.ctypes.data, ctypes.byref(n_layers), ctypes.byref(total))
+    if rc != 0:
+        raise ValueError(lib.bl_data_last_error().decode())
+    return {"live_arrays": arrays[: int(total.value)].copy(), "live_layout": layout[: int(n_layers.value)].copy()}
 
 
 def _copy_i32(ptr, n: int) -> np.ndarray:

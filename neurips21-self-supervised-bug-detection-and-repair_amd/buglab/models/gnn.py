@@ -161,17 +161,27 @@ class GnnBugLabModule(ModuleWithMetrics):
         return (self._dropout_base_seed * 0x9E3779B1 + self._dropout_step) & 0xFFFFFFFF
 
     def _compute_gnn_output(self, graph_data, dropout_seed=None) -> GnnOutput:
-        out: GnnOutput = self._gnn(**graph_data, return_all_states=self._use_all_gnn_layer_outputs, dropout_seed=dropout_seed)
+        idx_all = graph_data.get("head_gather_idx")
+        # Live rows: when the scoring heads are the only readers of the encoder's output, and read it through the ONE gather below,
+        # the gradient of that output is zero outside the gathered rows -- the last layers then run their backward over the rows
+        # that gather can reach (the minibatch's live arrays).  The contract is made explicit: in this mode the full output is
+        # handed out DETACHED, so a second consumer gets no gradient rather than a silently truncated one.
+        live = (not self._use_all_gnn_layer_outputs and idx_all is not None and idx_all.shape[0] > 0
+                and graph_data.get("live_arrays") is not None and graph_data.get("input_transform") is None
+                and isinstance(self._gnn, GraphNeuralNetwork) and torch.is_grad_enabled() and hip_ops.live_backward())
+        out: GnnOutput = self._gnn(**graph_data, return_all_states=self._use_all_gnn_layer_outputs, dropout_seed=dropout_seed,
+                                   **({"live_backward": True} if live else {}))
         if self._use_all_gnn_layer_outputs:  # reference :118-121
             out = out._replace(output_node_representations=hip_ops.gather_linear(
                 [(out.output_node_representations, None)], self.summarization_W, self.summarization_b, "none"))
-        idx_all = graph_data.get("head_gather_idx")
         if idx_all is not None and idx_all.shape[0] > 0:
             # all scorers read node rows through ONE gather: backward then has a single [N, H] scatter
             # instead of a zero-filled [N, H] buffer (and an accumulation) per gathered operand
             local, spans = graph_data["head_local_idx"], graph_data["head_spans"]
             out = out._replace(head_node_representations=hip_ops.gather_rows(out.output_node_representations, idx_all),
                                head_idx_references={k: local[s : s + n] for k, (s, n) in spans.items()})
+            if live:
+                out = out._replace(output_node_representations=out.output_node_representations.detach())
         return out
 
     def overlap_parameter_groups(self):

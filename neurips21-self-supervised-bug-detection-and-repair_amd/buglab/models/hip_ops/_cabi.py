@@ -64,7 +64,11 @@ class bl_mp_layer_t(Structure):
                 ("msg_act", c_int32), ("ln_eps", c_float), ("drop", bl_dropout_t), ("Wt", c_void_p),
                 ("Wd_packed", c_void_p), ("Wd_packed_bwd", c_void_p), ("num_hub_slots", c_int32), ("aggregation", c_int32),
                 ("num_runs", c_int32), ("run_ptr", c_void_p), ("bwd_group_ptr", c_void_p), ("bwd_group_w", c_void_p),
-                ("bwd_rows_tgt", c_void_p), ("bwd_rows_src", c_void_p), ("tgt_run_ptr", c_void_p), ("tgt_run_rows", c_void_p)]
+                ("bwd_rows_tgt", c_void_p), ("bwd_rows_src", c_void_p), ("tgt_run_ptr", c_void_p), ("tgt_run_rows", c_void_p),
+                ("live_num_nodes", c_int32), ("live_num_recv", c_int32), ("live_num_msgs", c_int32), ("live_num_runs", c_int32),
+                ("live_nodes", c_void_p), ("live_recv", c_void_p), ("live_msgs", c_void_p), ("live_run_ptr", c_void_p),
+                ("live_group_ptr", c_void_p), ("live_rows_tgt", c_void_p), ("live_rows_src", c_void_p), ("live_src_ptr", c_void_p),
+                ("live_src_msgs", c_void_p), ("live_run_csr_ptr", c_void_p), ("live_run_csr_rows", c_void_p)]
 
 
 class bl_x6_epi_t(Structure):
@@ -130,6 +134,13 @@ _SIGNATURES = {
     "bl_set_run_rows": ([c_int32], c_int32),
     "bl_winbits_or_runs": ([c_void_p, c_int32, c_void_p, c_int32, c_int32, c_int32, c_void_p], ctypes.c_int),
     "bl_mp_scatter_grad_runs": ([c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_int32, c_void_p,
+                                 c_int32, c_void_p, c_int32, c_void_p], ctypes.c_int),
+    "bl_set_live_backward": ([c_int32], c_int32),
+    "bl_get_live_backward": ([], c_int32),
+    "bl_winbits_gather": ([c_void_p, c_int32, c_int32, c_void_p, c_int32, c_int32, c_void_p, c_int32, c_void_p], ctypes.c_int),
+    "bl_node_update_bwd_rows": ([c_void_p, c_void_p, c_void_p, c_int32, c_int32, bl_dropout_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                 c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p], ctypes.c_int),
+    "bl_mp_scatter_grad_rows": ([c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p,
                                  c_int32, c_void_p, c_int32, c_void_p], ctypes.c_int),
     "bl_last_error": ([], ctypes.c_char_p),
     "bl_embed_subtoken_pool_fwd": ([c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_int32, c_int32, c_int32, bl_dropout_t, c_int32, c_void_p, c_int32, c_void_p, c_void_p], ctypes.c_int),

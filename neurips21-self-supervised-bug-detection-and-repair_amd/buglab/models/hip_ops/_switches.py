@@ -78,3 +78,11 @@ DIRECT_PARAM_GRAD = os.environ.get("BL_DIRECT_GRAD", "1") != "0"
 # Priority of the side stream that carries the weight-gradient GEMMs (lower number = higher priority; out-of-range values are
 # mapped to the nearest valid one).  BL_SIDE_STREAM_PRIORITY: A/B knob.
 SIDE_STREAM_PRIORITY = int(os.environ.get("BL_SIDE_STREAM_PRIORITY", "0"))
+
+# Switches whose one copy lives in the LIBRARY (a C call consults them, so a Python copy could only go stale); runtime.py holds their
+# setters / getters, the environment variable sets the initial value there:
+#   BL_MSG_GEMM   hip_ops.set_msg_gemm_mode / msg_gemm_mode      operand split of the message GEMMs
+#   BL_SEQ_GEMM   hip_ops.set_seq_gemm_mode / seq_gemm_mode      operand split of the sequence models' projections
+#   BL_RUN_ROWS   hip_ops.set_run_rows                           target halves of the routed gradients once per run
+#   BL_LIVE_BWD   hip_ops.set_live_backward / live_backward      backward of the last layers over the rows the heads can reach
+#                                                                (gnn.py asks live_backward() before it hands the live arrays on)

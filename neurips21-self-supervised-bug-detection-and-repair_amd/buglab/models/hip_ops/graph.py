@@ -16,7 +16,7 @@ from .gemm import (act_bwd, gemm_rows, gemm_rows_routed, gemm_rows_x6, gemm_wgra
                    layernorm_bwd, pack_bf16x3, pack_weights_x6, scatter_add_rows, segment_max, x6_ok)
 from .weights import _as_groups, _packed_layer_weights, _packed_message_weights, _transposed_layer_weights
 
-__all__ = ["GraphIndex", "MessageRuns", "POOLINGS", "AGGREGATIONS", "_EmbedSubtokenMax", "embed_subtoken_max", "_MpLayer", "node_update_bwd",
+__all__ = ["GraphIndex", "MessageRuns", "LiveRows", "live_rows_of", "POOLINGS", "AGGREGATIONS", "_EmbedSubtokenMax", "embed_subtoken_max", "_MpLayer", "node_update_bwd",
            "_use_vector_dgrad", "_layer_desc", "_MpLayerFused", "_pending_uses", "set_grad_ready_callback", "_note_use",
            "_notify_backward_launched", "fused_layer_ok", "_GatedMpLayer", "gated_mp_layer", "_MpLayerFeat",
            "mp_layer_with_edge_features", "mp_layer"]
@@ -44,6 +44,34 @@ class MessageRuns(NamedTuple):
         return int(self.run_ptr.shape[0]) - 1
 
 
+class LiveRows(NamedTuple):
+    """Device-side live arrays of ONE layer of one minibatch (buglab.data.collate.live_set_arrays): the rows of the layer's output
+    whose gradient can be non-zero, and the reduced backward problem over them (bl_mp_layer_t.live_nodes ...).  Handing them to a
+    layer is the caller's statement that the gradient of the layer's output IS zero everywhere else."""
+
+    nodes: torch.Tensor
+    recv: torch.Tensor
+    msgs: torch.Tensor
+    run_ptr: torch.Tensor
+    group_ptr: torch.Tensor
+    rows_tgt: torch.Tensor
+    rows_src: torch.Tensor
+    src_ptr: torch.Tensor
+    src_msgs: torch.Tensor
+    run_csr_ptr: torch.Tensor
+    run_csr_rows: torch.Tensor
+
+
+def live_rows_of(live_arrays: torch.Tensor, live_layout, T: int):
+    """Per live layer (the last layer first) the LiveRows views into the minibatch's one `live_arrays` tensor."""
+    out = []
+    for row in (live_layout.tolist() if hasattr(live_layout, "tolist") else live_layout):
+        nn, nr, ex, rx = row[:4]
+        sizes = (nn, nr, ex, rx + 1, 2 * T + 1, ex + rx, ex + rx, nr + 1, ex, nr + 1, rx)
+        out.append(LiveRows(*[live_arrays[o : o + n] for o, n in zip(row[4:], sizes)]))
+    return out
+
+
 class GraphIndex(NamedTuple):
     """Device-side index arrays of one minibatch (buglab.data.collate.to_device)."""
 
@@ -60,6 +88,7 @@ class GraphIndex(NamedTuple):
     node_order: Optional[torch.Tensor] = None  # processing order of the per-node kernels: high-degree nodes first
     num_hubs: int = -1  # leading entries of node_order that are hubs (-1: unknown, the kernels look at the first 4096)
     runs: Optional[MessageRuns] = None  # None: backward works message by message
+    live: Optional[LiveRows] = None  # the live rows of the layer this index is handed to (None: backward over all rows)
 
 
 POOLINGS = ("max", "sum", "mean")  # BL_POOL_MAX / _SUM / _MEAN
@@ -262,7 +291,7 @@ def _use_vector_dgrad(lib, E: int, Dm: int, K2: int) -> bool:
     return bool(want) and E > 0 and bool(lib.bl_routed_dgrad_vec_ok(Dm, K2))
 
 
-def _layer_desc(g: "GraphIndex", W, ln_g, ln_b, Wd, bd, Din, msg_act, drop: Dropout, agg: int = 0) -> bl_mp_layer_t:
+def _layer_desc(g: "GraphIndex", W, ln_g, ln_b, Wd, bd, Din, msg_act, drop: Dropout, agg: int = 0, backward: bool = False) -> bl_mp_layer_t:
     L = bl_mp_layer_t()
     L.aggregation = int(agg)
     L.N, L.E, L.T, L.Din, L.Dm, L.Dout = g.num_nodes, g.num_messages, W.shape[0], Din, W.shape[2], Wd.shape[1]
@@ -276,6 +305,12 @@ def _layer_desc(g: "GraphIndex", W, ln_g, ln_b, Wd, bd, Din, msg_act, drop: Drop
         L.num_runs = g.runs.num_runs
         for name in MessageRuns._fields:
             setattr(L, name, getattr(g.runs, name).data_ptr())
+    if backward and g.live is not None and g.live.nodes.shape[0] > 0:  # (whether the call takes them is bl_mp_layer_bwd's decision)
+        lv = g.live
+        L.live_num_nodes, L.live_num_recv = int(lv.nodes.shape[0]), int(lv.recv.shape[0])
+        L.live_num_msgs, L.live_num_runs = int(lv.msgs.shape[0]), int(lv.run_ptr.shape[0]) - 1
+        for name in LiveRows._fields:
+            setattr(L, "live_" + name, getattr(lv, name).data_ptr())
     return L
 
 
@@ -348,7 +383,7 @@ class _MpLayerFused(torch.autograd.Function):
         direct = [_direct_small(bd), _direct_small(ln_g), _direct_small(ln_b), _direct_grad_target(Wd), _direct_grad_target(W)]
         tgt = [d if d is not None else torch.zeros_like(p) for d, p in zip(direct, (bd, ln_g, ln_b, Wd, W))]
         g_bd, g_lng, g_lnb, g_Wd, g_W = tgt
-        L = _layer_desc(g, W, ln_g, ln_b, Wd, bd, Din, msg_act, drop, agg)
+        L = _layer_desc(g, W, ln_g, ln_b, Wd, bd, Din, msg_act, drop, agg, backward=True)
         if dense_x6:  # (forward kept the LayerNorm output in packed form: backward must take the same path)
             if wd_nk is None:
                 wd_nk = pack_weights_x6(_as_groups(Wd.detach()), False)

@@ -7,7 +7,7 @@ from . import _switches
 from ._cabi import load_library
 
 __all__ = ["set_deterministic", "_MSG_GEMM_MODES", "set_msg_gemm_mode", "msg_gemm_mode", "set_seq_gemm_mode", "seq_gemm_mode", "set_wgrad_tile",
-           "set_wgrad_kchunk_cap", "set_fused_node_bwd", "set_run_rows", "deterministic"]
+           "set_wgrad_kchunk_cap", "set_fused_node_bwd", "set_run_rows", "set_live_backward", "live_backward", "deterministic"]
 
 
 def set_deterministic(on: bool = True) -> None:
@@ -74,6 +74,17 @@ def set_run_rows(on: bool) -> bool:
     """A/B switch (BL_RUN_ROWS=0 starts with it off): backward of the fused layer call computes the target halves of the routed
     f16x3 gradients once per run of messages (default) or once per message, on the same arrays.  -> previous."""
     return bool(load_library().bl_set_run_rows(1 if on else 0))
+
+
+def set_live_backward(on: bool) -> bool:
+    """A/B switch (BL_LIVE_BWD=0 starts with it off): backward of the fused layer call runs over the live rows of a descriptor that
+    carries them (GraphIndex.live: the rows the heads' gather can reach) or over all rows.  Off, GnnBugLabModule does not hand the
+    live arrays to the layers either and keeps its full output attached.  -> previous."""
+    return bool(load_library().bl_set_live_backward(1 if on else 0))
+
+
+def live_backward() -> bool:
+    return bool(load_library().bl_get_live_backward())
 
 
 def deterministic() -> bool:

@@ -21,7 +21,7 @@ import torch
 from torch import nn
 
 from buglab.models import hip_ops
-from buglab.models.hip_ops import Dropout, GraphIndex, MessageRuns
+from buglab.models.hip_ops import Dropout, GraphIndex, MessageRuns, live_rows_of
 
 
 class GnnOutput(NamedTuple):
@@ -210,9 +210,12 @@ class GraphNeuralNetwork(nn.Module):
                 return_all_states: bool = False, dropout_seed: Optional[int] = None, tok_occ=None, tok_chunk_ptr=None,
                 tok_chunk_id=None, node_order=None, num_hub_nodes: int = -1, msg_feat=None, input_transform=None, run_ptr=None,
                 bwd_group_ptr=None, bwd_group_w=None, bwd_rows_tgt=None, bwd_rows_src=None, tgt_run_ptr=None, tgt_run_rows=None,
-                **_unused) -> GnnOutput:
+                live_arrays=None, live_layout=None, live_backward: bool = False, **_unused) -> GnnOutput:
         """input_transform: applied to the embedder's output before the first layer (buglab/models/explain.py scales and
-        re-leafs it there); None, as every other caller leaves it, changes nothing."""
+        re-leafs it there); None, as every other caller leaves it, changes nothing.
+        live_backward: the caller's promise that the gradient reaches the returned output only through the rows the minibatch's
+        live arrays were made for (head_gather_idx; GnnBugLabModule._compute_gnn_output) -- the last layers then get their live rows
+        and may run their backward over those alone.  Never with return_all_states or an input_transform."""
         graph = GraphIndex(msg_src, msg_tgt, type_ptr, tgt_ptr, tgt_msgs, src_ptr, src_msgs, int(num_nodes),
                            int(num_messages), int(type_ptr.shape[0]) - 1, node_order, int(num_hub_nodes),
                            MessageRuns.of(run_ptr, bwd_group_ptr, bwd_group_w, bwd_rows_tgt, bwd_rows_src, tgt_run_ptr, tgt_run_rows))
@@ -228,6 +231,10 @@ class GraphNeuralNetwork(nn.Module):
             if msg_feat is None:
                 raise ValueError("the model has an edge-feature embedding but the minibatch carries no `msg_feat`")
             edge_features = (self.edge_embed.table, msg_feat)
+        live = []  # LiveRows of the last message-passing layer, the one before it, ...
+        if live_backward and live_arrays is not None and live_layout is not None and not return_all_states and input_transform is None:
+            live = live_rows_of(live_arrays, live_layout, graph.num_types)
+        num_mp = sum(1 for l in self._recipe if isinstance(l, nn.Module))
         h = h0
         all_states = [h0]
         stash: Dict[int, torch.Tensor] = {}
@@ -242,10 +249,12 @@ class GraphNeuralNetwork(nn.Module):
             else:
                 if isinstance(h, tuple) and not isinstance(layer, MlpMessagePassingLayer):
                     h = torch.cat(h, dim=-1)
+                depth = num_mp - 1 - li  # 0: the last layer
+                layer_graph = graph._replace(live=live[depth]) if depth < len(live) else graph
                 if isinstance(layer, MlpMessagePassingLayer) and layer.features_dimension > 0:
                     h = layer(h, graph, mk(layer.dropout_rate, 1 + li), edge_features)
                 else:
-                    h = layer(h, graph, mk(layer.dropout_rate, 1 + li))
+                    h = layer(h, layer_graph, mk(layer.dropout_rate, 1 + li))
                 li += 1
                 all_states.append(h)
         if isinstance(h, tuple):

@@ -36,7 +36,8 @@ int bl_mp_scatter_src_accum_impl(const float* g_src, int32_t ld_src, const int32
 // col_tgt: column of g_a where the rows listed by tgt_msgs start (Din: the per-message [E, 2 Din] layout, 0: the run-row layout)
 int bl_mp_scatter_grad_hubs_impl(const float* g_a, int32_t ld_ga, const int32_t* src_ptr, const int32_t* src_msgs, const int32_t* tgt_ptr,
                                  const int32_t* tgt_msgs, int32_t N, int32_t Din, int32_t split, float* g_h_lo, int32_t ld_lo, float* g_h_hi,
-                                 int32_t ld_hi, const int32_t* node_order, int32_t hub_slots, int32_t col_tgt, void* stream);
+                                 int32_t ld_hi, const int32_t* node_order, int32_t hub_slots, int32_t col_tgt, void* stream,
+                                 const int32_t* out_rows = nullptr);  // out_rows: sums of CSR segment n go to row out_rows[n]
 // bl_gemm_wgrad_h3 for a group_w that maps every group to a slice of its own: the chunks of a (group, tile) may then add in order
 // like those of a launch without group_w (deterministic mode; csrc/bl_gemm_h3.hip)
 int bl_gemm_wgrad_h3_impl(const bl_rows_packed_t* a, const uint16_t* g_packed, const int32_t* g_idx, const uint32_t* win_bits,
@@ -47,7 +48,7 @@ int bl_gemm_wgrad_h3_impl(const bl_rows_packed_t* a, const uint16_t* g_packed, c
 int bl_node_update_bwd_impl(const float* g_out, const float* h_out, int32_t nrows, int32_t Dout, bl_dropout_t drop,
                             const uint16_t* wd_packed_bwd, const float* agg, const float* mean, const float* rstd, const float* ln_g,
                             const float* dact, int32_t Dm, uint16_t* g_z_packed, float* g_bias, float* gq, uint16_t* gq_packed,
-                            float* g_ln_g, float* g_ln_b, float* gq_amax, void* stream);
+                            float* g_ln_g, float* g_ln_b, float* gq_amax, const int32_t* rows, void* stream);
 
 // per-kernel timing inside a per-layer entry point (csrc/bl_mp_layer.hip: bl_prof_*): brackets the launches made while it is alive
 // with two HIP events on `stream` when profiling is enabled.  Kinds: indices into bl_prof_kind_name's table.

@@ -759,7 +759,7 @@ __global__ __launch_bounds__(256) void mp_scatter_grad_kernel(const float* __res
                                                               int accumulate, float* __restrict__ g_h, int ld_gh,
                                                               const int* __restrict__ node_order, int split,
                                                               float* __restrict__ g_h2, int ld_gh2, int hub_slots,
-                                                              int col_tgt) {
+                                                              int col_tgt, const int* __restrict__ out_rows) {
   // The first hub_slots entries of node_order are the nodes with many incident messages (the collators put them in front).
   // One wave walking a 512-row segment eight rows at a time is 64 dependent round trips -- at the power-law configuration
   // that one wave WAS the kernel's duration (207 vs 152 us at hidden 256).  Workgroups 0 .. hub_slots - 1 therefore take ONE
@@ -776,13 +776,15 @@ __global__ __launch_bounds__(256) void mp_scatter_grad_kernel(const float* __res
   // slot (the collator counts a node as a hub candidate above 32) is wave 0's alone -- no LDS merge, no barrier, and the same
   // summation order as on the ordinary path (uniform over the workgroup: it depends on n only)
   constexpr int MPS_SPLIT_MIN = 64;
+  // out_rows (the reduced problem of the live rows, csrc/bl_mp_layer.hip): n indexes the CSRs, the sums go to row out_rows[n]
+  const size_t o = out_rows ? (size_t)out_rows[n] : (size_t)n;
   const bool split4 = hub_wg && (src_ptr[n + 1] - src_ptr[n]) + (tgt_ptr ? tgt_ptr[n + 1] - tgt_ptr[n] : 0) >= MPS_SPLIT_MIN;
   if (hub_wg && !split4 && wave > 0) return;
   float acc[NV];
 #pragma unroll
   for (int j = 0; j < NV; ++j) {
     const int d = lane + 64 * j;
-    acc[j] = (accumulate && d < Din && !(split4 && wave > 0)) ? (d < split ? g_h[(size_t)n * ld_gh + d] : g_h2[(size_t)n * ld_gh2 + d - split]) : 0.f;
+    acc[j] = (accumulate && d < Din && !(split4 && wave > 0)) ? (d < split ? g_h[o * ld_gh + d] : g_h2[o * ld_gh2 + d - split]) : 0.f;
   }
 #pragma unroll
   for (int part = 0; part < 2; ++part) {
@@ -840,8 +842,8 @@ __global__ __launch_bounds__(256) void mp_scatter_grad_kernel(const float* __res
   for (int j = 0; j < NV; ++j) {
     const int d = lane + 64 * j;
     if (d < Din) {
-      if (d < split) g_h[(size_t)n * ld_gh + d] = acc[j];
-      else g_h2[(size_t)n * ld_gh2 + d - split] = acc[j];
+      if (d < split) g_h[o * ld_gh + d] = acc[j];
+      else g_h2[o * ld_gh2 + d - split] = acc[j];
     }
   }
 }
@@ -1148,13 +1150,13 @@ int bl_act_bwd_impl(const float* g_y, const float* y, int32_t nrows, int32_t N, 
 static int mp_scatter_launch(const char* who, const float* g_a, int32_t ld_ga, const int32_t* src_ptr, const int32_t* src_msgs,
                              const int32_t* tgt_ptr, const int32_t* tgt_msgs, int32_t N, int32_t Din, int32_t accumulate, float* g_h,
                              int32_t ld_gh, const int32_t* node_order, int32_t split, float* g_h2, int32_t ld_gh2, int32_t hub_slots,
-                             void* stream, int32_t col_tgt = -1) {
+                             void* stream, int32_t col_tgt = -1, const int32_t* out_rows = nullptr) {
   if (col_tgt < 0) col_tgt = Din;
   hipStream_t st = (hipStream_t)stream;
   const int hubs = (node_order && hub_slots > 0) ? min(hub_slots, N) : 0;
   const dim3 grid(hubs + (N - hubs + 3) / 4);
   DISPATCH_NV(Din, hipLaunchKernelGGL((mp_scatter_grad_kernel<NV>), grid, dim3(256), 0, st, g_a, ld_ga, src_ptr, src_msgs, tgt_ptr,
-                                       tgt_msgs, N, Din, accumulate, g_h, ld_gh, node_order, split, g_h2, ld_gh2, hubs, col_tgt))
+                                       tgt_msgs, N, Din, accumulate, g_h, ld_gh, node_order, split, g_h2, ld_gh2, hubs, col_tgt, out_rows))
   BL_LAUNCH_CHECK(who);
   return BL_OK;
 }
@@ -1174,13 +1176,14 @@ extern "C" int bl_mp_scatter_grad(const float* g_a, int32_t ld_ga, const int32_t
 // (bl_mp_layer_t.num_hub_slots): g_h_hi == NULL -> one output of Din columns (split ignored)
 int bl_mp_scatter_grad_hubs_impl(const float* g_a, int32_t ld_ga, const int32_t* src_ptr, const int32_t* src_msgs, const int32_t* tgt_ptr,
                                  const int32_t* tgt_msgs, int32_t N, int32_t Din, int32_t split, float* g_h_lo, int32_t ld_lo, float* g_h_hi,
-                                 int32_t ld_hi, const int32_t* node_order, int32_t hub_slots, int32_t col_tgt, void* stream) {
+                                 int32_t ld_hi, const int32_t* node_order, int32_t hub_slots, int32_t col_tgt, void* stream,
+                                 const int32_t* out_rows) {
   if (N == 0) return BL_OK;
   BL_CHECK_ARG(g_a && src_ptr && src_msgs && tgt_ptr && tgt_msgs && g_h_lo && Din > 0 && Din <= 512 && col_tgt >= 0 && ld_ga >= col_tgt + Din,
                "bl_mp_scatter_grad (layer call): bad argument");
   BL_CHECK_ARG(g_h_hi == nullptr || (split > 0 && split < Din && ld_lo >= split && ld_hi >= Din - split), "bl_mp_scatter_grad (layer call): split");
   return mp_scatter_launch("bl_mp_scatter_grad", g_a, ld_ga, src_ptr, src_msgs, tgt_ptr, tgt_msgs, N, Din, 0, g_h_lo, ld_lo, node_order,
-                           g_h_hi ? split : Din, g_h_hi, ld_hi, hub_slots, stream, col_tgt);
+                           g_h_hi ? split : Din, g_h_hi, ld_hi, hub_slots, stream, col_tgt, out_rows);
 }
 
 extern "C" int bl_mp_scatter_grad_runs(const float* g_a, int32_t ld_ga, const int32_t* src_ptr, const int32_t* src_msgs,
@@ -1189,6 +1192,14 @@ extern "C" int bl_mp_scatter_grad_runs(const float* g_a, int32_t ld_ga, const in
                                        int32_t num_hub_slots, void* stream) {
   return bl_mp_scatter_grad_hubs_impl(g_a, ld_ga, src_ptr, src_msgs, tgt_run_ptr, tgt_run_rows, N, Din, split, g_h_lo, ld_lo, g_h_hi, ld_hi,
                                       node_order, num_hub_slots, 0, stream);
+}
+
+extern "C" int bl_mp_scatter_grad_rows(const float* g_a, int32_t ld_ga, const int32_t* src_ptr, const int32_t* src_msgs,
+                                       const int32_t* run_csr_ptr, const int32_t* run_csr_rows, const int32_t* out_rows, int32_t n,
+                                       int32_t Din, int32_t split, float* g_h_lo, int32_t ld_lo, float* g_h_hi, int32_t ld_hi, void* stream) {
+  BL_CHECK_ARG(out_rows || n == 0, "bl_mp_scatter_grad_rows: null row index");
+  return bl_mp_scatter_grad_hubs_impl(g_a, ld_ga, src_ptr, src_msgs, run_csr_ptr, run_csr_rows, n, Din, split, g_h_lo, ld_lo, g_h_hi, ld_hi,
+                                      nullptr, 0, 0, stream, out_rows);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1233,6 +1244,38 @@ extern "C" int bl_winbits_or_runs(uint32_t* bits, int32_t ld_bits, const int32_t
   else
     hipLaunchKernelGGL((winbits_or_runs_kernel<uint32_t>), grid, dim3(256), 0, (hipStream_t)stream, bits, ld_bits, run_ptr, E, R, pieces);
   BL_LAUNCH_CHECK("bl_winbits_or_runs");
+  return BL_OK;
+}
+
+// Compact copy of the routing masks of the live messages (csrc/bl_mp_layer.hip): out[i, 0:words] = bits[rows[i], 0:words].  One thread
+// per (row, V-sized piece); a row id outside 0..nrows_in-1 (never from the collators) reads row 0 instead of memory it does not own.
+template <class V>
+__global__ __launch_bounds__(256) void winbits_gather_kernel(const uint32_t* __restrict__ bits, int ld_bits, int nrows_in,
+                                                             const int* __restrict__ rows, int n, int pieces, uint32_t* __restrict__ out,
+                                                             int ld_out) {
+  const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= (long long)n * pieces) return;
+  const int i = (int)(t / pieces), p = (int)(t - (long long)i * pieces);
+  int e = rows[i];
+  if (e < 0 || e >= nrows_in) e = 0;
+  constexpr int NW = sizeof(V) / 4;
+  *reinterpret_cast<V*>(out + (size_t)i * ld_out + (size_t)p * NW) = *reinterpret_cast<const V*>(bits + (size_t)e * ld_bits + (size_t)p * NW);
+}
+
+extern "C" int bl_winbits_gather(const uint32_t* bits, int32_t ld_bits, int32_t nrows_in, const int32_t* rows, int32_t n, int32_t words,
+                                 uint32_t* out, int32_t ld_out, void* stream) {
+  if (n == 0) return BL_OK;
+  BL_CHECK_ARG(bits && rows && out && n > 0 && nrows_in > 0 && words > 0 && ld_bits >= words && ld_out >= words,
+               "bl_winbits_gather: null pointer, no input rows or a row stride below words");
+  const bool vec = words % 4 == 0 && ld_bits % 4 == 0 && ld_out % 4 == 0 && bl_aligned16(bits) && bl_aligned16(out);
+  const int pieces = vec ? words / 4 : words;
+  const long long total = (long long)n * pieces;
+  const dim3 grid((unsigned)((total + 255) / 256));
+  if (vec)
+    hipLaunchKernelGGL((winbits_gather_kernel<uint4>), grid, dim3(256), 0, (hipStream_t)stream, bits, ld_bits, nrows_in, rows, n, pieces, out, ld_out);
+  else
+    hipLaunchKernelGGL((winbits_gather_kernel<uint32_t>), grid, dim3(256), 0, (hipStream_t)stream, bits, ld_bits, nrows_in, rows, n, pieces, out, ld_out);
+  BL_LAUNCH_CHECK("bl_winbits_gather");
   return BL_OK;
 }
 

@@ -11,7 +11,9 @@
 //             units from the non-zeros, or bf16x6 GEMM) -> segmented sums over the src / tgt CSRs (two outputs for a
 //             folded concat).  With the run arrays of the minibatch (bl_mp_layer_t.num_runs; f16x3, max aggregation, matrix cores):
 //             OR of the routing masks per run -> both routed GEMMs over E + R rows of Din columns (source halves per message,
-//             target halves per run) -> segmented sums over the source CSR and the run CSR
+//             target halves per run) -> segmented sums over the source CSR and the run CSR.  With the live arrays of the minibatch
+//             (bl_mp_layer_t.live_nodes: the rows of g_out that can be non-zero at all) the same chain over the live rows only:
+//             N' nodes, E' + R' GEMM rows, a compact copy of their routing masks, sums into a zero-filled [N, Din]
 //   forward-only (saved == NULL): the same forward without any store that only a backward pass reads
 // The caller owns every buffer: `saved` lives from forward to backward, `ws` only during the call
 // (sizes from bl_mp_layer_saved_bytes / bl_mp_layer_workspace_bytes); nothing is allocated here except three
@@ -41,10 +43,13 @@ const char* kProfNames[] = {"pack_rows",      "msg_gemm_x6",  "segment_max_ln", 
                             "linear_x6_epi", "linear_dgrad_x6", "gemm_wgrad_x6", "attn_probs_fwd", "attn_probs_bwd", "attn_rows_times",
                             "attn_transposed_times", "add_layernorm", "layernorm_bwd_branch",
                             // the run rows of bl_mp_layer_bwd: OR of the routing masks per run (bl_winbits_or_runs)
-                            "winbits_or_runs"};
+                            "winbits_or_runs",
+                            // the live rows of bl_mp_layer_bwd: compact copy of the live messages' routing masks (bl_winbits_gather)
+                            "winbits_gather_live"};
 constexpr int kProfWinbitsOrRuns = 26;
+constexpr int kProfWinbitsGatherLive = 27;
 constexpr int kProfKinds = sizeof(kProfNames) / sizeof(kProfNames[0]);
-static_assert(kProfWinbitsOrRuns == kProfKinds - 1, "kProfWinbitsOrRuns must index its name");
+static_assert(kProfWinbitsGatherLive == kProfKinds - 1 && kProfWinbitsOrRuns == kProfKinds - 2, "the kProf constants must index their names");
 
 hipEvent_t prof_event() {
   if (!g_prof_pool.empty()) {
@@ -228,6 +233,23 @@ bool run_rows_on() {
   }
   return g_run_rows != 0;
 }
+// bl_set_live_backward / BL_LIVE_BWD: backward over the live rows of a descriptor that carries them (bl_mp_layer_t.live_nodes)
+int g_live_bwd = -1;
+bool live_bwd_on() {
+  if (g_live_bwd < 0) {
+    const char* e = getenv("BL_LIVE_BWD");
+    g_live_bwd = (e && e[0] == '0') ? 0 : 1;
+  }
+  return g_live_bwd != 0;
+}
+// a descriptor carries the live arrays when all of them are there (the per-message ones may be NULL when no message is live)
+inline bool layer_has_live(const bl_mp_layer_t* L) {
+  if (!(L->live_nodes && L->live_num_nodes > 0 && L->live_num_nodes <= L->N && L->live_recv && L->live_num_recv > 0 && L->live_num_recv <= L->N &&
+        L->live_num_msgs >= 0 && L->live_num_msgs <= L->E && L->live_num_runs >= 0 && L->live_num_runs <= L->live_num_msgs && L->live_group_ptr))
+    return false;
+  return L->live_num_msgs == 0 || (L->live_msgs && L->live_run_ptr && L->live_rows_tgt && L->live_rows_src && L->live_src_ptr &&
+                                   L->live_src_msgs && L->live_run_csr_ptr && L->live_run_csr_rows);
+}
 // R of a descriptor that carries the run arrays (all of them), else 0; decides the rows of the routing bitmask in `saved`
 inline int layer_runs(const bl_mp_layer_t* L) {
   return (L->num_runs > 0 && L->run_ptr && L->bwd_group_ptr && L->bwd_group_w && L->bwd_rows_tgt && L->bwd_rows_src && L->tgt_run_ptr &&
@@ -286,6 +308,14 @@ extern "C" int32_t bl_set_run_rows(int32_t on) {
   g_run_rows = on != 0 ? 1 : 0;
   return prev;
 }
+
+extern "C" int32_t bl_set_live_backward(int32_t on) {
+  const int32_t prev = live_bwd_on() ? 1 : 0;
+  g_live_bwd = on != 0 ? 1 : 0;
+  return prev;
+}
+
+extern "C" int32_t bl_get_live_backward(void) { return live_bwd_on() ? 1 : 0; }
 
 extern "C" int64_t bl_mp_layer_saved_bytes(int32_t N, int32_t E, int32_t Din, int32_t Dm, int32_t msg_act) {
   return (int64_t)carve_saved(nullptr, N, E, Din, Dm, msg_act).bytes;
@@ -452,14 +482,29 @@ extern "C" int bl_mp_layer_bwd(const bl_mp_layer_t* L, const float* h_out, const
   BL_CHECK_ARG(dense_x6 || L->Wd_packed == nullptr, "bl_mp_layer_bwd: Wd_packed given without Wd_packed_bwd");
   // act backward -> dense input gradient -> LayerNorm backward x activation derivative in ONE kernel (csrc/bl_node_bwd.hip)
   const bool fused_node = dense_x6 && g_fused_node_bwd && bl_node_update_bwd_ok(Dm, Dout);
+  // Live rows: the caller states that g_out is zero outside the rows live_nodes (the heads read the encoder's output through one
+  // gather of a few rows, and a layer's input can receive a gradient only at its live rows and at the sources of the messages
+  // into them).  Rows with a zero gradient contribute additions of zero to every result, so the whole chain runs over the N' live
+  // nodes and the E' messages / R' runs into them: the node update's backward reads its rows through live_nodes and writes g_z and
+  // gq compact, the GEMMs see an ordinary smaller problem (operand rows gathered by global node id, gq rows by position in
+  // live_nodes, a compact copy of the routing masks), the segmented sums write the rows live_recv of a zero-filled [N, Din].
+  // THE place where a layer's backward takes this form: whatever the run rows and the one-kernel node update exclude (bf16x6 and
+  // f16x1, sum / mean, the deterministic mode, Din not a multiple of 128, the vector-unit input gradient) keeps the full backward.
+  const int Ex = L->live_num_msgs, Rx = L->live_num_runs;
+  const size_t live_ga_bytes = al(((size_t)Ex + Rx) * Din * 4);
+  const bool live = run_rows && fused_node && live_bwd_on() && layer_has_live(L) &&
+                    ((uint64_t)N * (uint64_t)Dout < (1ull << 32) || L->drop.p <= 0.f) &&  // (the dropout counter is the node's own row)
+                    live_ga_bytes + ((size_t)Ex + Rx) * (Dm / 32) * 4 <= (size_t)E * 2 * Din * 4;  // (compact masks behind the compact g_a)
+  const int Nn = live ? L->live_num_nodes : N;  // rows of the node update's backward and of everything it writes
+  uint32_t* live_bits = live ? (uint32_t*)((char*)B.g_a + live_ga_bytes) : nullptr;
   // f16x3 message GEMMs: gq leaves its producer in fp32 (B.g_ln); its packed form is made below, once its amax is known
   const bool h3 = msg_h3();
   if (h3 && E > 0 && hipMemsetAsync(B.amax, 0, 4, st) != hipSuccess) { bl_set_error("bl_mp_layer_bwd: memset failed"); return BL_EINVAL; }
   if (fused_node) {
-    ProfScope ps(12, 2.0 * N * (double)Dm * Dout, st, false);
-    BL_TRY(bl_node_update_bwd_impl(g_out, h_out, N, Dout, L->drop, L->Wd_packed_bwd, S.agg, S.mean, S.rstd, L->ln_g, S.dact, Dm,
+    ProfScope ps(12, 2.0 * Nn * (double)Dm * Dout, st, false);
+    BL_TRY(bl_node_update_bwd_impl(g_out, h_out, Nn, Dout, L->drop, L->Wd_packed_bwd, S.agg, S.mean, S.rstd, L->ln_g, S.dact, Dm,
                                    (uint16_t*)B.g_z, g_bd, (vec_dgrad || h3) ? B.g_ln : nullptr, h3 ? nullptr : B.gqp, g_ln_g, g_ln_b,
-                                   (h3 && E > 0) ? B.amax : nullptr, st));
+                                   (h3 && E > 0) ? B.amax : nullptr, live ? L->live_nodes : nullptr, st));
   } else {  // y = drop(tanh(z)): g_z (packed for the bf16x6 GEMMs), bias gradient
     ProfScope ps(4, 0.0, st, false);
     BL_TRY(bl_act_bwd_impl(g_out, h_out, N, Dout, Dout, BL_ACT_TANH, L->drop, dense_x6 ? nullptr : B.g_z, g_bd,
@@ -474,10 +519,11 @@ extern "C" int bl_mp_layer_bwd(const bl_mp_layer_t* L, const float* h_out, const
     (void)hipStreamWaitEvent(side, ev->fork1, 0);
   }
   {  // dense weight gradient, next to the input-gradient chain
-    ProfScope ps(5, 2.0 * N * (double)Dm * Dout, side, two);
-    if (dense_x6) {
-      p1.xp[0] = (const uint16_t*)S.ln_out; p1.width[0] = Dm;
-      BL_TRY(bl_gemm_wgrad_x6(&p1, (const uint16_t*)B.g_z, nullptr, nullptr, nullptr, 1, N, Dout, Dm, g_Wd, 0, Dout, side));
+    ProfScope ps(5, 2.0 * Nn * (double)Dm * Dout, side, two);
+    if (dense_x6) {  // (live: the compact g_z against the LayerNorm outputs of the live nodes)
+      p1.xp[0] = (const uint16_t*)S.ln_out; p1.width[0] = Dm; p1.idx[0] = live ? L->live_nodes : nullptr;
+      BL_TRY(bl_gemm_wgrad_x6(&p1, (const uint16_t*)B.g_z, nullptr, nullptr, nullptr, 1, Nn, Dout, Dm, g_Wd, 0, Dout, side));
+      p1.idx[0] = nullptr;
     } else {
       r1.x[0] = S.ln_out; r1.ld[0] = Dm; r1.width[0] = Dm;
       BL_TRY(bl_gemm_wgrad(&r1, B.g_z, Dout, nullptr, nullptr, 1, N, Dout, Dm, g_Wd, 0, Dout, side));
@@ -506,12 +552,27 @@ extern "C" int bl_mp_layer_bwd(const bl_mp_layer_t* L, const float* h_out, const
   if (h3 && E > 0) {  // amax of gq on the device -> its power-of-two scale -> two fp16 planes
     ProfScope ps(16, 0.0, st, two);
     if (!fused_node) BL_TRY(bl_amax(B.g_ln, (int64_t)N * Dm, B.amax, st));  // (the fused node-update backward took it on the way)
-    BL_TRY(bl_pack_f16x2(B.g_ln, Dm, N, Dm, Dm, 0, 1.0f, B.amax, B.gqp, st));
+    BL_TRY(bl_pack_f16x2(B.g_ln, Dm, Nn, Dm, Dm, 0, 1.0f, B.amax, B.gqp, st));  // (rows of zeros left out do not change the amax)
   }
-  if (run_rows) {  // (before the weight-gradient fork: both GEMMs read the runs' masks)
+  if (live && Ex > 0) {
+    ProfScope ps(kProfWinbitsGatherLive, 0.0, st, two);
+    BL_TRY(bl_winbits_gather(S.bits, Dm / 32, E, L->live_msgs, Ex, Dm / 32, live_bits, Dm / 32, st));
+  }
+  if (live) {
+    if (Ex > 0) {
+      ProfScope ps(kProfWinbitsOrRuns, 0.0, st, two);
+      BL_TRY(bl_winbits_or_runs(live_bits, Dm / 32, L->live_run_ptr, Ex, Rx, Dm / 32, st));
+    }
+  } else if (run_rows) {  // (before the weight-gradient fork: both GEMMs read the runs' masks)
     ProfScope ps(kProfWinbitsOrRuns, 0.0, st, two);
     BL_TRY(bl_winbits_or_runs(S.bits, Dm / 32, L->run_ptr, E, R, Dm / 32, st));
   }
+  // the row space of the two routed GEMMs on the run-row path: the minibatch's E + R rows, or the E' + R' live ones
+  const int rr_rows = live ? Ex + Rx : E + R;
+  const int32_t* rr_group_ptr = live ? L->live_group_ptr : L->bwd_group_ptr;
+  const int32_t* rr_rows_tgt = live ? L->live_rows_tgt : L->bwd_rows_tgt;  // live: positions in live_nodes (gq is compact)
+  const int32_t* rr_rows_src = live ? L->live_rows_src : L->bwd_rows_src;  // node ids either way (the packed layer input is whole)
+  const uint32_t* rr_bits = live ? live_bits : bits;
   // The routed weight gradient (side stream) reads what is ready at this point: the packed layer input, the packed gradient operand, the
   // routing bits.  WHEN it is forked decides what it runs next to.  Layers up to 128 wide: here, side by side with the routed input
   // gradient.  Wider layers (the hidden-256 configurations): behind the segmented sums, i.e. next to the bandwidth-bound tail of this layer
@@ -530,10 +591,10 @@ extern "C" int bl_mp_layer_bwd(const bl_mp_layer_t* L, const float* h_out, const
       (void)hipStreamWaitEvent(side, ev->fork2, 0);
     }
     if (run_rows) {  // one source: the message rows gather h[src], the run rows h[tgt]; gW viewed as [2 T, Din, Dm]
-      ProfScope ps(14, 2.0 * ((double)E + R) * Din * Dm, side, two);
-      a.idx[0] = L->bwd_rows_src; a.xp[1] = nullptr; a.idx[1] = nullptr; a.width[1] = 0;
+      ProfScope ps(14, 2.0 * (double)rr_rows * Din * Dm, side, two);
+      a.idx[0] = rr_rows_src; a.xp[1] = nullptr; a.idx[1] = nullptr; a.width[1] = 0;
       a.nsrc = 1;
-      BL_TRY(bl_gemm_wgrad_h3_impl(&a, B.gqp, L->bwd_rows_tgt, bits, Dm / 32, L->bwd_group_ptr, L->bwd_group_w, 2 * T, E + R, Dm, Din,
+      BL_TRY(bl_gemm_wgrad_h3_impl(&a, B.gqp, rr_rows_tgt, rr_bits, Dm / 32, rr_group_ptr, L->bwd_group_w, 2 * T, rr_rows, Dm, Din,
                                    1.0f / BL_H3_ROW_SCALE, B.amax, g_W, (int64_t)Din * Dm, Dm, true, side));
     } else if (h3) {
       ProfScope ps(14, 2.0 * E * (2.0 * Din) * Dm, side, two);
@@ -549,7 +610,8 @@ extern "C" int bl_mp_layer_bwd(const bl_mp_layer_t* L, const float* h_out, const
     }
     return BL_OK;
   };
-  if (E > 0) {
+  const bool msgs = E > 0 && !(live && Ex == 0);  // (no live message: nothing reaches W or the layer input)
+  if (msgs) {
     if (!late_fork) BL_TRY(launch_wgrad());
     bl_rows_packed_t g;
     g.xp[0] = B.gqp; g.xp[1] = g.xp[2] = nullptr; g.idx[0] = L->msg_tgt; g.idx[1] = g.idx[2] = nullptr;
@@ -576,10 +638,10 @@ extern "C" int bl_mp_layer_bwd(const bl_mp_layer_t* L, const float* h_out, const
       ProfScope ps(9, 2.0 * N * (2.0 * Din) * Dm, st, two);
       BL_TRY(bl_routed_dgrad_vec(B.g_ln, Dm, L->msg_tgt, S.bits, Dm / 32, L->type_ptr, T, L->Wt, E, Dm, 2 * Din, B.g_a, 2 * Din, st));
     } else if (run_rows) {  // g_a [E + R, Din]: rows 0..E-1 the messages' source halves, E..E+R-1 the runs' target halves
-      ProfScope ps(15, 2.0 * ((double)E + R) * Din * Dm, st, two);
-      g.idx[0] = L->bwd_rows_tgt;
-      BL_TRY(bl_gemm_rows_h3(&g, bits, Dm / 32, w_packed_bwd, bl_packed_weight_elems_h3(1, Dm, Din), L->bwd_group_ptr, L->bwd_group_w, 2 * T,
-                             E + R, Din, Dm, 1.0f / BL_H3_W_SCALE, B.amax, B.g_a, Din, st));
+      ProfScope ps(15, 2.0 * (double)rr_rows * Din * Dm, st, two);
+      g.idx[0] = rr_rows_tgt;
+      BL_TRY(bl_gemm_rows_h3(&g, rr_bits, Dm / 32, w_packed_bwd, bl_packed_weight_elems_h3(1, Dm, Din), rr_group_ptr, L->bwd_group_w, 2 * T,
+                             rr_rows, Din, Dm, 1.0f / BL_H3_W_SCALE, B.amax, B.g_a, Din, st));
     } else if (h3) {
       ProfScope ps(15, 2.0 * E * (2.0 * Din) * Dm, st, two);
       BL_TRY(bl_gemm_rows_h3(&g, bits, Dm / 32, w_packed_bwd, bl_packed_weight_elems_h3(1, Dm, 2 * Din), L->type_ptr, nullptr, T, E, 2 * Din,
@@ -597,14 +659,26 @@ extern "C" int bl_mp_layer_bwd(const bl_mp_layer_t* L, const float* h_out, const
   if (!fused_sums) {
     ProfScope ps(10, 0.0, st, two);
     // E == 0: both CSRs are empty and g_a is never read
-    if (run_rows)
+    if (live) {  // sums over the reduced CSRs into the rows live_recv of a zero-filled result
+      const int split = g_h_hi ? width_lo : Din;
+      auto zero = [&](float* p, int ld, int w) {
+        return ld == w ? hipMemsetAsync(p, 0, (size_t)N * w * 4, st) : hipMemset2DAsync(p, (size_t)ld * 4, 0, (size_t)w * 4, N, st);
+      };
+      if (zero(g_h_lo, ld_lo, split) != hipSuccess || (g_h_hi && zero(g_h_hi, ld_hi, Din - split) != hipSuccess)) {
+        bl_set_error("bl_mp_layer_bwd: memset failed");
+        return BL_EINVAL;
+      }
+      if (Ex > 0)
+        BL_TRY(bl_mp_scatter_grad_hubs_impl(B.g_a, Din, L->live_src_ptr, L->live_src_msgs, L->live_run_csr_ptr, L->live_run_csr_rows,
+                                            L->live_num_recv, Din, width_lo, g_h_lo, ld_lo, g_h_hi, ld_hi, nullptr, 0, 0, st, L->live_recv));
+    } else if (run_rows)
       BL_TRY(bl_mp_scatter_grad_hubs_impl(B.g_a, Din, L->src_ptr, L->src_msgs, L->tgt_run_ptr, L->tgt_run_rows, N, Din, width_lo, g_h_lo, ld_lo,
                                           g_h_hi, ld_hi, node_order, L->num_hub_slots, 0, st));
     else
     BL_TRY(bl_mp_scatter_grad_hubs_impl(B.g_a, 2 * Din, L->src_ptr, L->src_msgs, L->tgt_ptr, L->tgt_msgs, N, Din, width_lo, g_h_lo, ld_lo,
                                         g_h_hi, ld_hi, node_order, L->num_hub_slots, Din, st));
   }
-  if (E > 0 && late_fork) BL_TRY(launch_wgrad());
+  if (msgs && late_fork) BL_TRY(launch_wgrad());
   if (two && join_side) {
     (void)hipEventRecord(ev->join, side);
     (void)hipStreamWaitEvent(st, ev->join, 0);

@@ -72,13 +72,16 @@ __device__ __forceinline__ float rowgroup_reduce8(float (&v)[8], int lane) {
   return v[0] + __shfl_xor(v[0], 32, 64);
 }
 
-template <int NT>
+// ROWS: the tile's nodes are rows[row0 + i] (the live rows of bl_mp_layer_bwd): g_out, h_out, the aggregate, its activation
+// derivative and the LayerNorm statistics are read there (and the dropout counter is that row's), the packed g_z and gq are
+// written compact, row row0 + i of [nrows, .]
+template <int NT, bool ROWS>
 __global__ __launch_bounds__(256, 2) void node_bwd_kernel(
     const float* __restrict__ g_out, const float* __restrict__ h_out, int nrows, int K, bl_drop_dev drop,
     uint4* __restrict__ gz_packed, float* __restrict__ g_bias, const uint4* __restrict__ bp, const float* __restrict__ agg,
     const float* __restrict__ mean, const float* __restrict__ rstd, const float* __restrict__ gamma,
     const float* __restrict__ dact, float* __restrict__ gq_f32, uint32_t* __restrict__ gq_packed, float* __restrict__ g_gamma,
-    float* __restrict__ g_beta, int ntiles, float* __restrict__ gq_amax) {
+    float* __restrict__ g_beta, int ntiles, float* __restrict__ gq_amax, const int* __restrict__ rows) {
   constexpr int Dm = 128 * NT;
   constexpr int FR = 2 * NT;  // accumulator fragments (32 x 32) per wave
   // operand images of a stage (As: 64 rows, Bs: Dm rows); after the last stage the same memory holds the four waves' result
@@ -110,6 +113,7 @@ __global__ __launch_bounds__(256, 2) void node_bwd_kernel(
     const int tr = min(NB_ROWS, nrows - row0);  // rows of this tile
     const bool a_ok = p_row < tr;
     const size_t a_row = (size_t)(row0 + (a_ok ? p_row : 0));
+    const size_t a_in = ROWS ? (size_t)rows[a_row] : a_row;  // where the inputs of compact row a_row live
 
     // staging registers (scalars, not arrays: hipcc keeps small arrays that cross the stage loop in scratch)
     float4 rg0, rg1, ry0, ry1;
@@ -131,8 +135,8 @@ __global__ __launch_bounds__(256, 2) void node_bwd_kernel(
   }
 #define NB_LOAD_STAGE(k0_)                                                                   \
   {                                                                                          \
-    const float* gp_ = g_out + a_row * K + (k0_) + 8 * p_kg;                                 \
-    const float* yp_ = h_out + a_row * K + (k0_) + 8 * p_kg;                                 \
+    const float* gp_ = g_out + a_in * K + (k0_) + 8 * p_kg;                                  \
+    const float* yp_ = h_out + a_in * K + (k0_) + 8 * p_kg;                                  \
     rg0 = *reinterpret_cast<const float4*>(gp_);                                             \
     rg1 = *reinterpret_cast<const float4*>(gp_ + 4);                                         \
     ry0 = *reinterpret_cast<const float4*>(yp_);                                             \
@@ -151,7 +155,7 @@ __global__ __launch_bounds__(256, 2) void node_bwd_kernel(
     _Pragma("unroll") for (int u = 0; u < 8; ++u) {                                          \
       float yu_ = yy_[u];                                                                    \
       if (drop.thresh) {                                                                     \
-        const bool keep_ = bl_keep(drop, (uint32_t)(row0 + p_row) * (uint32_t)K + (uint32_t)(c0_ + u)); \
+        const bool keep_ = bl_keep(drop, (uint32_t)(ROWS ? (int)a_in : row0 + p_row) * (uint32_t)K + (uint32_t)(c0_ + u)); \
         gg_[u] = keep_ ? gg_[u] * drop.scale : 0.f;                                          \
         yu_ = yu_ * (1.0f / drop.scale);                                                     \
       }                                                                                      \
@@ -224,7 +228,7 @@ __global__ __launch_bounds__(256, 2) void node_bwd_kernel(
     // ---- epilogue: LayerNorm backward of this lane's row (layernorm_bwd_kernel's arithmetic) ----
     const int m = wm * 32 + li;  // row inside the tile
     const bool r_ok = m < tr;
-    const size_t grow = (size_t)(row0 + (r_ok ? m : 0));
+    const size_t grow = ROWS ? (size_t)rows[row0 + (r_ok ? m : 0)] : (size_t)(row0 + (r_ok ? m : 0));
     const float mu = mean[grow], rs = rstd[grow];
     const int cbase = wn * (Dm / 2) + 4 * half;  // this lane's first column; + 32 f + 8 gq + u
     // one base pointer per array: the (f, gq) steps are compile-time offsets of the load / store instructions
@@ -344,16 +348,16 @@ __global__ __launch_bounds__(256, 2) void node_bwd_kernel(
   }
 }
 
-template <int NT>
+template <int NT, bool ROWS>
 int node_bwd_launch(const float* g_out, const float* h_out, int nrows, int K, bl_drop_dev drop, uint16_t* gz_packed, float* g_bias,
                     const uint16_t* wd_packed_bwd, const float* agg, const float* mean, const float* rstd, const float* gamma,
-                    const float* dact, float* gq_f32, uint16_t* gq_packed, float* g_gamma, float* g_beta, float* gq_amax, hipStream_t st) {
-  const int resident = bl_resident_workgroups<node_bwd_kernel<NT>>(256, 1);
+                    const float* dact, float* gq_f32, uint16_t* gq_packed, float* g_gamma, float* g_beta, float* gq_amax, const int32_t* rows, hipStream_t st) {
+  const int resident = bl_resident_workgroups<node_bwd_kernel<NT, ROWS>>(256, 1);
   const int ntiles = (nrows + NB_ROWS - 1) / NB_ROWS;
   const int grid = ntiles < resident ? ntiles : resident;
-  hipLaunchKernelGGL((node_bwd_kernel<NT>), dim3(grid), dim3(256), 0, st, g_out, h_out, nrows, K, drop,
+  hipLaunchKernelGGL((node_bwd_kernel<NT, ROWS>), dim3(grid), dim3(256), 0, st, g_out, h_out, nrows, K, drop,
                      reinterpret_cast<uint4*>(gz_packed), g_bias, reinterpret_cast<const uint4*>(wd_packed_bwd), agg, mean, rstd, gamma,
-                     dact, gq_f32, reinterpret_cast<uint32_t*>(gq_packed), g_gamma, g_beta, ntiles, gq_amax);
+                     dact, gq_f32, reinterpret_cast<uint32_t*>(gq_packed), g_gamma, g_beta, ntiles, gq_amax, rows);
   return BL_OK;
 }
 }  // namespace
@@ -367,14 +371,25 @@ extern "C" int bl_node_update_bwd(const float* g_out, const float* h_out, int32_
                                   const float* ln_g, const float* dact, int32_t Dm, uint16_t* g_z_packed, float* g_bias,
                                   float* gq, uint16_t* gq_packed, float* g_ln_g, float* g_ln_b, void* stream) {
   return bl_node_update_bwd_impl(g_out, h_out, nrows, Dout, drop, wd_packed_bwd, agg, mean, rstd, ln_g, dact, Dm, g_z_packed, g_bias, gq,
-                                 gq_packed, g_ln_g, g_ln_b, nullptr, stream);
+                                 gq_packed, g_ln_g, g_ln_b, nullptr, nullptr, stream);
+}
+
+extern "C" int bl_node_update_bwd_rows(const float* g_out, const float* h_out, const int32_t* rows, int32_t nrows, int32_t Dout,
+                                       bl_dropout_t drop, const uint16_t* wd_packed_bwd, const float* agg, const float* mean,
+                                       const float* rstd, const float* ln_g, const float* dact, int32_t Dm, uint16_t* g_z_packed,
+                                       float* g_bias, float* gq, uint16_t* gq_packed, float* g_ln_g, float* g_ln_b, void* stream) {
+  BL_CHECK_ARG(rows || nrows == 0, "bl_node_update_bwd_rows: null row index");
+  return bl_node_update_bwd_impl(g_out, h_out, nrows, Dout, drop, wd_packed_bwd, agg, mean, rstd, ln_g, dact, Dm, g_z_packed, g_bias, gq,
+                                 gq_packed, g_ln_g, g_ln_b, nullptr, rows, stream);
 }
 
 // + gq_amax (optional, device float, zeroed by the caller): max |gq| is added to it with one atomic max per workgroup
+// + rows (optional, int32 [nrows]): the nodes to work on -- every per-node input is read at rows[i], g_z_packed / gq / gq_packed are
+//   written at row i (the caller guarantees rows[i] inside the inputs' row range)
 int bl_node_update_bwd_impl(const float* g_out, const float* h_out, int32_t nrows, int32_t Dout, bl_dropout_t drop,
                             const uint16_t* wd_packed_bwd, const float* agg, const float* mean, const float* rstd, const float* ln_g,
                             const float* dact, int32_t Dm, uint16_t* g_z_packed, float* g_bias, float* gq, uint16_t* gq_packed,
-                            float* g_ln_g, float* g_ln_b, float* gq_amax, void* stream) {
+                            float* g_ln_g, float* g_ln_b, float* gq_amax, const int32_t* rows, void* stream) {
   if (nrows == 0) return BL_OK;
   BL_CHECK_ARG(g_out && h_out && wd_packed_bwd && agg && mean && rstd && ln_g && g_z_packed && (gq || gq_packed) && g_ln_g && g_ln_b,
                "bl_node_update_bwd: null pointer");
@@ -387,12 +402,14 @@ int bl_node_update_bwd_impl(const float* g_out, const float* h_out, int32_t nrow
   const bl_drop_dev d = bl_make_drop(drop);
   hipStream_t st = (hipStream_t)stream;
   int rc;
+#define NB_LAUNCH(NT_, ROWS_)                                                                                                        \
+  node_bwd_launch<NT_, ROWS_>(g_out, h_out, nrows, Dout, d, g_z_packed, g_bias, wd_packed_bwd, agg, mean, rstd, ln_g, dact, gq, gq_packed, \
+                              g_ln_g, g_ln_b, gq_amax, rows, st)
   if (Dm == 128)
-    rc = node_bwd_launch<1>(g_out, h_out, nrows, Dout, d, g_z_packed, g_bias, wd_packed_bwd, agg, mean, rstd, ln_g, dact, gq, gq_packed,
-                            g_ln_g, g_ln_b, gq_amax, st);
+    rc = rows ? NB_LAUNCH(1, true) : NB_LAUNCH(1, false);
   else
-    rc = node_bwd_launch<2>(g_out, h_out, nrows, Dout, d, g_z_packed, g_bias, wd_packed_bwd, agg, mean, rstd, ln_g, dact, gq, gq_packed,
-                            g_ln_g, g_ln_b, gq_amax, st);
+    rc = rows ? NB_LAUNCH(2, true) : NB_LAUNCH(2, false);
+#undef NB_LAUNCH
   BL_LAUNCH_CHECK("bl_node_update_bwd");
   return rc;
 }

@@ -490,7 +490,7 @@ bool parse_datapoint(bl_reader* r, P p, P end, bl_datapoint_t* out) {
 }  // namespace
 
 extern "C" const char* bl_data_last_error(void) { return g_err; }
-extern "C" int32_t bl_data_version(void) { return 4; }  // 3: bl_graph_in_t.adj_feat / bl_collated_t.msg_feat; 4: bl_message_runs
+extern "C" int32_t bl_data_version(void) { return 5; }  // 3: bl_graph_in_t.adj_feat / bl_collated_t.msg_feat; 4: bl_message_runs; 5: bl_live_sets
 
 extern "C" int32_t bl_pyset_order(const int32_t* inserted, int32_t n, int32_t* out) {
   if (n < 0 || (n > 0 && (!inserted || !out))) { set_err("bl_pyset_order: bad arguments"); return -1; }
@@ -794,5 +794,124 @@ extern "C" int32_t bl_message_runs(const int32_t* msg_src, const int32_t* msg_tg
   std::vector<int32_t> next(tgt_run_ptr, tgt_run_ptr + N);
   for (int64_t r = 0; r < R; ++r) tgt_run_rows[next[bwd_rows_tgt[E + r]]++] = (int32_t)(E + r);
   *num_runs = R;
+  return 0;
+}
+
+// ---- live rows of a collated minibatch (buglab/data/collate.py::live_set_arrays) --------------------------------
+// The scoring heads read the encoder's output through one gather of the rows head_idx, so the backward pass of the last layer can
+// only meet a non-zero gradient at those nodes, the layer below at those nodes and the sources of the messages into them, and so
+// on.  Per live layer (the last one first) this writes the index arrays of the reduced backward problem (csrc/bl_mp_layer.hip) into
+// ONE caller-allocated int32 array `arrays` of `capacity` elements, every piece at a multiple of 4 elements, the gaps zeroed; and
+// one row of 15 int32 per layer into `layout` [max_layers, 15]: N', N'', E', R', then the offsets of
+//   nodes [N'], recv [N''], msgs [E'], run_ptr [R' + 1], group_ptr [2 T + 1], rows_tgt [E' + R'], rows_src [E' + R'],
+//   src_ptr [N'' + 1], src_msgs [E'], run_csr_ptr [N'' + 1], run_csr_rows [R'].
+// The descent ends after max_layers layers, or at the first layer with E' > fraction * E (not emitted).  *num_layers, *total say
+// how much was written.  Returns -3 when `capacity` is too small.
+extern "C" int32_t bl_live_sets(const int32_t* msg_src, const int32_t* msg_tgt, const int32_t* type_ptr, int64_t E, int32_t T, int64_t N,
+                                const int32_t* head_idx, int64_t num_head, int32_t max_layers, double fraction, int32_t* arrays,
+                                int64_t capacity, int32_t* layout, int32_t* num_layers, int64_t* total) {
+  if (!type_ptr || !num_layers || !total || T < 1 || N < 0 || E < 0 || num_head < 0 || max_layers < 0 || capacity < 0 ||
+      (E > 0 && (!msg_src || !msg_tgt)) || (num_head > 0 && !head_idx) || (max_layers > 0 && !layout)) {
+    set_err("bl_live_sets: bad argument");
+    return -1;
+  }
+  if (2 * E > 0x7fffffffLL || N > 0x7fffffffLL) { set_err("bl_live_sets: E' + R' may exceed 2^31 rows"); return -1; }
+  if (type_ptr[0] != 0 || type_ptr[T] != E) { set_err("bl_live_sets: type_ptr does not span the messages"); return -1; }
+  for (int32_t t = 0; t < T; ++t)
+    if (type_ptr[t + 1] < type_ptr[t]) { set_err("bl_live_sets: type_ptr not monotone"); return -1; }
+  for (int64_t e = 0; e < E; ++e)
+    if (msg_tgt[e] < 0 || msg_tgt[e] >= N || msg_src[e] < 0 || msg_src[e] >= N) { set_err("bl_live_sets: message %lld: node out of range", (long long)e); return -2; }
+  std::vector<int32_t> pos((size_t)N, -1), rpos((size_t)N, -1), nodes, recv, msgs, starts, next;
+  for (int64_t i = 0; i < num_head; ++i) {
+    if (head_idx[i] < 0 || head_idx[i] >= N) { set_err("bl_live_sets: head row %lld out of range", (long long)i); return -2; }
+    pos[head_idx[i]] = 0;
+  }
+  for (int64_t v = 0; v < N; ++v)
+    if (pos[v] == 0) nodes.push_back((int32_t)v);
+  int64_t off = 0;
+  int32_t layers = 0;
+  while (!nodes.empty() && layers < max_layers) {
+    std::fill(pos.begin(), pos.end(), -1);
+    for (size_t i = 0; i < nodes.size(); ++i) pos[nodes[i]] = (int32_t)i;
+    msgs.clear();
+    for (int64_t e = 0; e < E; ++e)
+      if (pos[msg_tgt[e]] >= 0) msgs.push_back((int32_t)e);
+    const int64_t Ex = (int64_t)msgs.size();
+    if ((double)Ex > fraction * (double)E) break;
+    // runs of the live messages and the type boundaries among them
+    starts.clear();
+    std::vector<int32_t> tp_c((size_t)T + 1, 0), runs_before((size_t)T + 1, 0);
+    {
+      int32_t t = 0;
+      for (int64_t i = 0; i < Ex; ++i) {
+        bool first = i == 0 || msg_tgt[msgs[i]] != msg_tgt[msgs[i - 1]];
+        while (t < T && msgs[i] >= type_ptr[t]) {  // message i is the first live one at or behind the start of type t
+          tp_c[t] = (int32_t)i;
+          runs_before[t] = (int32_t)starts.size();
+          if (msgs[i] < type_ptr[t + 1]) first = true;  // (it is of type t: a type's first message starts a run)
+          ++t;
+        }
+        if (first) starts.push_back((int32_t)i);
+      }
+      for (; t <= T; ++t) { tp_c[t] = (int32_t)Ex; runs_before[t] = (int32_t)starts.size(); }
+      tp_c[T] = (int32_t)Ex;
+      runs_before[T] = (int32_t)starts.size();
+    }
+    const int64_t Rx = (int64_t)starts.size();
+    // recv = nodes + sources of the live messages, ascending
+    std::fill(rpos.begin(), rpos.end(), -1);
+    for (int32_t v : nodes) rpos[v] = 0;
+    for (int64_t i = 0; i < Ex; ++i) rpos[msg_src[msgs[i]]] = 0;
+    recv.clear();
+    for (int64_t v = 0; v < N; ++v)
+      if (rpos[v] == 0) { rpos[v] = (int32_t)recv.size(); recv.push_back((int32_t)v); }
+    const int64_t Nn = (int64_t)nodes.size(), Nr = (int64_t)recv.size();
+    const int64_t sizes[11] = {Nn, Nr, Ex, Rx + 1, 2 * (int64_t)T + 1, Ex + Rx, Ex + Rx, Nr + 1, Ex, Nr + 1, Rx};
+    int64_t need = 0;
+    for (int k = 0; k < 11; ++k) need += (sizes[k] + 3) / 4 * 4;
+    if (!arrays || off + need > capacity) { set_err("bl_live_sets: output array too small"); return -3; }
+    int32_t* row = layout + (size_t)layers * 15;
+    row[0] = (int32_t)Nn; row[1] = (int32_t)Nr; row[2] = (int32_t)Ex; row[3] = (int32_t)Rx;
+    int32_t* piece[11];
+    for (int k = 0; k < 11; ++k) {
+      piece[k] = arrays + off;
+      row[4 + k] = (int32_t)off;
+      const int64_t padded = (sizes[k] + 3) / 4 * 4;
+      for (int64_t i = sizes[k]; i < padded; ++i) piece[k][i] = 0;
+      off += padded;
+    }
+    for (int64_t i = 0; i < Nn; ++i) piece[0][i] = nodes[i];
+    for (int64_t i = 0; i < Nr; ++i) piece[1][i] = recv[i];
+    for (int64_t i = 0; i < Ex; ++i) {
+      piece[2][i] = msgs[i];
+      piece[5][i] = pos[msg_tgt[msgs[i]]];
+      piece[6][i] = msg_src[msgs[i]];
+    }
+    for (int64_t r = 0; r < Rx; ++r) {
+      const int32_t v = msg_tgt[msgs[starts[r]]];
+      piece[3][r] = starts[r];
+      piece[5][Ex + r] = pos[v];
+      piece[6][Ex + r] = v;
+    }
+    piece[3][Rx] = (int32_t)Ex;
+    for (int32_t t = 0; t < T; ++t) { piece[4][t] = tp_c[t]; piece[4][T + t] = (int32_t)(Ex + runs_before[t]); }
+    piece[4][2 * T] = (int32_t)(Ex + Rx);
+    // the two CSRs over the positions in recv (counting sorts: items ascending inside a segment)
+    for (int which = 0; which < 2; ++which) {
+      int32_t* ptr = piece[which == 0 ? 7 : 9];
+      int32_t* items = piece[which == 0 ? 8 : 10];
+      const int64_t n = which == 0 ? Ex : Rx;
+      auto key = [&](int64_t i) { return which == 0 ? rpos[msg_src[msgs[i]]] : rpos[msg_tgt[msgs[starts[i]]]]; };
+      for (int64_t k = 0; k <= Nr; ++k) ptr[k] = 0;
+      for (int64_t i = 0; i < n; ++i) ++ptr[key(i) + 1];
+      for (int64_t k = 0; k < Nr; ++k) ptr[k + 1] += ptr[k];
+      next.assign(ptr, ptr + Nr);
+      for (int64_t i = 0; i < n; ++i) items[next[key(i)]++] = (int32_t)(which == 0 ? i : Ex + i);
+    }
+    ++layers;
+    nodes = recv;
+  }
+  *num_layers = layers;
+  *total = off;
   return 0;
 }
