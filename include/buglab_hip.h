@@ -451,13 +451,14 @@ typedef struct {
   const int32_t* bwd_rows_src;    /* [E + R] = [msg_src ; run target] */
   const int32_t* tgt_run_ptr;     /* [N + 1] CSR node -> the rows of its runs ... */
   const int32_t* tgt_run_rows;    /* [R]     ... E + run id, ascending */
-  /* Optional (backward only): the LIVE ROWS of this layer (the collators make these arrays per minibatch and layer,
+  /* Optional: the LIVE ROWS of this layer (the collators make these arrays per minibatch and layer,
    * buglab/data/collate.py::live_set_arrays).  By handing them in the caller states that g_out is zero outside the rows
    * live_nodes: the heads read the encoder's output through one gather of a few rows, and a layer's input can receive a
    * gradient only at the layer's live nodes and at the sources of the messages into them (live_recv = the layer below's
    * live_nodes).  Backward then runs over the live rows only -- N' nodes, the E' messages and R' runs into them -- and writes
    * the rows live_recv of g_h_lo / g_h_hi, every other row zero.  Taken where the run-row path and bl_node_update_bwd apply
-   * (bl_set_live_backward); every other configuration ignores the arrays.  live_nodes == NULL: none. */
+   * (bl_set_live_backward); every other configuration ignores the arrays.  live_nodes == NULL: none.
+   * FORWARD reads them only with live_fwd set (below); without it they may be filled or not, bl_mp_layer_fwd ignores them. */
   int32_t live_num_nodes;           /* N' */
   int32_t live_num_recv;            /* N'' */
   int32_t live_num_msgs;            /* E' (messages keep their order: type-major, target-sorted inside a type) */
@@ -473,7 +474,18 @@ typedef struct {
   const int32_t* live_src_msgs;     /* [E']      ... as rows 0..E'-1, ascending */
   const int32_t* live_run_csr_ptr;  /* [N'' + 1] CSR position in live_recv -> rows of the live runs into it ... */
   const int32_t* live_run_csr_rows; /* [R']      ... E' + run, ascending */
+  /* Live rows in FORWARD too.  The same reachability run upwards: with the heads' gather as the only reader, the output of this layer
+   * is needed only at the rows live_nodes, and its input only at live_recv.  Non-zero: the caller states (a) that nothing reads h_out
+   * outside the rows live_nodes -- the layer above runs live as well, so it reads its live_recv = this layer's live_nodes -- and
+   * (b) that the input is valid at least on the rows live_recv.  bl_mp_layer_fwd then computes those rows only (each bit-identical to
+   * the full forward's) and leaves the saved state valid on the live rows / live messages only; bl_mp_layer_bwd, handed the same
+   * value, takes the live path or returns BL_EINVAL -- never the full backward over half-valid state.  Set it only after
+   * bl_mp_layer_live_ok(L, ..., forward = 1) said yes.  BL_LIVE_FWD_LAST additionally zero-fills h_out first (the layer whose output
+   * is handed out as the encoder's), BL_LIVE_FWD_INNER leaves the other rows untouched (uninitialised). */
+  int32_t live_fwd;
 } bl_mp_layer_t;
+#define BL_LIVE_FWD_INNER 1
+#define BL_LIVE_FWD_LAST 2
 #define BL_AGG_MAX 0
 #define BL_AGG_SUM 1
 #define BL_AGG_MEAN 2
@@ -566,6 +578,30 @@ int bl_mp_scatter_grad_rows(const float* g_a, int32_t ld_ga, const int32_t* src_
                             int32_t split, float* g_h_lo, int32_t ld_lo, float* g_h_hi, int32_t ld_hi, void* stream);
 int32_t bl_set_live_backward(int32_t on);
 int32_t bl_get_live_backward(void);
+/* The live rows in forward (bl_mp_layer_t.live_fwd):
+ *   bl_mp_layer_live_ok: THE decision whether a layer call runs over its live rows, one host function for both directions (no GPU
+ *     work).  1 when the descriptor carries the live arrays and: live backward on, run rows on and present, f16x3 three-term
+ *     message GEMMs, max aggregation, matrix-core input gradient (have_w_packed_bwd: backward gets / got the packed W^T image, and
+ *     L->Wt does not select the vector path), Din a multiple of 128, dense update on bf16x6 (L->Wd_packed), the one-kernel node
+ *     update backward applies (which excludes the deterministic mode), the dropout counter of a node's own row fits 32 bits, the
+ *     compact gradient + masks fit the backward workspace.  forward != 0 adds: live forward on (bl_set_live_forward), no winner
+ *     table (want_winners == 0), compact pre [E', Dm] + message-position map [E] + target ids [E'] fit the forward workspace
+ *     bl_mp_layer_workspace_bytes(.., 0).  0 otherwise, the reason then in bl_last_error().  The caller asks from the LAST layer
+ *     downwards and sets live_fwd on the longest run of layers from the top that all pass.
+ *   bl_set_live_forward: A/B switch, 1 (default; BL_LIVE_FWD=0 in the environment starts with 0); it applies only where the live
+ *     backward is on.  0: every kernel and launch as without it.  Returns the previous value; bl_get_live_forward the current one.
+ *   bl_pack_f16x2_rows: bl_pack_f16x2 (fixed scale) for the rows rows[0..R-1] of x, each written at its own row of `out`; no other
+ *     row of x is read, none of out written.
+ *   bl_gemm_rows_x6_epi_rows: bl_gemm_rows_x6_epi (one group, bias / tanh / dropout) whose result row i goes to row out_rows[i]
+ *     (< nrows_out) of c with that row's dropout counter (row * N + column): bit-identical to the same rows of the full launch. */
+int32_t bl_mp_layer_live_ok(const bl_mp_layer_t* L, int32_t have_w_packed_bwd, int32_t forward, int32_t want_winners);
+int32_t bl_set_live_forward(int32_t on);
+int32_t bl_get_live_forward(void);
+int bl_pack_f16x2_rows(const float* x, int32_t ld, const int32_t* rows, int32_t R, int32_t D, int32_t D_total, int32_t col_off,
+                       float scale, uint16_t* out, void* stream);
+int bl_gemm_rows_x6_epi_rows(const bl_rows_packed_t* a, const uint16_t* bp, int32_t M, int32_t N, int32_t K, const float* bias,
+                             int32_t act, bl_dropout_t drop, const int32_t* out_rows, int32_t nrows_out, float* c, int32_t ldc,
+                             void* stream);
 
 /* optional per-kernel timing of the launches made inside bl_mp_layer_fwd / _bwd (HIP events on the stream each
  * kernel is launched on); read after a device synchronisation.  bench.py's roofline numbers come from here. */

@@ -165,7 +165,9 @@ class GnnBugLabModule(ModuleWithMetrics):
         # Live rows: when the scoring heads are the only readers of the encoder's output, and read it through the ONE gather below,
         # the gradient of that output is zero outside the gathered rows -- the last layers then run their backward over the rows
         # that gather can reach (the minibatch's live arrays).  The contract is made explicit: in this mode the full output is
-        # handed out DETACHED, so a second consumer gets no gradient rather than a silently truncated one.
+        # handed out DETACHED, so a second consumer gets no gradient rather than a silently truncated one.  Where the library's
+        # predicate allows it (hip_ops.set_live_forward) those layers compute their FORWARD on the same rows only: the detached
+        # output is then exact on the gathered rows and zero on every other row.
         live = (not self._use_all_gnn_layer_outputs and idx_all is not None and idx_all.shape[0] > 0
                 and graph_data.get("live_arrays") is not None and graph_data.get("input_transform") is None
                 and isinstance(self._gnn, GraphNeuralNetwork) and torch.is_grad_enabled() and hip_ops.live_backward())

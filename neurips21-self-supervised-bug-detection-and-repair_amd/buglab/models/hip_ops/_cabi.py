@@ -68,7 +68,7 @@ class bl_mp_layer_t(Structure):
                 ("live_num_nodes", c_int32), ("live_num_recv", c_int32), ("live_num_msgs", c_int32), ("live_num_runs", c_int32),
                 ("live_nodes", c_void_p), ("live_recv", c_void_p), ("live_msgs", c_void_p), ("live_run_ptr", c_void_p),
                 ("live_group_ptr", c_void_p), ("live_rows_tgt", c_void_p), ("live_rows_src", c_void_p), ("live_src_ptr", c_void_p),
-                ("live_src_msgs", c_void_p), ("live_run_csr_ptr", c_void_p), ("live_run_csr_rows", c_void_p)]
+                ("live_src_msgs", c_void_p), ("live_run_csr_ptr", c_void_p), ("live_run_csr_rows", c_void_p), ("live_fwd", c_int32)]
 
 
 class bl_x6_epi_t(Structure):
@@ -137,6 +137,12 @@ _SIGNATURES = {
                                  c_int32, c_void_p, c_int32, c_void_p], ctypes.c_int),
     "bl_set_live_backward": ([c_int32], c_int32),
     "bl_get_live_backward": ([], c_int32),
+    "bl_set_live_forward": ([c_int32], c_int32),
+    "bl_get_live_forward": ([], c_int32),
+    "bl_mp_layer_live_ok": ([c_void_p, c_int32, c_int32, c_int32], c_int32),
+    "bl_pack_f16x2_rows": ([c_void_p, c_int32, c_void_p, c_int32, c_int32, c_int32, c_int32, ctypes.c_float, c_void_p, c_void_p], ctypes.c_int),
+    "bl_gemm_rows_x6_epi_rows": ([c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_int32, bl_dropout_t, c_void_p, c_int32, c_void_p,
+                                  c_int32, c_void_p], ctypes.c_int),
     "bl_winbits_gather": ([c_void_p, c_int32, c_int32, c_void_p, c_int32, c_int32, c_void_p, c_int32, c_void_p], ctypes.c_int),
     "bl_node_update_bwd_rows": ([c_void_p, c_void_p, c_void_p, c_int32, c_int32, bl_dropout_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                  c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p], ctypes.c_int),

@@ -86,3 +86,5 @@ SIDE_STREAM_PRIORITY = int(os.environ.get("BL_SIDE_STREAM_PRIORITY", "0"))
 #   BL_RUN_ROWS   hip_ops.set_run_rows                           target halves of the routed gradients once per run
 #   BL_LIVE_BWD   hip_ops.set_live_backward / live_backward      backward of the last layers over the rows the heads can reach
 #                                                                (gnn.py asks live_backward() before it hands the live arrays on)
+#   BL_LIVE_FWD   hip_ops.set_live_forward / live_forward        forward of those layers over the same rows (only where BL_LIVE_BWD is
+#                                                                on; GraphNeuralNetwork.forward asks the library layer by layer)

@@ -16,7 +16,7 @@ from .gemm import (act_bwd, gemm_rows, gemm_rows_routed, gemm_rows_x6, gemm_wgra
                    layernorm_bwd, pack_bf16x3, pack_weights_x6, scatter_add_rows, segment_max, x6_ok)
 from .weights import _as_groups, _packed_layer_weights, _packed_message_weights, _transposed_layer_weights
 
-__all__ = ["GraphIndex", "MessageRuns", "LiveRows", "live_rows_of", "POOLINGS", "AGGREGATIONS", "_EmbedSubtokenMax", "embed_subtoken_max", "_MpLayer", "node_update_bwd",
+__all__ = ["GraphIndex", "MessageRuns", "LiveRows", "live_rows_of", "live_forward_ok", "LIVE_FWD_INNER", "LIVE_FWD_LAST", "POOLINGS", "AGGREGATIONS", "_EmbedSubtokenMax", "embed_subtoken_max", "_MpLayer", "node_update_bwd",
            "_use_vector_dgrad", "_layer_desc", "_MpLayerFused", "_pending_uses", "set_grad_ready_callback", "_note_use",
            "_notify_backward_launched", "fused_layer_ok", "_GatedMpLayer", "gated_mp_layer", "_MpLayerFeat",
            "mp_layer_with_edge_features", "mp_layer"]
@@ -89,8 +89,12 @@ class GraphIndex(NamedTuple):
     num_hubs: int = -1  # leading entries of node_order that are hubs (-1: unknown, the kernels look at the first 4096)
     runs: Optional[MessageRuns] = None  # None: backward works message by message
     live: Optional[LiveRows] = None  # the live rows of the layer this index is handed to (None: backward over all rows)
+    # forward over the live rows too (bl_mp_layer_t.live_fwd): 0, LIVE_FWD_INNER or LIVE_FWD_LAST.  Set by GraphNeuralNetwork.forward for
+    # the longest run of layers from the top for which live_forward_ok() said yes; a layer handed it runs live or raises.
+    live_fwd: int = 0
 
 
+LIVE_FWD_INNER, LIVE_FWD_LAST = 1, 2  # BL_LIVE_FWD_INNER / _LAST (LAST: the output is zero-filled first, it is handed out)
 POOLINGS = ("max", "sum", "mean")  # BL_POOL_MAX / _SUM / _MEAN
 
 
@@ -291,7 +295,7 @@ def _use_vector_dgrad(lib, E: int, Dm: int, K2: int) -> bool:
     return bool(want) and E > 0 and bool(lib.bl_routed_dgrad_vec_ok(Dm, K2))
 
 
-def _layer_desc(g: "GraphIndex", W, ln_g, ln_b, Wd, bd, Din, msg_act, drop: Dropout, agg: int = 0, backward: bool = False) -> bl_mp_layer_t:
+def _layer_desc(g: "GraphIndex", W, ln_g, ln_b, Wd, bd, Din, msg_act, drop: Dropout, agg: int = 0, live_fwd: int = 0) -> bl_mp_layer_t:
     L = bl_mp_layer_t()
     L.aggregation = int(agg)
     L.N, L.E, L.T, L.Din, L.Dm, L.Dout = g.num_nodes, g.num_messages, W.shape[0], Din, W.shape[2], Wd.shape[1]
@@ -305,13 +309,37 @@ def _layer_desc(g: "GraphIndex", W, ln_g, ln_b, Wd, bd, Din, msg_act, drop: Drop
         L.num_runs = g.runs.num_runs
         for name in MessageRuns._fields:
             setattr(L, name, getattr(g.runs, name).data_ptr())
-    if backward and g.live is not None and g.live.nodes.shape[0] > 0:  # (whether the call takes them is bl_mp_layer_bwd's decision)
+    # (forward reads them only with live_fwd set; whether backward takes them is bl_mp_layer_bwd's decision -- bl_mp_layer_live_ok's)
+    if g.live is not None and g.live.nodes.shape[0] > 0:
         lv = g.live
         L.live_num_nodes, L.live_num_recv = int(lv.nodes.shape[0]), int(lv.recv.shape[0])
         L.live_num_msgs, L.live_num_runs = int(lv.msgs.shape[0]), int(lv.run_ptr.shape[0]) - 1
         for name in LiveRows._fields:
             setattr(L, "live_" + name, getattr(lv, name).data_ptr())
+    L.live_fwd = int(live_fwd)
     return L
+
+
+def live_forward_ok(din: int, lo_width: Optional[int], W, ln_g, ln_b, Wd, bd, g: "GraphIndex", msg_act: str, drop: Dropout,
+                    aggregation: str = "max") -> bool:
+    """Whether mp_layer(...) on these arguments (g.live set; lo_width: the stash's width of a ConcatResidual pair, else None) may run
+    its FORWARD over the live rows: the layer takes the one-call form, a backward pass will follow, no winner table is wanted, and
+    the library's predicate (bl_mp_layer_live_ok, the same one bl_mp_layer_bwd evaluates) says yes.  No GPU work."""
+    if g.live is None or g.live.nodes.shape[0] == 0 or not torch.is_grad_enabled():
+        return False
+    if not (fused_layer_ok(din, W.shape[2]) and (lo_width is None or lo_width % 32 == 0)):
+        return False
+    if not all(p.requires_grad for p in (W, ln_g, ln_b, Wd, bd)):  # (_direct_grad_target and the packed W^T image presuppose it)
+        return False
+    lib = load_library()
+    agg = AGGREGATIONS.index(aggregation)
+    Dm, Dout = W.shape[2], Wd.shape[1]
+    if not (_switches.DENSE_X6 and Dm % 32 == 0 and Dout % 32 == 0):
+        return False
+    use_vec = agg == 0 and _use_vector_dgrad(lib, g.num_messages, Dm, 2 * din)
+    L = _layer_desc(g, W, ln_g, ln_b, Wd, bd, din, _ACTS[msg_act], drop, agg)
+    L.Wd_packed = _packed_layer_weights(Wd, True)[0].data_ptr()  # (cached: the same image forward is about to use)
+    return bool(lib.bl_mp_layer_live_ok(ctypes.byref(L), 0 if use_vec else 1, 1, 1 if _switches.WINNER_SINK is not None else 0))
 
 
 class _MpLayerFused(torch.autograd.Function):
@@ -338,7 +366,9 @@ class _MpLayerFused(torch.autograd.Function):
         wkn, wnk = _packed_message_weights(W, Din, need_bwd and not use_vec)
         wt = _transposed_layer_weights(W) if (need_bwd and use_vec) else None
         dev = h_lo.device
-        L = _layer_desc(g, W, ln_g, ln_b, Wd, bd, Din, msg_act, drop, agg)
+        # (g.live_fwd: decided for the whole run of layers before the first of them ran; the call runs live or fails -- a silent full
+        # forward here would read rows the layer below never computed)
+        L = _layer_desc(g, W, ln_g, ln_b, Wd, bd, Din, msg_act, drop, agg, live_fwd=g.live_fwd)
         dense_x6 = _switches.DENSE_X6 and Dm % 32 == 0 and Dout % 32 == 0
         wd_kn = wd_nk = None
         if dense_x6:
@@ -383,7 +413,7 @@ class _MpLayerFused(torch.autograd.Function):
         direct = [_direct_small(bd), _direct_small(ln_g), _direct_small(ln_b), _direct_grad_target(Wd), _direct_grad_target(W)]
         tgt = [d if d is not None else torch.zeros_like(p) for d, p in zip(direct, (bd, ln_g, ln_b, Wd, W))]
         g_bd, g_lng, g_lnb, g_Wd, g_W = tgt
-        L = _layer_desc(g, W, ln_g, ln_b, Wd, bd, Din, msg_act, drop, agg, backward=True)
+        L = _layer_desc(g, W, ln_g, ln_b, Wd, bd, Din, msg_act, drop, agg, live_fwd=g.live_fwd)  # (forward's decision binds backward)
         if dense_x6:  # (forward kept the LayerNorm output in packed form: backward must take the same path)
             if wd_nk is None:
                 wd_nk = pack_weights_x6(_as_groups(Wd.detach()), False)
@@ -602,6 +632,8 @@ def mp_layer(h, W, ln_g, ln_b, Wd, bd, graph: GraphIndex, msg_act: str = "gelu_a
     if fused_layer_ok(Din, W.shape[2]) and (not pair or h[0].shape[1] % 32 == 0):
         lo, hi = (h[0].contiguous(), h[1].contiguous()) if pair else (h.contiguous(), None)
         return _MpLayerFused.apply(lo, hi, W, ln_g, ln_b, Wd, bd, graph, _ACTS[msg_act], drop, agg)
+    if graph.live_fwd:
+        raise RuntimeError("mp_layer: the graph index asks for the live forward, which only the one-call layer form has")
     if agg != 0:
         raise NotImplementedError("sum / mean message aggregation runs in the one-call layer form only (state and message widths multiples of "
                                   "32, message width <= 512, FUSED_LAYER on)")

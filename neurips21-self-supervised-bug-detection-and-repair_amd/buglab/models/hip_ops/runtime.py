@@ -7,7 +7,8 @@ from . import _switches
 from ._cabi import load_library
 
 __all__ = ["set_deterministic", "_MSG_GEMM_MODES", "set_msg_gemm_mode", "msg_gemm_mode", "set_seq_gemm_mode", "seq_gemm_mode", "set_wgrad_tile",
-           "set_wgrad_kchunk_cap", "set_fused_node_bwd", "set_run_rows", "set_live_backward", "live_backward", "deterministic"]
+           "set_wgrad_kchunk_cap", "set_fused_node_bwd", "set_run_rows", "set_live_backward", "live_backward", "set_live_forward", "live_forward",
+           "deterministic"]
 
 
 def set_deterministic(on: bool = True) -> None:
@@ -85,6 +86,17 @@ def set_live_backward(on: bool) -> bool:
 
 def live_backward() -> bool:
     return bool(load_library().bl_get_live_backward())
+
+
+def set_live_forward(on: bool) -> bool:
+    """A/B switch (BL_LIVE_FWD=0 starts with it off): the last layers run their FORWARD over their live rows too, where the library's
+    one predicate (bl_mp_layer_live_ok) says they can; it applies only where the live backward is on.  Off, every kernel and launch is
+    as without it.  -> previous."""
+    return bool(load_library().bl_set_live_forward(1 if on else 0))
+
+
+def live_forward() -> bool:
+    return bool(load_library().bl_get_live_forward())
 
 
 def deterministic() -> bool:

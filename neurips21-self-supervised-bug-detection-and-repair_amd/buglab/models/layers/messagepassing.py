@@ -201,6 +201,35 @@ class GraphNeuralNetwork(nn.Module):
         self.input_node_state_dim = node_embedder.embedding_size
         self.output_node_state_dim = [l for l in layer_recipe if isinstance(l, nn.Module)][-1].output_state_dimension
 
+    def _live_forward_plan(self, graph: GraphIndex, live, mk) -> Dict[int, int]:
+        """Which layers run their FORWARD over their live rows: {index among the message-passing layers: LIVE_FWD_LAST / _INNER}.
+        Decided here, before the first layer runs, from the last layer downwards: a layer may compute only its live rows if every
+        layer above it reads nothing else, so the run ends at the first layer that cannot -- a layer with edge features, the GGNN
+        layer, the kernel-by-kernel form, or whatever the library's predicate excludes (hip_ops.live_forward_ok)."""
+        if not isinstance(self._recipe[-1], nn.Module):  # (a trailing ConcatResidual would hand out the stash's uncomputed rows)
+            return {}
+        seq, width, stash = [], self.input_node_state_dim, {}  # per message-passing layer: (layer, stash width of a pair or None)
+        for layer in self._recipe:
+            if isinstance(layer, _PassThrough):
+                stash[id(layer.owner)] = width
+            elif isinstance(layer, ConcatResidualLayer):
+                width = (stash.pop(id(layer)), width)
+            else:
+                seq.append((layer, width[0] if isinstance(width, tuple) else None, sum(width) if isinstance(width, tuple) else width))
+                width = layer.output_state_dimension
+        plan: Dict[int, int] = {}
+        for depth in range(min(len(live), len(seq))):
+            li = len(seq) - 1 - depth
+            layer, lo_width, din = seq[li]
+            if not (isinstance(layer, MlpMessagePassingLayer) and layer.features_dimension == 0):
+                break
+            if not hip_ops.live_forward_ok(din, lo_width, layer.W, layer.ln_g, layer.ln_b, layer.Wd, layer.bd, graph._replace(live=live[depth]),
+                                           layer._msg_act(), mk(layer.dropout_rate, 1 + li),
+                                           getattr(layer, "message_aggregation_function", "max")):
+                break
+            plan[li] = hip_ops.LIVE_FWD_LAST if depth == 0 else hip_ops.LIVE_FWD_INNER
+        return plan
+
     @property
     def message_passing_layers(self):
         return list(self.mp)
@@ -215,7 +244,8 @@ class GraphNeuralNetwork(nn.Module):
         re-leafs it there); None, as every other caller leaves it, changes nothing.
         live_backward: the caller's promise that the gradient reaches the returned output only through the rows the minibatch's
         live arrays were made for (head_gather_idx; GnnBugLabModule._compute_gnn_output) -- the last layers then get their live rows
-        and may run their backward over those alone.  Never with return_all_states or an input_transform."""
+        and may run their backward over those alone, and (hip_ops.set_live_forward) their forward too: the returned output is then
+        valid on the rows of the last layer's live nodes and zero elsewhere.  Never with return_all_states or an input_transform."""
         graph = GraphIndex(msg_src, msg_tgt, type_ptr, tgt_ptr, tgt_msgs, src_ptr, src_msgs, int(num_nodes),
                            int(num_messages), int(type_ptr.shape[0]) - 1, node_order, int(num_hub_nodes),
                            MessageRuns.of(run_ptr, bwd_group_ptr, bwd_group_w, bwd_rows_tgt, bwd_rows_src, tgt_run_ptr, tgt_run_rows))
@@ -235,6 +265,7 @@ class GraphNeuralNetwork(nn.Module):
         if live_backward and live_arrays is not None and live_layout is not None and not return_all_states and input_transform is None:
             live = live_rows_of(live_arrays, live_layout, graph.num_types)
         num_mp = sum(1 for l in self._recipe if isinstance(l, nn.Module))
+        live_fwd = self._live_forward_plan(graph, live, mk) if live else {}
         h = h0
         all_states = [h0]
         stash: Dict[int, torch.Tensor] = {}
@@ -250,7 +281,7 @@ class GraphNeuralNetwork(nn.Module):
                 if isinstance(h, tuple) and not isinstance(layer, MlpMessagePassingLayer):
                     h = torch.cat(h, dim=-1)
                 depth = num_mp - 1 - li  # 0: the last layer
-                layer_graph = graph._replace(live=live[depth]) if depth < len(live) else graph
+                layer_graph = graph._replace(live=live[depth], live_fwd=live_fwd.get(li, 0)) if depth < len(live) else graph
                 if isinstance(layer, MlpMessagePassingLayer) and layer.features_dimension > 0:
                     h = layer(h, graph, mk(layer.dropout_rate, 1 + li), edge_features)
                 else:

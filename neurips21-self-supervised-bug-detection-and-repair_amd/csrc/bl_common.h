@@ -23,7 +23,8 @@ unsigned* bl_h3_sat_counter();
 int bl_segment_max_fwd_impl(const float* x, int32_t ldx, const int32_t* seg_ptr, const int32_t* seg_items, int32_t nseg, int32_t D,
                             int32_t act, float* out, int32_t* arg, const float* ln_g, const float* ln_b, float eps, float* ln_out,
                             float* mean, float* rstd, float* dact, uint32_t* winbits, const int32_t* seg_order,
-                            uint16_t* ln_out_packed, int32_t num_hub_slots, void* stream);
+                            uint16_t* ln_out_packed, int32_t num_hub_slots, void* stream,
+                            const int32_t* item_row = nullptr, int32_t x_rows = 0);  // item_row: x is compact [x_rows, ldx], item e's row is item_row[e]
 int bl_segment_sum_fwd_impl(const float* x, int32_t ldx, const int32_t* seg_ptr, const int32_t* seg_items, int32_t nseg, int32_t D,
                             int32_t act, int32_t mean_agg, float* out, const float* ln_g, const float* ln_b, float eps, float* ln_out,
                             float* mean, float* rstd, float* dact, const int32_t* seg_order, uint16_t* ln_out_packed, void* stream);

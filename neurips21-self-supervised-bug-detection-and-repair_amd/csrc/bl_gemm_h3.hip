@@ -40,14 +40,17 @@
 // ---- packing ------------------------------------------------------------------------------------
 // rows: out[r][plane][kg][j] = plane(x[r, 8 kg + j] * scale), planes back to back (row = 2 D halves)
 // (kg_total, kg_off) as in pack_rows_kernel: a ConcatResidual pair is packed without a concatenated copy
+// LIST (bl_pack_f16x2_rows): the R rows rows[0..R-1] of x, each written at its own row of the whole-layout `out`; no other row of
+// either is touched (the live forward of a layer: the rows outside the list were never computed)
+template <bool LIST>
 __global__ __launch_bounds__(256) void pack_rows_h_kernel(const float* __restrict__ x, int ld, long long R, int D, uint4* __restrict__ out,
                                                           int kg_total, int kg_off, float scale, const float* __restrict__ amax_dev,
-                                                          unsigned* __restrict__ sat_counter) {
+                                                          unsigned* __restrict__ sat_counter, const int* __restrict__ rows) {
   const int kgs = D >> 3;
   const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= R * kgs) return;
   if (amax_dev) scale *= h3_scale_from_amax(*amax_dev);
-  const long long r = t / kgs;
+  const long long r = LIST ? (long long)rows[t / kgs] : t / kgs;
   const int kgn = kg_total;
   const int kg = (int)(t % kgs) + kg_off;
   x -= 8 * kg_off;
@@ -153,9 +156,25 @@ extern "C" int bl_pack_f16x2(const float* x, int32_t ld, int64_t R, int32_t D, i
                "bl_pack_f16x2: widths / offset must be multiples of 8 with col_off + D <= D_total");
   BL_CHECK_ARG(scale > 0.f, "bl_pack_f16x2: scale must be positive (a power of two)");
   const long long total = (long long)R * (D / 8);
-  hipLaunchKernelGGL(pack_rows_h_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, ld, (long long)R, D,
-                     reinterpret_cast<uint4*>(out), D_total / 8, col_off / 8, scale, amax_dev, bl_h3_sat_counter());
+  hipLaunchKernelGGL(pack_rows_h_kernel<false>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, ld, (long long)R, D,
+                     reinterpret_cast<uint4*>(out), D_total / 8, col_off / 8, scale, amax_dev, bl_h3_sat_counter(), nullptr);
   BL_LAUNCH_CHECK("bl_pack_f16x2");
+  return BL_OK;
+}
+
+// bl_pack_f16x2 for the rows rows[0..R-1] (ids below nrows) of x [nrows, ld] and of out [nrows, 2 D_total]: every other row of
+// both stays untouched and unread
+extern "C" int bl_pack_f16x2_rows(const float* x, int32_t ld, const int32_t* rows, int32_t R, int32_t D, int32_t D_total, int32_t col_off,
+                                  float scale, uint16_t* out, void* stream) {
+  if (R == 0) return BL_OK;
+  BL_CHECK_ARG(x && out && rows && R > 0 && bl_aligned16(x) && bl_aligned16(out), "bl_pack_f16x2_rows: null or misaligned pointer");
+  BL_CHECK_ARG(D > 0 && D % 8 == 0 && ld % 4 == 0 && D_total % 8 == 0 && col_off % 8 == 0 && col_off >= 0 && col_off + D <= D_total,
+               "bl_pack_f16x2_rows: widths / offset must be multiples of 8 with col_off + D <= D_total");
+  BL_CHECK_ARG(scale > 0.f, "bl_pack_f16x2_rows: scale must be positive (a power of two)");
+  const long long total = (long long)R * (D / 8);
+  hipLaunchKernelGGL(pack_rows_h_kernel<true>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, ld, (long long)R, D,
+                     reinterpret_cast<uint4*>(out), D_total / 8, col_off / 8, scale, nullptr, bl_h3_sat_counter(), rows);
+  BL_LAUNCH_CHECK("bl_pack_f16x2_rows");
   return BL_OK;
 }
 

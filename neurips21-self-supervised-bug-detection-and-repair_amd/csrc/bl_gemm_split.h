@@ -88,13 +88,16 @@ struct X6Epi {
   float mask_scale;
   float* colsum;           // MASK: [N] += column sums of c (the bias gradient)
   uint2* c_packed;         // PACK / MASK: the result in bl_pack_bf16x3's form [M][3 N] instead of fp32
+  const int* out_rows;     // ROWS: result row i is stored at row out_rows[i] of c, and its dropout counter is that row's
 };
 
 // C[rows of g] = rows(a) . B_g, rows gathered from <= 3 packed sources; MASKED: the routed (winner-masked) left operand, one
 // source, of the input-gradient GEMM.  128 x 128 tile, 4 waves 2 x 2, 32 k's per LDS stage with a register prefetch.
 // EPI: -1 = no epilogue, else the epilogue family of the unscaled split: 0..15 = activation code (bias / activation / dropout,
 // fp32 result); 16 + code = the same, result PACKED only; 32 = + residual (fp32 result); 64 = masked by the packed forward output,
-// column sums, result packed only.  (The activation is a template parameter: with a run-time switch the compiler evaluates every
+// column sums, result packed only; 128 + code = ROWS, the 0..15 form whose result row i goes to row epi.out_rows[i] of c with that
+// row's dropout counter (the dense update of a layer's live nodes: a kept row is bit-identical to the full launch's).
+// (The activation is a template parameter: with a run-time switch the compiler evaluates every
 // activation's libm call for every element -- measured 0.12 vs 0.05 ms on the c2 dense shape.)
 // A SCALED split multiplies the result by out_scale = 1 / (s_a s_b) (host part), divided by h3_scale_from_amax(*a_amax_dev) when
 // the left operand's scale lives in device memory.
@@ -110,7 +113,8 @@ __device__ __forceinline__ void gemm_rows_body(
     long long strideB, const int* __restrict__ group_ptr, const int* __restrict__ group_w, int G, int M, int N, int K,
     float* __restrict__ c, int ldc, int xcd_remap, X6Epi epi, float out_scale, const float* __restrict__ a_amax_dev) {
   static_assert(EPI == -1 || !S::SCALED, "the epilogues are built for the unscaled split only");
-  constexpr bool E_ACT = EPI >= 0 && EPI < 32, E_PACK = EPI >= 16 && (EPI < 32 || EPI == 64), E_RES = EPI == 32, E_MASK = EPI == 64;
+  constexpr bool E_ROWS = EPI >= 128 && EPI < 144;
+  constexpr bool E_ACT = (EPI >= 0 && EPI < 32) || E_ROWS, E_PACK = EPI >= 16 && (EPI < 32 || EPI == 64), E_RES = EPI == 32, E_MASK = EPI == 64;
   constexpr int ACT = EPI >= 0 ? (EPI & 15) : 0;
   constexpr bool SWZ = S::swizzled(MASKED);
   constexpr int NP = ONE ? 1 : S::NP;    // planes loaded, staged and multiplied
@@ -253,6 +257,8 @@ __device__ __forceinline__ void gemm_rows_body(
 #pragma unroll
   for (int ti = 0; ti < 2; ++ti) {
     const int m = wm * 64 + ti * 32 + li;
+    // (ROWS: the row whose dropout counter this result row takes; rows past the tile's last are computed and dropped as ever)
+    const uint32_t drow = E_ROWS ? (uint32_t)epi.out_rows[row0 + min(m, nrows - 1)] : (uint32_t)(row0 + m);
 #pragma unroll
     for (int tj = 0; tj < 2; ++tj)
 #pragma unroll
@@ -271,7 +277,7 @@ __device__ __forceinline__ void gemm_rows_body(
           for (int u = 0; u < 4; ++u) {
             v[u] = bl_act(ACT, v[u]);
             if (epi.drop_thresh) {  // same counter as the fp32 row GEMM: element index row * N + column
-              const uint32_t idx = (uint32_t)(row0 + m) * (uint32_t)N + (uint32_t)(n + u);
+              const uint32_t idx = drow * (uint32_t)N + (uint32_t)(n + u);
               v[u] = ((bl_lowbias32(idx + epi.drop_key) >> 8) >= epi.drop_thresh) ? v[u] * epi.drop_scale : 0.f;
             }
           }
@@ -286,7 +292,7 @@ __device__ __forceinline__ void gemm_rows_body(
       const int mm = wm * 64 + ti * 32 + r;
       float4 v = *reinterpret_cast<const float4*>(stage + r * 68 + 4 * c4);
       if (mm < nrows && n < N) {
-        const size_t grow = (size_t)(row0 + mm);
+        const size_t grow = E_ROWS ? (size_t)epi.out_rows[row0 + mm] : (size_t)(row0 + mm);
         if (E_RES) {
           const float4 rv = *reinterpret_cast<const float4*>(epi.res + grow * epi.ld_res + n);
           v.x += rv.x; v.y += rv.y; v.z += rv.z; v.w += rv.w;

@@ -527,7 +527,13 @@ int gemm_rows_x6_impl(const char* who, const bl_rows_packed_t* a, const uint32_t
     X6_LAUNCH(false, 32)
   else if (epi && e.form == BL_X6_EPI_MASK_PACK)
     X6_LAUNCH(false, 64)
-  else if (epi && e.form != BL_X6_EPI_ACT) {
+  else if (epi && e.out_rows) {  // (bl_gemm_rows_x6_epi_rows: the node update's tanh only)
+    if (e.form != BL_X6_EPI_ACT || e.act != BL_ACT_TANH) {
+      bl_set_error("%s: the row-list epilogue is built for bias / tanh / dropout only (got form %d, activation %d)", who, e.form, e.act);
+      return BL_EINVAL;
+    }
+    X6_LAUNCH(false, 128 + BL_ACT_TANH)
+  } else if (epi && e.form != BL_X6_EPI_ACT) {
     bl_set_error("%s: epilogue form %d with activation %d is not built (packed result: relu only)", who, e.form, e.act);
     return BL_EINVAL;
   } else if (epi == nullptr)
@@ -637,6 +643,19 @@ extern "C" int bl_gemm_rows_x6_epi(const bl_rows_packed_t* a, const uint16_t* bp
   const bl_drop_dev d = bl_make_drop(drop);
   X6Epi e = {bias, act, d.key, d.thresh, d.scale, 0, nullptr, 0, nullptr, 1.f, nullptr, nullptr};
   return gemm_rows_x6_impl("bl_gemm_rows_x6_epi", a, nullptr, 0, bp, b_group_stride, group_ptr, group_w, G, M, N, K, &e, c, ldc, stream);
+}
+
+// bl_gemm_rows_x6_epi (one group, tanh) whose result row i is stored at row out_rows[i] (< nrows_out) of c, with the dropout counter
+// of THAT row (row * N + column): what it stores is bit-identical to the same rows of the launch over all nrows_out rows.
+extern "C" int bl_gemm_rows_x6_epi_rows(const bl_rows_packed_t* a, const uint16_t* bp, int32_t M, int32_t N, int32_t K, const float* bias,
+                                        int32_t act, bl_dropout_t drop, const int32_t* out_rows, int32_t nrows_out, float* c, int32_t ldc,
+                                        void* stream) {
+  BL_CHECK_ARG(out_rows && nrows_out >= M, "bl_gemm_rows_x6_epi_rows: out_rows missing or fewer output rows than result rows");
+  BL_CHECK_ARG((uint64_t)nrows_out * (uint64_t)N < (1ull << 32) || drop.p <= 0.f, "bl_gemm_rows_x6_epi_rows: dropout index space is 32 bit");
+  BL_CHECK_ARG(bias == nullptr || bl_aligned16(bias), "bl_gemm_rows_x6_epi_rows: misaligned bias");
+  const bl_drop_dev d = bl_make_drop(drop);
+  X6Epi e = {bias, act, d.key, d.thresh, d.scale, 0, nullptr, 0, nullptr, 1.f, nullptr, nullptr, out_rows};
+  return gemm_rows_x6_impl("bl_gemm_rows_x6_epi_rows", a, nullptr, 0, bp, 0, nullptr, nullptr, 1, M, N, K, &e, c, ldc, stream);
 }
 
 extern "C" int bl_gemm_rows_x6_epi2(const bl_rows_packed_t* a, const uint16_t* bp, int32_t M, int32_t N, int32_t K, const bl_x6_epi_t* epi,

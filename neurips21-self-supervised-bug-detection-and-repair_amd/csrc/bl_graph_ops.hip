@@ -209,14 +209,18 @@ __global__ __launch_bounds__(256) void embed_bwd_sorted_kernel(const float* __re
 #define SEGMAX_HUB_SLOTS 4096  // hub_slots unknown to the caller: the first so many slots of seg_order are looked at
 
 // extremes of the items [beg, end) of one segment: best = largest (activated, unless GELU2) value and its item, low = smallest raw value
-template <int NV, bool GELU2>
+// MAP: the row of item e is x + item_row[e] * ldx (a compact x that holds the rows of the listed items only; the winners stay item ids)
+template <int NV, bool GELU2, bool MAP = false>
 __device__ __forceinline__ void segmax_scan(const float* __restrict__ x, int ldx, const int* __restrict__ seg_items, int beg, int end, int D,
-                                            int act, float (&best)[NV], int (&barg)[NV], float (&low)[NV], int (&larg)[NV]) {
+                                            int act, float (&best)[NV], int (&barg)[NV], float (&low)[NV], int (&larg)[NV],
+                                            const int* __restrict__ item_row = nullptr, int x_rows = 0) {
   constexpr int U = NV <= 4 ? 8 : 4;  // rows in flight per step
   const int lane = threadIdx.x & 63;
   for (int base = beg; base < end; base += 64) {
     const int cnt = min(64, end - base);
     const int mine = lane < cnt ? (seg_items ? seg_items[base + lane] : base + lane) : 0;
+    // (clamped: an item the map was not made for must not turn into a read outside x)
+    const int mine_row = (MAP && lane < cnt) ? min(max(item_row[mine], 0), max(x_rows - 1, 0)) : 0;
     // U rows in flight per step (independent loads; a short last step re-reads the last row and ignores it, so that a
     // segment of up to U items is ONE round trip), compared in item order (ties -> first item)
     for (int i = 0; i < cnt; i += U) {
@@ -225,7 +229,7 @@ __device__ __forceinline__ void segmax_scan(const float* __restrict__ x, int ldx
 #pragma unroll
       for (int u = 0; u < U; ++u) {
         e[u] = __shfl(mine, min(i + u, cnt - 1), 64);
-        const float* __restrict__ row = x + (size_t)e[u] * ldx;
+        const float* __restrict__ row = x + (size_t)(MAP ? __shfl(mine_row, min(i + u, cnt - 1), 64) : e[u]) * ldx;
 #pragma unroll
         for (int j = 0; j < NV; ++j) {
           const int d = lane + 64 * j;
@@ -467,6 +471,28 @@ __global__ __launch_bounds__(256) void segment_max_kernel(SEGMAX_PARAMS) {
   }
   segmax_finish<NV, HAS_LN, GELU2>(x, ldx, seg, D, act, best, barg, raw, werf, out, arg, ln_g, ln_b, eps, ln_out, mean_out, rstd_out, dact,
                                    ln_out_packed);
+}
+
+// The live-row form of the layer's forward (bl_mp_layer_fwd, bl_mp_layer_t.live_fwd): the segments seg_order[0..nseg-1] only (node ids;
+// no hubs, one wave per segment), their items read from a COMPACT x through item_row (segmax_scan<MAP>: x holds the rows of the live
+// messages).  Everything is written where segment_max_kernel writes it -- winbits at row = item id, the per-node outputs at row = node
+// id -- so that backward reads the saved state unchanged.  A kernel of its own: the instantiations above keep their registers.
+template <int NV, bool GELU2>
+__global__ __launch_bounds__(256) void segment_max_rows_kernel(SEGMAX_PARAMS, const int* __restrict__ item_row, int x_rows) {
+  const int slot = (int)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (slot >= nseg) return;
+  const int seg = seg_order[slot];
+  const int beg = seg_ptr[seg], end = seg_ptr[seg + 1];
+  float best[NV], low[NV], raw[NV], werf[NV];
+  int barg[NV], larg[NV];
+#pragma unroll
+  for (int j = 0; j < NV; ++j) { best[j] = NEG_INF; barg[j] = -1; low[j] = -NEG_INF; larg[j] = -1; raw[j] = 0.f; werf[j] = 0.f; }
+  segmax_scan<NV, GELU2, true>(x, ldx, seg_items, beg, end, D, act, best, barg, low, larg, item_row, x_rows);
+  segmax_pick<NV, GELU2>(best, barg, low, larg, raw, werf);
+  if (winbits) segmax_winbits<NV>(seg_items, beg, end, D, barg, winbits);
+  // (x is passed on for the per-message GELU of the non-GELU2 form only, which the GELU2 dispatch below never takes)
+  segmax_finish<NV, true, GELU2>(x, ldx, seg, D, act, best, barg, raw, werf, out, arg, ln_g, ln_b, eps, ln_out, mean_out, rstd_out, dact,
+                                 ln_out_packed);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1000,7 +1026,7 @@ extern "C" int bl_segment_max_fwd(const float* x, int32_t ldx, const int32_t* se
 int bl_segment_max_fwd_impl(const float* x, int32_t ldx, const int32_t* seg_ptr, const int32_t* seg_items, int32_t nseg, int32_t D,
                             int32_t act, float* out, int32_t* arg, const float* ln_g, const float* ln_b, float eps, float* ln_out,
                             float* mean, float* rstd, float* dact, uint32_t* winbits, const int32_t* seg_order,
-                            uint16_t* ln_out_packed, int32_t num_hub_slots, void* stream) {
+                            uint16_t* ln_out_packed, int32_t num_hub_slots, void* stream, const int32_t* item_row, int32_t x_rows) {
   if (nseg == 0) return BL_OK;
   // arg (the winner table) is optional; so are out / mean / rstd when only the LayerNorm output is wanted (forward-only calls)
   BL_CHECK_ARG(seg_ptr && (out || ln_g), "bl_segment_max_fwd: null pointer");
@@ -1012,6 +1038,20 @@ int bl_segment_max_fwd_impl(const float* x, int32_t ldx, const int32_t* seg_ptr,
   BL_CHECK_ARG(ln_out_packed == nullptr || (has_ln && D % 8 == 0), "bl_segment_max_fwd: the packed LayerNorm output needs D %% 8 == 0");
   hipStream_t st = (hipStream_t)stream;
   uint32_t* lnp = reinterpret_cast<uint32_t*>(ln_out_packed);
+  if (item_row) {  // the live-row form: listed segments, compact x
+    BL_CHECK_ARG(has_ln && seg_order && seg_items && arg == nullptr && x_rows >= 0, "bl_segment_max_fwd: the row-mapped form needs LayerNorm, seg_order and seg_items, and writes no winner table");
+    dim3 grid((nseg + 3) / 4), block(256);
+    DISPATCH_NV(D, {
+      if (act == BL_ACT_GELU)
+        hipLaunchKernelGGL((segment_max_rows_kernel<NV, true>), grid, block, 0, st, x, ldx, seg_ptr, seg_items, nseg, D, act, out, arg, ln_g,
+                           ln_b, eps, ln_out, mean, rstd, dact, winbits, seg_order, lnp, 0, item_row, x_rows);
+      else
+        hipLaunchKernelGGL((segment_max_rows_kernel<NV, false>), grid, block, 0, st, x, ldx, seg_ptr, seg_items, nseg, D, act, out, arg, ln_g,
+                           ln_b, eps, ln_out, mean, rstd, dact, winbits, seg_order, lnp, 0, item_row, x_rows);
+    })
+    BL_LAUNCH_CHECK("bl_segment_max_fwd");
+    return BL_OK;
+  }
   // hub candidates: the first hub_slots entries of seg_order (the collator sorts high-degree nodes to the front) get a
   // workgroup each at the front of the grid, so that the longest segments start at t = 0
   const int hub_slots = seg_order ? (num_hub_slots < 0 ? min(nseg, SEGMAX_HUB_SLOTS) : min(nseg, num_hub_slots)) : 0;

@@ -14,6 +14,10 @@
 //             target halves per run) -> segmented sums over the source CSR and the run CSR.  With the live arrays of the minibatch
 //             (bl_mp_layer_t.live_nodes: the rows of g_out that can be non-zero at all) the same chain over the live rows only:
 //             N' nodes, E' + R' GEMM rows, a compact copy of their routing masks, sums into a zero-filled [N, Din]
+//   forward, live form (bl_mp_layer_t.live_fwd; the decision is live_ok() below, made once per layer before forward and enforced
+//             again at backward): the same chain over the rows the heads can reach -- pack the rows live_recv -> message GEMM over the
+//             E' live messages into a compact `pre` -> segmented max + LayerNorm of the N' live nodes -> dense update of those rows.
+//             Saved state and h_out are valid on the live rows only; backward of such a layer must take the live path
 //   forward-only (saved == NULL): the same forward without any store that only a backward pass reads
 // The caller owns every buffer: `saved` lives from forward to backward, `ws` only during the call
 // (sizes from bl_mp_layer_saved_bytes / bl_mp_layer_workspace_bytes); nothing is allocated here except three
@@ -45,11 +49,15 @@ const char* kProfNames[] = {"pack_rows",      "msg_gemm_x6",  "segment_max_ln", 
                             // the run rows of bl_mp_layer_bwd: OR of the routing masks per run (bl_winbits_or_runs)
                             "winbits_or_runs",
                             // the live rows of bl_mp_layer_bwd: compact copy of the live messages' routing masks (bl_winbits_gather)
-                            "winbits_gather_live"};
+                            "winbits_gather_live",
+                            // the live rows of bl_mp_layer_fwd: message -> row of the compact pre-activations, target ids of the live messages
+                            "live_index_fwd"};
 constexpr int kProfWinbitsOrRuns = 26;
 constexpr int kProfWinbitsGatherLive = 27;
+constexpr int kProfLiveIndexFwd = 28;
 constexpr int kProfKinds = sizeof(kProfNames) / sizeof(kProfNames[0]);
-static_assert(kProfWinbitsGatherLive == kProfKinds - 1 && kProfWinbitsOrRuns == kProfKinds - 2, "the kProf constants must index their names");
+static_assert(kProfLiveIndexFwd == kProfKinds - 1 && kProfWinbitsGatherLive == kProfKinds - 2 && kProfWinbitsOrRuns == kProfKinds - 3,
+              "the kProf constants must index their names");
 
 hipEvent_t prof_event() {
   if (!g_prof_pool.empty()) {
@@ -256,6 +264,78 @@ inline int layer_runs(const bl_mp_layer_t* L) {
           L->tgt_run_rows) ? L->num_runs : 0;
 }
 
+// bl_set_live_forward / BL_LIVE_FWD: forward of the last layers over their live rows too (only where the live backward is on)
+int g_live_fwd = -1;
+bool live_fwd_on() {
+  if (g_live_fwd < 0) {
+    const char* e = getenv("BL_LIVE_FWD");
+    g_live_fwd = (e && e[0] == '0') ? 0 : 1;
+  }
+  return g_live_fwd != 0;
+}
+
+// bytes of the live forward's scratch: compact pre [E', Dm] | msg_pos [E] (only the E' live entries are written and read) | tgt_id [E']
+struct WsLiveFwd {
+  float* pre;
+  int32_t* msg_pos;
+  int32_t* tgt_id;
+  size_t bytes;
+};
+WsLiveFwd carve_live_fwd(void* base, int E, int Ex, int Dm) {
+  WsLiveFwd w;
+  char* p = (char*)base;
+  size_t o = 0;
+  auto take = [&](size_t b) { char* q = p ? p + o : nullptr; o += al(b); return q; };
+  w.pre = (float*)take((size_t)Ex * Dm * 4);
+  w.msg_pos = (int32_t*)take((size_t)E * 4);
+  w.tgt_id = (int32_t*)take((size_t)Ex * 4);
+  w.bytes = o;
+  return w;
+}
+
+// THE decision whether a layer runs over its live rows (bl_mp_layer_live_ok): asked before forward for the live forward, evaluated
+// again by bl_mp_layer_bwd.  A layer whose forward ran live has valid saved state on its live rows only, so whatever is false here
+// at backward after a live forward is an error there, never a fall-back.
+//   have_w_bwd: the packed C = G . W^T image of the message weights will be / is handed to backward (not the Wt path)
+//   forward:    also what the live FORWARD needs: its switch, no winner table, its scratch inside the forward workspace
+bool live_ok(const bl_mp_layer_t* L, bool have_w_bwd, bool forward, bool want_winners, const char** why) {
+  const char* dummy;
+  if (!why) why = &dummy;
+  const int N = L->N, E = L->E, Din = L->Din, Dm = L->Dm, Dout = L->Dout;
+#define LIVE_NEEDS(cond_, text_) \
+  if (!(cond_)) { *why = text_; return false; }
+  LIVE_NEEDS(live_bwd_on(), "the live backward is switched off (bl_set_live_backward / BL_LIVE_BWD)");
+  LIVE_NEEDS(layer_has_live(L), "the descriptor carries no (complete) live arrays");
+  LIVE_NEEDS(layer_runs(L) > 0 && E > 0 && run_rows_on(), "the run rows are off or the minibatch carries no run arrays");
+  LIVE_NEEDS(msg_h3() && g_msg_h3 == 1, "the message GEMMs are not in the f16x3 three-term mode");
+  LIVE_NEEDS(L->aggregation == BL_AGG_MAX, "the aggregation is not max");
+  LIVE_NEEDS(have_w_bwd && !(L->Wt != nullptr && bl_routed_dgrad_vec_ok(Dm, 2 * Din)), "the input gradient takes the vector-unit (Wt) path");
+  LIVE_NEEDS(Din % 128 == 0, "Din is not a multiple of 128");
+  LIVE_NEEDS(L->Wd_packed != nullptr && Dm % 32 == 0 && Dout % 32 == 0, "the dense node update is not on the bf16x6 path");
+  LIVE_NEEDS(g_fused_node_bwd && bl_node_update_bwd_ok(Dm, Dout), "the one-kernel node update backward does not apply (shape, switch or deterministic mode)");
+  LIVE_NEEDS((uint64_t)N * (uint64_t)Dout < (1ull << 32) || L->drop.p <= 0.f, "the dropout counter of a node's own row leaves 32 bits");
+  const size_t Ex = (size_t)L->live_num_msgs, Rx = (size_t)L->live_num_runs;
+  LIVE_NEEDS(al((Ex + Rx) * Din * 4) + (Ex + Rx) * (Dm / 32) * 4 <= (size_t)E * 2 * Din * 4, "the compact gradient and masks do not fit the backward workspace");
+  if (forward) {
+    LIVE_NEEDS(live_fwd_on(), "the live forward is switched off (bl_set_live_forward / BL_LIVE_FWD)");
+    LIVE_NEEDS(!want_winners, "a winner table is wanted");
+    LIVE_NEEDS(carve_live_fwd(nullptr, E, (int)Ex, Dm).bytes <= al((size_t)E * Dm * 4), "the compact pre-activations and index arrays do not fit the forward workspace");
+  }
+#undef LIVE_NEEDS
+  return true;
+}
+
+// msg_pos[live_msgs[i]] = i (row of message live_msgs[i] in the compact pre-activations), tgt_id[i] = msg_tgt[live_msgs[i]]
+__global__ __launch_bounds__(256) void live_index_kernel(const int* __restrict__ live_msgs, const int* __restrict__ msg_tgt, int Ex, int E,
+                                                         int* __restrict__ msg_pos, int* __restrict__ tgt_id) {
+  const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  if (i >= Ex) return;
+  const int e = live_msgs[i];
+  if ((unsigned)e >= (unsigned)E) return;  // (a malformed list must not write outside the region)
+  msg_pos[e] = i;
+  tgt_id[i] = msg_tgt[e];
+}
+
 // fork / join events of the side stream, one set per device (a process that drives several GPUs -- tests, tools -- must not
 // record an event created on another device)
 constexpr int kMaxDevices = 16;
@@ -316,6 +396,22 @@ extern "C" int32_t bl_set_live_backward(int32_t on) {
 }
 
 extern "C" int32_t bl_get_live_backward(void) { return live_bwd_on() ? 1 : 0; }
+
+extern "C" int32_t bl_set_live_forward(int32_t on) {
+  const int32_t prev = live_fwd_on() ? 1 : 0;
+  g_live_fwd = on != 0 ? 1 : 0;
+  return prev;
+}
+
+extern "C" int32_t bl_get_live_forward(void) { return live_fwd_on() ? 1 : 0; }
+
+extern "C" int32_t bl_mp_layer_live_ok(const bl_mp_layer_t* L, int32_t have_w_packed_bwd, int32_t forward, int32_t want_winners) {
+  if (L == nullptr || check_layer(L, "bl_mp_layer_live_ok") != BL_OK) return 0;
+  const char* why = nullptr;
+  const bool ok = live_ok(L, have_w_packed_bwd != 0, forward != 0, want_winners != 0, &why);
+  if (!ok) bl_set_error("bl_mp_layer_live_ok: %s", why);  // (a reason to read, not a failure: the caller runs the full form)
+  return ok ? 1 : 0;
+}
 
 extern "C" int64_t bl_mp_layer_saved_bytes(int32_t N, int32_t E, int32_t Din, int32_t Dm, int32_t msg_act) {
   return (int64_t)carve_saved(nullptr, N, E, Din, Dm, msg_act).bytes;
@@ -383,6 +479,57 @@ extern "C" int bl_mp_layer_fwd(const bl_mp_layer_t* L, const float* h_lo, int32_
     S.dact = nullptr; S.bits = nullptr; S.agg = nullptr; S.mean = nullptr; S.rstd = nullptr;
   }
   const bool h3 = msg_h3();
+  if (L->live_fwd) {
+    // Live rows, forward: the caller (GraphNeuralNetwork.forward, after bl_mp_layer_live_ok) states that nothing reads h_out outside
+    // the rows live_nodes -- the layer above, live as well, reads its live_recv = these live_nodes, the heads gather a subset of the
+    // last layer's -- and that the input is valid at least on the rows live_recv.  Every buffer keeps its whole-problem layout
+    // (saved state by node / message id, h_out by node id), so bl_mp_layer_bwd's live path reads it unchanged; only `pre` is compact.
+    const char* why = nullptr;
+    if (infer || !live_ok(L, true, true, winner_out != nullptr, &why)) {
+      bl_set_error("bl_mp_layer_fwd: live_fwd is set but the layer cannot run over its live rows: %s", infer ? "forward-only call (saved == NULL)" : why);
+      return BL_EINVAL;
+    }
+    const int Nx = L->live_num_nodes, Nr = L->live_num_recv, Ex = L->live_num_msgs;
+    const WsLiveFwd V = carve_live_fwd(ws, E, Ex, Dm);
+    if (L->live_fwd == BL_LIVE_FWD_LAST &&  // the output handed out as the encoder's: no caller ever sees a row nobody computed
+        hipMemsetAsync(h_out, 0, (size_t)N * Dout * 4, st) != hipSuccess) {
+      bl_set_error("bl_mp_layer_fwd: memset failed");
+      return BL_EINVAL;
+    }
+    if (Ex > 0) {
+      ProfScope ps(kProfLiveIndexFwd, 0.0, st, false);
+      hipLaunchKernelGGL(live_index_kernel, dim3((unsigned)((Ex + 255) / 256)), dim3(256), 0, st, L->live_msgs, L->msg_tgt, Ex, E, V.msg_pos, V.tgt_id);
+      BL_LAUNCH_CHECK("bl_mp_layer_fwd (live index)");
+    }
+    {  // rows outside the previous layer's live set were never computed: only the rows live_recv are read and packed
+      ProfScope ps(0, 0.0, st, false);
+      BL_TRY(bl_pack_f16x2_rows(h_lo, ld_lo, L->live_recv, Nr, h_hi ? width_lo : Din, Din, 0, BL_H3_ROW_SCALE, S.hp, st));
+      if (h_hi) BL_TRY(bl_pack_f16x2_rows(h_hi, ld_hi, L->live_recv, Nr, Din - width_lo, Din, width_lo, BL_H3_ROW_SCALE, S.hp, st));
+    }
+    if (Ex > 0) {  // the live messages keep their order (type-major): the first T + 1 entries of live_group_ptr are their type ranges
+      bl_rows_packed_t a;
+      a.xp[0] = S.hp; a.xp[1] = S.hp; a.xp[2] = nullptr;
+      a.idx[0] = L->live_rows_src; a.idx[1] = V.tgt_id; a.idx[2] = nullptr;
+      a.width[0] = Din; a.width[1] = Din; a.width[2] = 0;
+      a.nsrc = 2;
+      ProfScope ps(13, 2.0 * Ex * (2.0 * Din) * Dm, st, false);
+      BL_TRY(bl_gemm_rows_h3(&a, nullptr, 0, w_packed, bl_packed_weight_elems_h3(1, 2 * Din, Dm), L->live_group_ptr, nullptr, T, Ex, Dm, 2 * Din,
+                             1.0f / (BL_H3_ROW_SCALE * BL_H3_W_SCALE), nullptr, V.pre, Dm, st));
+    }
+    {  // every message into a live node is live: the full target CSR, the segments live_nodes, the items' rows through msg_pos
+      ProfScope ps(2, 0.0, st, false);
+      BL_TRY(bl_segment_max_fwd_impl(V.pre, Dm, L->tgt_ptr, L->tgt_msgs, Nx, Dm, L->msg_act, S.agg, nullptr, L->ln_g, L->ln_b, L->ln_eps, nullptr,
+                                     S.mean, S.rstd, S.dact, S.bits, L->live_nodes, (uint16_t*)S.ln_out, 0, st, V.msg_pos, Ex));
+    }
+    {
+      ProfScope ps(3, 2.0 * Nx * (double)Dm * Dout, st, false);
+      bl_rows_packed_t d;
+      d.xp[0] = (const uint16_t*)S.ln_out; d.xp[1] = d.xp[2] = nullptr; d.idx[0] = L->live_nodes; d.idx[1] = d.idx[2] = nullptr;
+      d.width[0] = Dm; d.width[1] = d.width[2] = 0; d.nsrc = 1;
+      BL_TRY(bl_gemm_rows_x6_epi_rows(&d, L->Wd_packed, Nx, Dout, Dm, L->bd, BL_ACT_TANH, L->drop, L->live_nodes, N, h_out, Dout, st));
+    }
+    return BL_OK;
+  }
   if (h3) {
     ProfScope ps(0, 0.0, st, false);
     BL_TRY(bl_pack_f16x2(h_lo, ld_lo, N, h_hi ? width_lo : Din, Din, 0, BL_H3_ROW_SCALE, nullptr, S.hp, st));
@@ -492,9 +639,14 @@ extern "C" int bl_mp_layer_bwd(const bl_mp_layer_t* L, const float* h_out, const
   // f16x1, sum / mean, the deterministic mode, Din not a multiple of 128, the vector-unit input gradient) keeps the full backward.
   const int Ex = L->live_num_msgs, Rx = L->live_num_runs;
   const size_t live_ga_bytes = al(((size_t)Ex + Rx) * Din * 4);
-  const bool live = run_rows && fused_node && live_bwd_on() && layer_has_live(L) &&
-                    ((uint64_t)N * (uint64_t)Dout < (1ull << 32) || L->drop.p <= 0.f) &&  // (the dropout counter is the node's own row)
-                    live_ga_bytes + ((size_t)Ex + Rx) * (Dm / 32) * 4 <= (size_t)E * 2 * Din * 4;  // (compact masks behind the compact g_a)
+  // (the conditions are live_ok()'s, the same function the caller asked before a live FORWARD)
+  const char* why_not = "the run-row path or the one-kernel node update does not apply";
+  const bool live = run_rows && fused_node && live_ok(L, w_packed_bwd != nullptr, false, false, &why_not);
+  if (L->live_fwd && !live) {  // forward left the saved state valid on the live rows only: the full backward would read garbage
+    bl_set_error("bl_mp_layer_bwd: this layer's forward ran over its live rows, but backward cannot take the live path: %s (a switch "
+                 "was changed between forward and backward?)", why_not);
+    return BL_EINVAL;
+  }
   const int Nn = live ? L->live_num_nodes : N;  // rows of the node update's backward and of everything it writes
   uint32_t* live_bits = live ? (uint32_t*)((char*)B.g_a + live_ga_bytes) : nullptr;
   // f16x3 message GEMMs: gq leaves its producer in fp32 (B.g_ln); its packed form is made below, once its amax is known
